@@ -10,7 +10,16 @@ configuration the metric is quoted on -- 3-D Poisson 512^3 fp64, periodic BCs, C
 decomposed along axis 0 for N > 1 (strong scaling: the global grid is fixed).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5|c4|c4t|c4_512|c1|c3b|c3j]
-                    [--size n0,n1,n2]
+                    [--size n0,n1,n2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W steps), times the K steps, and prints the line: ``value``, ``ms_per_step``
+(wall time of the K timed steps / K) and what can be derived from them.  ``--full`` adds everything
+that takes work of its own: the plain-copy yardstick of the box, GPU clocks during the timed region, the
+placement-search probe, the per-kernel roofline probe and the CPU baseline (the last two can still be
+switched off with --no-roofline-probe / --no-cpu-baseline).  ``--dump-outputs DIR`` writes what the timed
+path computed in its last step (the solution array, and the solver report's stop-test value and r.r)
+as DIR/<name>.npy in float32 / float64, before any --full probe moves it on; an array larger than its share
+of 64 MB is written as a fixed, seeded sample of its elements.  The inputs are synthetic and deterministic.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 ``python -m torch.distributed.run`` on 127.0.0.1, one rank per GPU; the parent never touches the GPU),
@@ -20,6 +29,7 @@ relays rank 0's JSON line and returns the child's exit code.  Under an external
 from __future__ import annotations
 
 import argparse
+import contextlib
 import hashlib
 import json
 import math
@@ -56,6 +66,7 @@ WORKLOADS = {
     "c3j": ("jacobi3", (512, 512, 512), "double", "periodic", (1.0, 1.0, 1.0), 3),
 }
 ALG_PASSES_ONESHOT = {"bicgstab": 22, "jacobi3": 3}   # array passes per iteration, algorithmic count
+DUMP_SHARE_BYTES = 32 * 2 ** 20   # --dump-outputs: per array; at most two arrays per process (64 MB in all)
 
 
 def log(msg):
@@ -233,6 +244,30 @@ def gaussian(X, Y, Z):
 
 def euler_params(dx, u=1.0, nu=1e-3):
     return nu, 0.2 * min(dx * dx / (6 * nu), dx / abs(u))
+
+
+def dump_outputs(out_dir, arrays, share_bytes=DUMP_SHARE_BYTES):
+    """--dump-outputs: each tensor of ``arrays`` (name -> tensor) as out_dir/<name>.npy, flattened, in its own
+    precision (float32 / float64).  One larger than ``share_bytes`` is written as a sample of its elements at indices
+    drawn from a fixed seed: the same indices for the same size in every run, so that two builds compare cell by cell."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        assert flat.dtype in (torch.float32, torch.float64), f"{name}: {flat.dtype}"
+        keep = share_bytes // flat.element_size()
+        if flat.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), size=keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.cpu().numpy())
+    log(f"outputs of the last timed step written to {out_dir}: {', '.join(arrays)}")
+
+
+def report_array(rep):
+    """What the solver's report hands its caller besides x: the stop-test value and r.r, as a float64 array."""
+    import torch
+    return torch.tensor([rep.tol, rep.rr], dtype=torch.float64)
 
 
 def host_mem_available() -> int:
@@ -505,9 +540,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="c3", choices=list(WORKLOADS))
     ap.add_argument("--size", dest="n", default=None, help="override global node counts n0,n1[,n2] (testing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline-probe", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-roofline-probe", action="store_true", help="with --full: no per-kernel roofline probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the box yardstick, clocks, placement probe, roofline probe and CPU baseline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    probe_roofline = args.full and not args.no_roofline_probe
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: be the launcher (before anything can touch the GPU)
@@ -626,76 +668,83 @@ def main():
         e1 = torch.cuda.Event(enable_timing=True)
         log("array bases: x %#x rhs %#x (ctx-owned r / d buffers: hipMalloc, 2 MiB-aligned)" % (var().data_ptr(), rhs.data_ptr()))
         box = {}
-        try:   # how much of the card is free: a box whose GiB-sized allocations run slow is worth a look at this
-            free_b, total_b = torch.cuda.mem_get_info()
-            log(f"device memory: {free_b / 2**30:.1f} GiB free of {total_b / 2**30:.1f} GiB")
-            box["free_gib"] = round(free_b / 2 ** 30, 1)
-        except Exception:
-            pass
-        try:
-            # The yardstick of THIS box: a plain device copy of an array of the workload's size (1 read + 1 write).  The CG
-            # phases of 512^3 measure 853 us on some boxes and 990 us on others with the same bytes moved (DESIGN.md
-            # section 8); the copy says what the box gives a kernel that does nothing else.
-            src = var()[0]
-            dst = torch.empty_like(src)
-            for _ in range(2):
-                dst.copy_(src)
-            torch.cuda.synchronize()
-            c0 = torch.cuda.Event(enable_timing=True)
-            c1 = torch.cuda.Event(enable_timing=True)
-            c0.record()
-            for _ in range(5):
-                dst.copy_(src)
-            c1.record()
-            torch.cuda.synchronize()
-            cms = c0.elapsed_time(c1) / 5
-            box["copy_ms"] = cms
-            box["copy_GBs"] = 2 * src.numel() * src.element_size() / (cms * 1e-3) / 1e9
-            log(f"this box: torch copy_ of one {src.numel() * src.element_size() / 2**20:.0f} MiB array {cms * 1e3:.1f} us = {box['copy_GBs']:.0f} GB/s")
-            del dst
-        except Exception:
-            pass
-        with ClockSampler(local_rank) as clk:
+        if args.full:
+            try:   # how much of the card is free: a box whose GiB-sized allocations run slow is worth a look at this
+                free_b, total_b = torch.cuda.mem_get_info()
+                log(f"device memory: {free_b / 2**30:.1f} GiB free of {total_b / 2**30:.1f} GiB")
+                box["free_gib"] = round(free_b / 2 ** 30, 1)
+            except Exception:
+                pass
+            try:
+                # The yardstick of THIS box: a plain device copy of an array of the workload's size (1 read + 1 write).  The CG
+                # phases of 512^3 measure 853 us on some boxes and 990 us on others with the same bytes moved (DESIGN.md
+                # section 8); the copy says what the box gives a kernel that does nothing else.
+                src = var()[0]
+                dst = torch.empty_like(src)
+                for _ in range(2):
+                    dst.copy_(src)
+                torch.cuda.synchronize()
+                c0 = torch.cuda.Event(enable_timing=True)
+                c1 = torch.cuda.Event(enable_timing=True)
+                c0.record()
+                for _ in range(5):
+                    dst.copy_(src)
+                c1.record()
+                torch.cuda.synchronize()
+                cms = c0.elapsed_time(c1) / 5
+                box["copy_ms"] = cms
+                box["copy_GBs"] = 2 * src.numel() * src.element_size() / (cms * 1e-3) / 1e9
+                log(f"this box: torch copy_ of one {src.numel() * src.element_size() / 2**20:.0f} MiB array {cms * 1e3:.1f} us = {box['copy_GBs']:.0f} GB/s")
+                del dst
+            except Exception:
+                pass
+        clk = ClockSampler(local_rank) if args.full else contextlib.nullcontext()
+        with clk:
             t0 = time.perf_counter()
             e0.record(ctx.stream)
             ctx.cg_iterate(K)
             e1.record(ctx.stream)
             torch.cuda.synchronize()
             secs = time.perf_counter() - t0
-        clocks = clk.record()
-        log(f"clocks / power during the timed region: {clocks}")
+        if args.full:
+            clocks = clk.record()
+            log(f"clocks / power during the timed region: {clocks}")
         ev_ms = e0.elapsed_time(e1)
         rep = ctx.report()
         assert rep.itr == W + K and rep.status == 0, f"work was skipped: itr={rep.itr} status={rep.status}"
         assert bool(torch.isfinite(var()).all()), "iterate became non-finite inside the timed region"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"x": var()[0], "report": report_array(rep)})
         # The online placement search (csrc/pa_place.hip) rides on the iterations above -- warm-up and timed region
         # alike, its copies and memsets included in `value`.  What it has done so far, and what the SAME solve reaches
-        # once its pass is over (at most BENCH_STEADY_MAX more iterations, then K timed ones): `probe`.
-        st = ctx.place_stats()
-        probe = {"mode": "online (pa_place.hip): trials ride on the solve's own iterations, no set-up cost",
-                 "state_after_timed_region": st["state"], "trials": int(st["trials"]), "kept": int(st["kept"])}
-        if st["state"] != "off" and STEADY_MAX > 0:
-            extra = 0
-            while extra < STEADY_MAX and ctx.place_stats()["state"] == "searching":
-                ctx.cg_iterate(8)
-                torch.cuda.synchronize()
-                extra += 8
-            q0 = torch.cuda.Event(enable_timing=True)
-            q1 = torch.cuda.Event(enable_timing=True)
-            q0.record(ctx.stream)
-            ctx.cg_iterate(K)
-            q1.record(ctx.stream)
-            torch.cuda.synchronize()
+        # once its pass is over (at most BENCH_STEADY_MAX more iterations, then K timed ones): `probe` (--full).
+        probe = None
+        if args.full:
             st = ctx.place_stats()
-            probe.update({"state": st["state"], "trials": int(st["trials"]), "kept": int(st["kept"]),
-                          "allocations": int(st["allocations"]), "iterations_until_steady": W + K + extra,
-                          "steady_ms_per_step": q0.elapsed_time(q1) / K,
-                          "as_allocated_ms_per_step": st["first_pair_us"] / 2e3, "best_ms_per_step": st["best_pair_us"] / 2e3,
-                          "spent_ms": st["spent_us"] / 1e3, "timed_ms": st["timed_us"] / 1e3})
-            gain = (st["first_pair_us"] - st["best_pair_us"]) / 2.0
-            probe["break_even_iterations"] = (st["spent_us"] / gain) if gain > 1.0 else None
-            log(f"placement search: {probe}")
-        if not args.no_roofline_probe:
+            probe = {"mode": "online (pa_place.hip): trials ride on the solve's own iterations, no set-up cost",
+                     "state_after_timed_region": st["state"], "trials": int(st["trials"]), "kept": int(st["kept"])}
+            if st["state"] != "off" and STEADY_MAX > 0:
+                extra = 0
+                while extra < STEADY_MAX and ctx.place_stats()["state"] == "searching":
+                    ctx.cg_iterate(8)
+                    torch.cuda.synchronize()
+                    extra += 8
+                q0 = torch.cuda.Event(enable_timing=True)
+                q1 = torch.cuda.Event(enable_timing=True)
+                q0.record(ctx.stream)
+                ctx.cg_iterate(K)
+                q1.record(ctx.stream)
+                torch.cuda.synchronize()
+                st = ctx.place_stats()
+                probe.update({"state": st["state"], "trials": int(st["trials"]), "kept": int(st["kept"]),
+                              "allocations": int(st["allocations"]), "iterations_until_steady": W + K + extra,
+                              "steady_ms_per_step": q0.elapsed_time(q1) / K,
+                              "as_allocated_ms_per_step": st["first_pair_us"] / 2e3, "best_ms_per_step": st["best_pair_us"] / 2e3,
+                              "spent_ms": st["spent_us"] / 1e3, "timed_ms": st["timed_us"] / 1e3})
+                gain = (st["first_pair_us"] - st["best_pair_us"]) / 2.0
+                probe["break_even_iterations"] = (st["spent_us"] / gain) if gain > 1.0 else None
+                log(f"placement search: {probe}")
+        if probe_roofline:
             # per-kernel durations of the two dominant kernels, HIP events on the launch stream
             ctx.profile(True)
             ctx.cg_iterate(min(K, 10))
@@ -760,7 +809,12 @@ def main():
         rep = drv.be.report()
         assert rep.itr == W + K and rep.status == 0, f"work was skipped: itr={rep.itr} status={rep.status}"
         assert bool(torch.isfinite(var()).all()), "iterate became non-finite inside the timed region"
-        if not args.no_roofline_probe:
+        if args.dump_outputs:
+            # every rank its own slab (the ranks share the 64 MB); the report is the same on every rank
+            dump_outputs(args.dump_outputs, {f"x_rank{rank}": var()[0]}, DUMP_SHARE_BYTES // world)
+            if rank == 0:
+                dump_outputs(args.dump_outputs, {"report": report_array(rep)})
+        if probe_roofline:
             pr = drv.profile(min(K, 10))
             dom = "b" if pr["phase_b_ms"] >= pr["phase_a_ms"] else "a"
             roof = roofline(f"cg_phase_{dom}", pr[f"phase_{dom}_ms"], ALG_PASSES_PHASE[dom] * esize * mesh.N,
@@ -793,27 +847,28 @@ def main():
         cur = ctx.euler_march(a, b, kindc, u, nu, dts, W)
         oth = b if cur is a else a
         torch.cuda.synchronize()
-        try:
-            # The yardstick of THIS box for a step's arrays: a plain device copy of one of them into the other (1 read + 1
-            # write, the same two allocations, warm).  At 256^3 fp32 both arrays (64 MiB each) sit in the 256 MiB Infinity
-            # Cache, so this -- not 8 TB/s of HBM -- is the ceiling a 2-pass kernel can be held against.
-            for _ in range(3):
-                oth.copy_(cur)
-            torch.cuda.synchronize()
-            c0 = torch.cuda.Event(enable_timing=True)
-            c1 = torch.cuda.Event(enable_timing=True)
-            c0.record()
-            for _ in range(20):
-                oth.copy_(cur)
-            c1.record()
-            torch.cuda.synchronize()
-            cms = c0.elapsed_time(c1) / 20
-            box = {"copy_ms": cms, "copy_GBs": 2 * cur.numel() * cur.element_size() / (cms * 1e-3) / 1e9,
-                   "what": f"torch copy_ between the step's two {cur.numel() * cur.element_size() / 2**20:.0f} MiB arrays, warm "
-                           "(Infinity-Cache resident when they fit 256 MiB)"}
-            log(f"this box: copy between the step's arrays {cms * 1e3:.1f} us = {box['copy_GBs']:.0f} GB/s")
-        except Exception:
-            pass
+        if args.full:
+            try:
+                # The yardstick of THIS box for a step's arrays: a plain device copy of one of them into the other (1 read + 1
+                # write, the same two allocations, warm).  At 256^3 fp32 both arrays (64 MiB each) sit in the 256 MiB Infinity
+                # Cache, so this -- not 8 TB/s of HBM -- is the ceiling a 2-pass kernel can be held against.
+                for _ in range(3):
+                    oth.copy_(cur)
+                torch.cuda.synchronize()
+                c0 = torch.cuda.Event(enable_timing=True)
+                c1 = torch.cuda.Event(enable_timing=True)
+                c0.record()
+                for _ in range(20):
+                    oth.copy_(cur)
+                c1.record()
+                torch.cuda.synchronize()
+                cms = c0.elapsed_time(c1) / 20
+                box = {"copy_ms": cms, "copy_GBs": 2 * cur.numel() * cur.element_size() / (cms * 1e-3) / 1e9,
+                       "what": f"torch copy_ between the step's two {cur.numel() * cur.element_size() / 2**20:.0f} MiB arrays, warm "
+                               "(Infinity-Cache resident when they fit 256 MiB)"}
+                log(f"this box: copy between the step's arrays {cms * 1e3:.1f} us = {box['copy_GBs']:.0f} GB/s")
+            except Exception:
+                pass
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
@@ -824,8 +879,10 @@ def main():
         secs = time.perf_counter() - t0
         ev_ms = e0.elapsed_time(e1)
         assert bool(torch.isfinite(fin).all()), "state became non-finite inside the timed region"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"phi": fin})
         passes = 2 if solver == "euler" else 3
-        if not args.no_roofline_probe:
+        if probe_roofline:
             ctx.profile(True)
             ctx.euler_march(fin, cur if fin is oth else oth, kindc, u, nu, dts, min(K, 10))
             pr = ctx.profile_read()
@@ -874,16 +931,19 @@ def main():
         ev_ms = rep.gpu_ms
         assert rep.itr == K and rep.status == 0, f"work was skipped: itr={rep.itr} status={rep.status}"
         assert bool(torch.isfinite(var()).all()), "iterate became non-finite inside the timed region"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"x": var()[0], "report": report_array(rep)})
         passes = ALG_PASSES_ONESHOT[solver]
         moved = {"bicgstab": 15, "jacobi3": 3}[solver]
-        roof = roofline(f"{method} iteration (all kernels of the loop: stream time of the iterations / K)", ev_ms / K,
-                        passes * esize * mesh.N, args.workload, True,
-                        {"remark": f"{passes} array passes per iteration by the algorithmic count, {moved} really moved "
-                                   "(DESIGN.md section 4); per-kernel table: profiles/r04_bicgstab512_kernel_stats.csv; "
-                                   "frac can exceed 1 on the algorithmic count because fused phases never store "
-                                   "what the count assumes stored -- frac_moved prices the passes the loop really makes",
-                         "passes_moved": moved,
-                         "frac_moved": moved * esize * mesh.N / (ev_ms / K * 1e-3) / 1e9 / HBM_PEAK_GBS})
+        if args.full:
+            roof = roofline(f"{method} iteration (all kernels of the loop: stream time of the iterations / K)", ev_ms / K,
+                            passes * esize * mesh.N, args.workload, True,
+                            {"remark": f"{passes} array passes per iteration by the algorithmic count, {moved} really moved "
+                                       "(DESIGN.md section 4); per-kernel table: profiles/r04_bicgstab512_kernel_stats.csv; "
+                                       "frac can exceed 1 on the algorithmic count because fused phases never store "
+                                       "what the count assumes stored -- frac_moved prices the passes the loop really makes",
+                             "passes_moved": moved,
+                             "frac_moved": moved * esize * mesh.N / (ev_ms / K * 1e-3) / 1e9 / HBM_PEAK_GBS})
         wl_text = (f"3-D Poisson {gn[0]}x{gn[1]}x{gn[2]} {dtype}, {kind} BCs, "
                    f"{'BiCGSTAB' if method == 'bicgstab' else 'Jacobi'} (BASELINE config {cfg_no}'s mesh)")
     else:  # jacobi (config 1)
@@ -906,9 +966,11 @@ def main():
         ev_ms = rep.gpu_ms
         assert rep.itr == K and rep.status == 0, f"work was skipped: itr={rep.itr}"
         assert bool(torch.isfinite(var()).all())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"x": var()[0], "report": report_array(rep)})
         passes = 3
         res_wg = ctx.resident_used()
-        if res_wg > 0:
+        if res_wg > 0 and args.full:
             # small mesh: the whole solve ran as ONE cooperative launch with the fields in LDS (pa_resident.hip);
             # there is no per-sweep kernel to bracket, a sweep costs stream time / sweeps
             roof = roofline("k_resident (Jacobi, whole solve in one launch)", ev_ms / K, passes * esize * mesh.N, args.workload,
@@ -916,7 +978,7 @@ def main():
                                                      "bound by the grid-wide step of a sweep (one agent-scope arrive + wait), "
                                                      "not by HBM; kernel_ms = stream time of the solve / sweeps",
                                            "resident_workgroups": res_wg})
-        elif not args.no_roofline_probe:
+        elif res_wg == 0 and probe_roofline:
             ctx.profile(True)
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
@@ -962,8 +1024,9 @@ def main():
         if solver == "cg" and not slab:
             out["setup_ms"] = setup["wall_ms"]
             out["setup"] = setup
-            out["probe"] = probe
-        if not args.no_cpu_baseline and world == 1 and not slab:   # reported baseline: rank 0 at N = 1 only
+            if probe is not None:
+                out["probe"] = probe
+        if args.full and not args.no_cpu_baseline and world == 1 and not slab:   # reported baseline: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(solver, kind, dtype, gn)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

@@ -12,7 +12,7 @@ REPO="${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$REPO/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B=(python3 "$REPO/bench.py" --workload "$WL" "${ARGS[@]}" --no-cpu-baseline)
+B=(python3 "$REPO/bench.py" --workload "$WL" "${ARGS[@]}" --full --no-cpu-baseline)
 # Every pass's exit code is recorded (exit_codes.txt) and the script fails if one of them did: a collection that
 # crashed must not read as clean.  Known: under rocprofv3 7.2 ANY process that has made a cooperative launch dies
 # with SIGSEGV in libhsa-runtime64 inside exit() (profiles/README.md; tools/coop_exit_repro.sh shows it with an

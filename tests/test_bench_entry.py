@@ -23,6 +23,19 @@ def _run(args, env_extra, timeout=600):
     return p
 
 
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def _record(p):
+    assert p.returncode == 0, p.stderr[-3000:]
+    return json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][0])
+
+
 def test_self_launch_without_gpu_fails_loudly_and_returns():
     """No GPU here: the ranks must die on their own assertion (there is no CPU path), the parent must
     relay a non-zero exit code and must not hang or print a JSON line."""
@@ -36,9 +49,10 @@ def test_self_launch_without_gpu_fails_loudly_and_returns():
 
 
 @pytest.mark.gpu
-def test_self_launch_two_ranks_one_gpu():
+def test_self_launch_two_ranks_one_gpu(tmp_path):
     """the driver's command shape, N = 2, through the NEW entry path (parent -> torch.distributed.run -> ranks)"""
-    p = _run(["--gpus", "2", "--size", "48,40,136", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"],
+    p = _run(["--gpus", "2", "--size", "48,40,136", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
+              "--dump-outputs", str(tmp_path)],
              {"BENCH_SINGLE_DEVICE": "1", "BENCH_BACKEND": "gloo"})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -47,6 +61,7 @@ def test_self_launch_two_ranks_one_gpu():
     assert rec["n_gpus"] == 2 and rec["steps"] == 4 and rec["warmup"] == 2
     assert rec["config"]["parallelism"].startswith("slab2")
     assert rec["value"] > 0 and rec["roofline"]["kernel"].startswith("cg_phase_")
+    assert sorted(os.listdir(tmp_path)) == ["report.npy", "x_rank0.npy", "x_rank1.npy"]
 
 
 @pytest.mark.gpu
@@ -66,21 +81,57 @@ def test_slab_bench_library_side_rccl_one_rank():
 @pytest.mark.parametrize("wl,size", [("c4", "40,36,72"), ("c4t", "40,36,72"), ("c1", "64,64"), ("c2", "40,36,72"),
                                      ("c5", "40,36,72")])
 def test_every_workload_runs(wl, size):
-    p = _run(["--workload", wl, "--size", size, "--steps", "6", "--warmup", "2", "--no-cpu-baseline"], {})
+    p = _run(["--workload", wl, "--size", size, "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"], {})
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][0])
     assert rec["steps"] == 6 and rec["value"] > 0 and rec["n_gpus"] == 1
     assert "roofline" in rec and rec["roofline"]["kernel_ms"] > 0
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("wl,size", [("c3", "48,40,136"), ("c4", "40,36,72")])
+def test_plain_run_is_lean_and_dumps_what_full_computes(wl, size, tmp_path):
+    """A plain run prints the headline line without the measurements of --full; the outputs it dumps are the ones a
+    --full run of the same arguments dumps, bit for bit (--full's probes run after the outputs are taken)."""
+    import numpy as np
+    args = ["--workload", wl, "--size", size, "--steps", "6", "--warmup", "2"]
+    plain = _record(_run(args + ["--dump-outputs", str(tmp_path / "plain")], {}))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain
+    assert plain["steps"] == 6 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert not {"roofline", "cpu_baseline", "probe", "clocks", "box"} & set(plain)
+    full = _record(_run(args + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")], {}))
+    assert "roofline" in full
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names and names == sorted(os.listdir(tmp_path / "full"))
+    for name in names:
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.dtype == b.dtype and a.dtype in (np.float32, np.float64)
+        assert np.array_equal(a, b), name
+
+
+def test_dump_outputs_samples_a_large_array_the_same_way_every_run(tmp_path):
+    """--dump-outputs on the host: an array within its share is written whole, a larger one as a fixed sample of its
+    elements -- the same indices in every run -- and every file is float32 / float64."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+    big = torch.arange(10000, dtype=torch.float64)
+    small = torch.linspace(0, 1, 10, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small}, share_bytes=800)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (100,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and set(a.tolist()) <= set(big.tolist())
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.numpy())
+
+
 def test_launcher_budget_and_first_attempt_record(monkeypatch, capsys):
     """launch_ranks on the host only (the attempts are stand-ins): a first attempt that times out is followed by
     ONE attempt on the stepwise driver with what is left of the budget -- both inside the driver's 600 s -- and the
     relayed record carries how the first attempt ended; a refused configuration is not retried."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
-    bench = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bench)
+    bench = _load_bench()
     calls = []
     clock = [0.0]
 
