@@ -289,7 +289,7 @@ int pa_cg_finish_iter(pa_ctx* ctx);
  * returns, so pa_report_read / pa_cg_end see the same state as after n x { phase_a, phase_b }. */
 int pa_cg_iterate(pa_ctx* ctx, int64_t n);
 int pa_cg_end(pa_ctx* ctx, pa_report* out);       /* synchronises */
-int pa_cg_abort(pa_ctx* ctx);                     /* drop the live stepwise solve (no read-back) */
+int pa_cg_abort(pa_ctx* ctx);                     /* drop the live stepwise solve, CG, BiCGSTAB or Jacobi (no read-back) */
 /* ---- stepwise BiCGSTAB on a slab (linalg.py:162-279 split at its reductions and exchanges; SURVEY 8e + 8f-1) ----
  * BASELINE config 3 is periodic: CG never meets the reference's stop test there, BiCGSTAB does -- so it has
  * to exist on slabs.  A host driver (pyapes_amd/slab.py SlabBiCGSTAB) puts the communication between the calls:

@@ -1,6 +1,6 @@
 // mallocbench.hip -- what an allocation costs on this part: hipMalloc / hipFree wall time by size, the rate of a
 // hipMemsetAsync and of a device-to-device copy of the same block (the price list of the online placement search of
-// the CG set-up, pa_solver.hip).  hipcc --offload-arch=gfx950 -O2 mallocbench.hip -o mallocbench
+// the CG set-up, pa_cg.hip / pa_place.hip).  hipcc --offload-arch=gfx950 -O2 mallocbench.hip -o mallocbench
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>

@@ -10,13 +10,16 @@ OBJ="$HERE/build"
 mkdir -p "$OUT" "$OBJ"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-variable ${PA_EXTRA_FLAGS:-})
+TUS=(pa_core pa_bc pa_ops pa_solver pa_cg pa_bicgstab pa_jacobi pa_cg3d pa_cg3d_b pa_sf pa_comm pa_rfp pa_resident pa_place)
 pids=()
-for tu in pa_core pa_bc pa_ops pa_solver pa_cg3d pa_cg3d_b pa_sf pa_comm pa_rfp pa_resident pa_place; do
+objs=()
+for tu in "${TUS[@]}"; do
   "$HIPCC" "${FLAGS[@]}" -c "$HERE/$tu.hip" -o "$OBJ/$tu.o" &
   pids+=($!)
+  objs+=("$OBJ/$tu.o")
 done
 for p in "${pids[@]}"; do wait "$p"; done
-"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpyapes_hip.so" "$OBJ/pa_core.o" "$OBJ/pa_bc.o" "$OBJ/pa_ops.o" "$OBJ/pa_solver.o" "$OBJ/pa_cg3d.o" "$OBJ/pa_cg3d_b.o" "$OBJ/pa_sf.o" "$OBJ/pa_comm.o" "$OBJ/pa_rfp.o" "$OBJ/pa_resident.o" "$OBJ/pa_place.o" -ldl
+"$HIPCC" --offload-arch=gfx950 -shared -fPIC -o "$OUT/libpyapes_hip.so" "${objs[@]}" -ldl
 echo "built $OUT/libpyapes_hip.so"
 # TEST-ONLY: the stand-in for librccl that lets the multi-rank tests run their ranks as processes sharing one GPU
 # (tests/lib/pa_hostring.hip; handed to the library through pa_comm_use_impl(path), never linked into it)

@@ -506,6 +506,14 @@ __global__ void __launch_bounds__(PA_BLOCK) k_bc_pair(DevGeom G, T* __restrict__
 }
 
 // ---- host side ----------------------------------------------------------------------------------
+// (the three launch sequences below are this file's own: the solvers reach them through pa_bc_fill_start / _step)
+template <typename T>
+static int pa_bc_shell_fused(pa_ctx* c, T* x, double* part2, int with_delta, bool guarded, int* nsh, bool standalone);
+template <typename T>
+static int pa_bc_pair_apply(pa_ctx* c, T* x, double* part2, int mode, bool guarded, int* nsh);
+template <typename T>
+static void pa_shell_launch(pa_ctx* c, const T* x, T* shell, double* part2, int with_delta);
+
 template <typename T>
 int pa_bc_apply_faces(pa_ctx* c, T* x, bool guarded) {
   const DevGeom& G = c->G;
@@ -675,7 +683,7 @@ static int bc_fill_all(pa_ctx* c, BCAll<T>& B) {
 
 // fills x; with_delta: partial sums of (new - old)^2 over the shell -> part2 (returns #blocks via *nsh)
 template <typename T>
-int pa_bc_shell_fused(pa_ctx* c, T* x, double* part2, int with_delta, bool guarded, int* nsh,
+static int pa_bc_shell_fused(pa_ctx* c, T* x, double* part2, int with_delta, bool guarded, int* nsh,
                           bool standalone) {
   BCAll<T> B;
   int rc = bc_fill_all<T>(c, B);
@@ -775,7 +783,7 @@ static void bc_face_args(pa_ctx* c, int f, BCArgs<T>& B, bool guarded) {
 // mode 0: fill only; 1: fill + shell delta (partials -> part2, rows returned in *nsh) + save; 2: fill + save;
 // 3: save only (slab: the driver has filled the BCs itself)
 template <typename T>
-int pa_bc_pair_apply(pa_ctx* c, T* x, double* part2, int mode, bool guarded, int* nsh) {
+static int pa_bc_pair_apply(pa_ctx* c, T* x, double* part2, int mode, bool guarded, int* nsh) {
   const DevGeom& G = c->G;
   const int64_t sz[3] = {G.n1 * G.n2, G.n0 * G.n2, G.n0 * G.n1};
   int64_t start[6], total = 0;
@@ -829,17 +837,47 @@ int pa_bc_shell_rows(const pa_ctx* c) {
 // boundary-shell pass on its own (after a face-by-face fill): save the shell, with_delta: + partial sums of
 // (new - old)^2 -> part2 (pa_shell_blocks rows)
 template <typename T>
-void pa_shell_launch(pa_ctx* c, const T* x, T* shell, double* part2, int with_delta) {
+static void pa_shell_launch(pa_ctx* c, const T* x, T* shell, double* part2, int with_delta) {
   hipLaunchKernelGGL(k_shell<T>, dim3(pa_shell_blocks(c)), dim3(PA_BLOCK), 0, c->stream, c->G, c->sc, x, shell, part2,
                      with_delta);
+}
+
+// ---- the solvers' BC fill (CG, Jacobi; BiCGSTAB fills through pa_bc_apply_auto) ------------------------------------
+void pa_bc_plan(pa_ctx* c) {
+  c->bc_static = pa_bc_is_static(c);
+  c->bc_fused = pa_bc_fusable(c);
+  c->bc_pair = (!c->bc_fused && pa_bc_pairable(c)) ? 1 : 0;
+  c->shell_cur = 0;
+}
+
+template <typename T>
+int pa_bc_fill_start(pa_ctx* c, T* x, bool filled_by_driver) {
+  if (c->bc_fused && !filled_by_driver)   // fill + remember the filled shell as x_old in one go
+    return pa_bc_shell_fused<T>(c, x, nullptr, 0, false, nullptr, false);
+  if (c->bc_pair) return pa_bc_pair_apply<T>(c, x, nullptr, filled_by_driver ? 3 : 2, false, nullptr);
+  if (!filled_by_driver)
+    if (int rc = pa_bc_apply_faces<T>(c, x)) return rc;
+  pa_shell_launch<T>(c, (const T*)x, (T*)c->scr[SCR_SHELL], (double*)c->scr[SCR_PART2], 0);
+  return PA_OK;
+}
+
+template <typename T>
+int pa_bc_fill_step(pa_ctx* c, T* x, double* part2, int* nsh) {
+  *nsh = 0;
+  if (c->bc_static) return PA_OK;
+  if (c->bc_fused) return pa_bc_shell_fused<T>(c, x, part2, 1, true, nsh, false);
+  if (c->bc_pair) return pa_bc_pair_apply<T>(c, x, part2, 1, true, nsh);
+  if (int rc = pa_bc_apply_faces<T>(c, x, true)) return rc;
+  *nsh = pa_shell_blocks(c);
+  pa_shell_launch<T>(c, (const T*)x, (T*)c->scr[SCR_SHELL], part2, 1);
+  return PA_OK;
 }
 
 #define PA_BC_INST(T)                                                                            \
   template int pa_bc_apply_faces<T>(pa_ctx*, T*, bool);                                          \
   template int pa_bc_apply_auto<T>(pa_ctx*, T*, bool);                                           \
-  template int pa_bc_shell_fused<T>(pa_ctx*, T*, double*, int, bool, int*, bool);                \
-  template int pa_bc_pair_apply<T>(pa_ctx*, T*, double*, int, bool, int*);                       \
-  template void pa_shell_launch<T>(pa_ctx*, const T*, T*, double*, int);
+  template int pa_bc_fill_start<T>(pa_ctx*, T*, bool);                                           \
+  template int pa_bc_fill_step<T>(pa_ctx*, T*, double*, int*);
 PA_BC_INST(float)
 PA_BC_INST(double)
 #undef PA_BC_INST

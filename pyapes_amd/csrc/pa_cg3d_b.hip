@@ -29,7 +29,7 @@ int pa_tile3d_bicg_pv(pa_ctx* c, const DevEq<T>& E, Vec<T> r, Vec<T> p, Vec<T> v
   return n;
 }
 
-// the same phase when p' already exists (k_bicg_x formed it, pa_solver.hip): v' = A p' on the interior set, r0 . v'
+// the same phase when p' already exists (k_bicg_x formed it, pa_bicgstab.hip): v' = A p' on the interior set, r0 . v'
 template <typename T>
 int pa_tile3d_bicg_v(pa_ctx* c, const DevEq<T>& E, Vec<T> p, const T* r0, T* vnew, double* partials) {
   const int mode = c->cg_pitch ? 3 : cg3d_mode<T>(c, E, {p.p, r0, vnew, p.glo, p.ghi}, true, false, true);

@@ -6,7 +6,7 @@
 //
 // Equation covered: one Laplacian term (scalar or no coefficient), any BC mix, fp64 / fp32,
 // single GPU or slab (ghost planes through Vec<T>).  Anything else returns 0 and the caller
-// launches the generic kernels of pa_solver.hip / pa_ops.hip.
+// launches the generic kernels of pa_cg.hip / pa_bicgstab.hip / pa_jacobi.hip / pa_ops.hip.
 //
 // Data movement (both phases are HBM-bound; no MFMA):
 //   phase A  reads r, d      writes d' = r + beta d          + sum d'.(A d')      3 array passes
@@ -117,7 +117,7 @@ __device__ __forceinline__ int64_t pa_wrapmod(int64_t v, int64_t n) {
 // LAY 0.  Only x, the caller's contiguous field, is touched cell by cell: phase A is fully vector, phase B on
 // three of its five streams.  A pad cell is never a neighbour anybody uses: the last real cell of a row is a
 // boundary node of a non-periodic axis, outside the interior set.  BiCGSTAB (phases 5, 6, 8): EVERY array of these
-// phases is the ctx's (r, p, v, r0, s, t) and pitched; only the x / r update (k_bicg_x, pa_solver.hip) touches x.
+// phases is the ctx's (r, p, v, r0, s, t) and pitched; only the x / r update (k_bicg_x, pa_bicgstab.hip) touches x.
 template <typename T, int RJ, int PHASE, bool CF = false, int KIND = 0, int LAY = 0>
 __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
   // PHASE 9 = the Jacobi sweep (phase 4) marching its chunks BACKWARDS: consecutive sweeps alternate, so the planes a sweep
@@ -805,7 +805,7 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
           T ax = axv[v];
           T cCk = cCkV[v];
           if (PH == 4) {
-            // Jacobi:  x + omega (b - A x) / diag(A)   (k_jacobi, pa_solver.hip)
+            // Jacobi:  x + omega (b - A x) / diag(A)   (k_jacobi, pa_jacobi.hip)
             T dg = act0 ? cCi : (T)0;
             dg = dg + cCj;
             dg = dg + cCk;
@@ -850,7 +850,7 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
           if (CF) ax = ax * cv[jj][v]; else ax = ax * cfe;
           ax = ax * sgn;
           if (PH == 4) {
-            // Jacobi:  x + omega (b - A x) / diag(A)   (k_jacobi, pa_solver.hip)
+            // Jacobi:  x + omega (b - A x) / diag(A)   (k_jacobi, pa_jacobi.hip)
             T dg = act0 ? cCi : (T)0;
             dg = dg + cCj;
             dg = dg + cCk;

@@ -378,10 +378,9 @@ int pa_comm_plan(pa_ctx* c, const pa_exchange* plan) {
 }
 
 int pa_cg_iterate_comm(pa_ctx* c, int64_t n) {
-  if (!c || !c->solver_live) { if (c) pa_set_err(c, "pa_cg_iterate_comm without pa_cg_begin"); return PA_E_STATE; }
+  if (int rc = pa_require_solve(c, PA_SOLVE_CG, "pa_cg_iterate_comm")) return rc;
   if (!c->slab || !c->ext_sums) { pa_set_err(c, "pa_cg_iterate_comm needs slab mode (pa_slab_set)"); return PA_E_STATE; }
   if (!c->comm || !c->plan_set) { pa_set_err(c, "pa_cg_iterate_comm needs pa_comm_init + pa_comm_plan"); return PA_E_STATE; }
-  PA_HIP(c, hipSetDevice(c->device));
   Rccl* R = rccl();
   ncclComm_t comm = (ncclComm_t)c->comm;
   double* sums = c->ext_sums;
@@ -454,10 +453,9 @@ int pa_cg_iterate_comm(pa_ctx* c, int64_t n) {
 // (include/pyapes_hip.h), the three small all-reduces and the two plane exchanges between them.  Iterations enqueued
 // after the device-side stop are no-ops (the collectives still run: every rank enqueues the same sequence).
 int pa_bicg_iterate_comm(pa_ctx* c, int64_t n) {
-  if (!c || c->solver_live != 2) { if (c) pa_set_err(c, "pa_bicg_iterate_comm without pa_bicg_begin"); return PA_E_STATE; }
+  if (int rc = pa_require_solve(c, PA_SOLVE_BICG, "pa_bicg_iterate_comm")) return rc;
   if (!c->slab || !c->ext_sums) { pa_set_err(c, "pa_bicg_iterate_comm needs slab mode (pa_slab_set)"); return PA_E_STATE; }
   if (!c->comm || !c->plan_set) { pa_set_err(c, "pa_bicg_iterate_comm needs pa_comm_init + pa_comm_plan"); return PA_E_STATE; }
-  PA_HIP(c, hipSetDevice(c->device));
   Rccl* R = rccl();
   ncclComm_t comm = (ncclComm_t)c->comm;
   double* sums = c->ext_sums;
@@ -481,10 +479,9 @@ int pa_bicg_iterate_comm(pa_ctx* c, int64_t n) {
 // |dx|^2 -> all-reduce -> first / last plane into the neighbours' ghost planes -> stop test.  Sweeps enqueued after the
 // device-side stop are no-ops (the collectives still run).
 int pa_jacobi_iterate_comm(pa_ctx* c, int64_t n) {
-  if (!c || c->solver_live != 3) { if (c) pa_set_err(c, "pa_jacobi_iterate_comm without pa_jacobi_begin"); return PA_E_STATE; }
+  if (int rc = pa_require_solve(c, PA_SOLVE_JACOBI, "pa_jacobi_iterate_comm")) return rc;
   if (!c->slab || !c->ext_sums) { pa_set_err(c, "pa_jacobi_iterate_comm needs slab mode (pa_slab_set)"); return PA_E_STATE; }
   if (!c->comm || !c->plan_set) { pa_set_err(c, "pa_jacobi_iterate_comm needs pa_comm_init + pa_comm_plan"); return PA_E_STATE; }
-  PA_HIP(c, hipSetDevice(c->device));
   Rccl* R = rccl();
   ncclComm_t comm = (ncclComm_t)c->comm;
   double* sums = c->ext_sums;

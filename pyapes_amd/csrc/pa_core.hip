@@ -1,8 +1,9 @@
 // pa_core.hip -- host infrastructure of libpyapes_hip: context, scratch, grid / coordinate system / BC list /
 // equation state behind the C ABI declared in include/pyapes_hip.h.  gfx950 only.
 // The kernels live beside the host code that launches them: pa_bc.hip (BC fill), pa_ops.hip (generic
-// operators, explicit entry points), pa_solver.hip (generic solver kernels, CG / Jacobi / BiCGSTAB
-// drivers), pa_cg3d*.hip (the tiled marching kernel), pa_rfp.hip, pa_comm.hip.
+// operators, explicit entry points), pa_cg.hip / pa_bicgstab.hip / pa_jacobi.hip (the CG / BiCGSTAB / Jacobi drivers
+// and their generic kernels) with pa_solver.hip (what they share), pa_cg3d*.hip (the tiled marching kernel), pa_rfp.hip,
+// pa_comm.hip.
 #include "pa_host.h"
 
 #include <dlfcn.h>
@@ -300,7 +301,7 @@ int pa_ctx_create(int device, void* hip_stream, pa_ctx** out) {
 
 int pa_ctx_set_stream(pa_ctx* c, void* hip_stream) {
   if (!c) return PA_E_ARG;
-  if (c->solver_live && (hipStream_t)hip_stream != c->stream) {
+  if (c->solve != PA_SOLVE_NONE && (hipStream_t)hip_stream != c->stream) {
     pa_set_err(c, "pa_ctx_set_stream during a stepwise solve");
     return PA_E_STATE;
   }
@@ -329,7 +330,7 @@ int pa_ctx_set_stream(pa_ctx* c, void* hip_stream) {
 
 int pa_ctx_set_option(pa_ctx* c, const char* name, int value) {
   if (!c || !name) return PA_E_ARG;
-  if (c->solver_live) { pa_set_err(c, "pa_ctx_set_option during a solve"); return PA_E_STATE; }
+  if (c->solve != PA_SOLVE_NONE) { pa_set_err(c, "pa_ctx_set_option during a solve"); return PA_E_STATE; }
   if (!strcmp(name, "fastpath")) c->fastpath = value != 0;      // tiled kernels (else the generic ones)
   else if (!strcmp(name, "sf")) c->sf = value != 0;             // k_sf (else k_cg3d's single-field phases)
   else if (!strcmp(name, "fold")) c->fold = value != 0;         // scalar steps in the next kernel's prologue
@@ -434,7 +435,7 @@ int pa_grid_set(pa_ctx* c, int ndim, const int64_t* n, const double* dx, int dty
   c->esize = dtype == PA_F64 ? 8 : 4;
   c->grid_set = 1;
   c->eq_set = 0;
-  c->solver_live = 0;
+  c->solve = PA_SOLVE_NONE;
   for (int f = 0; f < 6; ++f) c->bc[f] = HostBC();
   c->nbc = 0;
   c->coord = PA_COORD_XYZ;
@@ -463,14 +464,14 @@ int pa_coord_set(pa_ctx* c, int coord_sys, const void* r_nodes) {
   PA_HIP(c, hipGetLastError());
   c->coord = PA_COORD_RZ;
   c->rz_tab = c->scr[SCR_RZ];
-  c->solver_live = 0;
+  c->solve = PA_SOLVE_NONE;
   return PA_OK;
 }
 
 // The BC list and the equation are read again by every phase of a live stepwise solve (pa_cg_begin ...
 // pa_cg_end): changing them in between would silently change the fill and the stencil of the running solve.
 static int pa_refuse_live(pa_ctx* c, const char* what) {
-  if (!c->solver_live) return PA_OK;
+  if (c->solve == PA_SOLVE_NONE) return PA_OK;
   pa_set_err(c, "%s during a stepwise solve (pa_cg_begin ... pa_cg_end); end or abort it first", what);
   return PA_E_STATE;
 }
@@ -529,7 +530,7 @@ extern "C" {
 
 int pa_slab_set(pa_ctx* c, const pa_slab* s) {
   if (!c || !c->grid_set) { if (c) pa_set_err(c, "pa_slab_set before pa_grid_set"); return PA_E_STATE; }
-  if (c->solver_live) { pa_set_err(c, "pa_slab_set during a solve"); return PA_E_STATE; }
+  if (c->solve != PA_SOLVE_NONE) { pa_set_err(c, "pa_slab_set during a solve"); return PA_E_STATE; }
   if (!s) {
     c->slab = 0;
     c->ext_sums = nullptr;

@@ -74,6 +74,9 @@ struct PlaceSearch {
   double spent_us = 0.0, elapsed_us = 0.0, first_pair = 0.0;
 };
 
+// which stepwise solve is live on a context (pa_cg_begin / pa_bicg_begin / pa_jacobi_begin ... its end or pa_cg_abort)
+enum PaSolve { PA_SOLVE_NONE, PA_SOLVE_CG, PA_SOLVE_BICG, PA_SOLVE_JACOBI };
+
 struct pa_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -125,10 +128,12 @@ struct pa_ctx {
   double* ext_sums = nullptr;     // slab: caller-owned sums buffer (all-reduced by the host driver)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_switch = nullptr;   // pa_ctx_set_stream: orders the new stream after what the old one still holds
-  // CG state
-  int solver_live = 0, cur = 0, bc_static = 0, pending_init_logic = 0, b_blocks = 0;
-  int bc_pair = 0;  // per-axis pair kernels (lower + upper face + shell stop-test term in one launch)
-  int bc_fused = 0, shell_cur = 0;  // fused BC fill: which half of SCR_SHELL holds x_old on the shell
+  PaSolve solve = PA_SOLVE_NONE;
+  int cur = 0, pending_init_logic = 0, b_blocks = 0;
+  // BC fill of the live solve's iterate (pa_bc_plan): every face Dirichlet (no fill after the first), the closed form,
+  // the per-axis pair kernels (lower + upper face + shell stop-test term in one launch), else one launch per face
+  int bc_static = 0, bc_fused = 0, bc_pair = 0;
+  int shell_cur = 0;  // fused BC fill: which half of SCR_SHELL holds x_old on the shell
   void* cg_x = nullptr;
   const void* jac_rhs = nullptr;   // stepwise Jacobi on a slab (pa_jacobi_begin): the right-hand side and omega of the live solve
   double jac_omega = 1.0;
@@ -226,7 +231,9 @@ int pa_scratch(pa_ctx* c, void** slot, size_t* cap, size_t bytes);
 void pa_refresh_geom(pa_ctx* c);
 int pa_bc_apply_any(pa_ctx* c, void* x);
 int pa_check_eq_applicable(pa_ctx* c);   // pa_ops.hip: Grad inside a solver equation is 1-D only
-int pa_cg_slab_mid(pa_ctx* c);                // pa_solver.hip: the step between the phases of a folded slab iteration
+// pa_solver.hip: PA_OK (device selected) when the stepwise solve `kind` is live, else PA_E_STATE, error text naming `what`
+int pa_require_solve(pa_ctx* c, PaSolve kind, const char* what);
+int pa_cg_slab_mid(pa_ctx* c);                // pa_cg.hip: the step between the phases of a folded slab iteration
 int pa_cg_slab_flush(pa_ctx* c);              // close the last iteration of a folded batch (single-block kernel)
 int pa_bc_shell_rows(const pa_ctx* c);        // pa_bc.hip: partial rows the BC fill + shell pass of an iteration writes
 void pa_profile_stop(pa_ctx* c, int which);   // pa_solver.hip: close the HIP-event bracket of dominant kernel `which`
@@ -235,7 +242,7 @@ int pa_place_begin(pa_ctx* c, const void* x, size_t array_bytes);   // pa_cg_beg
 int pa_place_tick(pa_ctx* c);                                        // top of every iteration, before phase A
 int pa_place_batch_end(pa_ctx* c);                                   // after the last iteration a call enqueues
 void pa_place_r_written(pa_ctx* c);                                  // phase B has written r into c->cg_r_out
-int pa_place_prepare_block(pa_ctx* c, void* block);                  // pa_solver.hip: zero what the tiled phases never write
+int pa_place_prepare_block(pa_ctx* c, void* block);                  // zero what the tiled phases never write
 void pa_place_end(pa_ctx* c, int may_free);                          // the solve is over (or dropped); may_free: the stream has been waited for
 void pa_place_reset(pa_ctx* c);                                      // the arrays changed: free the pool, forget the pass
 void pa_place_destroy(pa_ctx* c);
@@ -250,12 +257,13 @@ template <typename T>
 int pa_bc_apply_faces(pa_ctx* c, T* x, bool guarded = false);   // one launch per face, list order
 template <typename T>
 int pa_bc_apply_auto(pa_ctx* c, T* x, bool guarded);            // fewest launches with the sequential semantics
+// the solvers' BC fill: pa_bc_plan picks the launch sequence of a solve; _start fills x (not when the slab driver has)
+// and records its shell (x_old of the first stop test); _step fills + shell term, *nsh rows into part2 (0: bc_static)
+void pa_bc_plan(pa_ctx* c);
 template <typename T>
-int pa_bc_shell_fused(pa_ctx* c, T* x, double* part2, int with_delta, bool guarded, int* nsh, bool standalone);
+int pa_bc_fill_start(pa_ctx* c, T* x, bool filled_by_driver);
 template <typename T>
-int pa_bc_pair_apply(pa_ctx* c, T* x, double* part2, int mode, bool guarded, int* nsh);
-template <typename T>
-void pa_shell_launch(pa_ctx* c, const T* x, T* shell, double* part2, int with_delta);
+int pa_bc_fill_step(pa_ctx* c, T* x, double* part2, int* nsh);
 
 #define PA_HIP(c, call)                                              \
   do {                                                               \

@@ -1,5 +1,5 @@
 // pa_resident.hip -- small meshes: the whole CG / Jacobi / BiCGSTAB solve in ONE cooperative launch, the fields
-// resident in LDS (linalg.py:74-279 and the Jacobi of SURVEY a15, same arithmetic as the kernels of pa_solver.hip).
+// resident in LDS (linalg.py:74-279 and the Jacobi of SURVEY a15, same arithmetic as the kernels of pa_cg.hip / pa_jacobi.hip / pa_bicgstab.hip).
 //
 // On the meshes the reference's tests and demos run (128^2, 33^3, 64^3 ...) an iteration of the launch-per-
 // phase loops costs ~10 us per dependent kernel whatever the kernel does (DESIGN "small meshes").  Here the

@@ -1,5 +1,5 @@
 // pa_scalar_steps.h -- the scalar steps of the solver loops on the device-resident state (shared by the
-// single-block / folded kernels of pa_solver.hip and the resident small-mesh solver of pa_resident.hip)
+// single-block / folded kernels of pa_cg.hip / pa_bicgstab.hip / pa_jacobi.hip and the resident small-mesh solver of pa_resident.hip)
 #pragma once
 #include "pa_host.h"
 

@@ -35,8 +35,8 @@ def slab_extent(n0: int, rank: int, world: int) -> tuple[int, int]:
 
 
 class _SlabDriver:
-    """What the slab solvers share: the neighbour relation, the packed exchange buffers and the plane exchange /
-    all-reduce primitives over ``torch.distributed``."""
+    """What the slab solvers share: the neighbour relation, the packed exchange buffers, the plane exchange /
+    all-reduce primitives over ``torch.distributed`` and the begin / solve / end skeleton of a solve."""
 
     uses_lib_comm = False     # (SlabCG: RCCL inside the library where the process group allows it)
 
@@ -222,6 +222,51 @@ class _SlabDriver:
     def _allreduce(self, lo: int, hi: int) -> None:
         self.dist.all_reduce(self.sums[lo:hi], op=self.dist.ReduceOp.SUM, group=self.group)
 
+    # -- solve (the methods' own parts: _slab_extra, _start, _limit, _end) -------------------------
+    def begin(self, tol: float, max_it: int, adjust_rhs: bool = True) -> None:
+        be = self.be
+        be.slab_set(self.bufs)
+        self._slab_extra()
+        be.bind_bcs(self.var(), self.var.bcs, 0)
+        be.set_terms(self.terms)
+        if adjust_rhs:
+            be.rhs_adjust(self.rhs)
+        self._exchange_bc_far()
+        be.apply_bc_bound(self.x)                      # linalg.py:97 / 181, before the ghosts of x move
+        self._exchange_planes(self.x[0], self.x[-1], self.bufs["x_ghost_lo"], self.bufs["x_ghost_hi"])
+        self._start(tol, max_it)
+
+    def _slab_extra(self) -> None:
+        pass
+
+    def solve(self, tol: float, max_it: int, poll: int = 8, adjust_rhs: bool = True) -> Any:
+        """Run to the method's stop rule (``_limit`` iterations at most); polls the device-side done flag every ``poll``
+        iterations -- iterations enqueued after it is set are no-ops.  On an error the live solve is dropped and the
+        context leaves slab mode before the error propagates, so the next solve on this mesh starts clean."""
+        try:
+            self.begin(tol, max_it, adjust_rhs=adjust_rhs)
+            done, limit = 0, self._limit(int(max_it))
+            while done < limit:
+                n = min(poll, limit - done)
+                self.iterate(n)
+                done += n
+                if self.be.report().itr < done:
+                    break
+            return self.end()
+        except BaseException:
+            for cleanup in (self.be.cg_abort, lambda: self.be.slab_set(None)):
+                try:
+                    cleanup()
+                except Exception:   # (the error that got us here is the one to report)
+                    pass
+            raise
+
+    def end(self) -> Any:
+        try:
+            return self._end()
+        finally:
+            self.be.slab_set(None)
+
 
 class SlabCG(_SlabDriver):
     """Stepwise CG over P slabs.  ``begin`` / ``iterate(n)`` / ``end`` mirror pa_cg_begin /
@@ -230,17 +275,8 @@ class SlabCG(_SlabDriver):
 
     uses_lib_comm = True
 
-    # -- solve ------------------------------------------------------------------------
-    def begin(self, tol: float, max_it: int, adjust_rhs: bool = True) -> None:
+    def _start(self, tol: float, max_it: int) -> None:
         be = self.be
-        be.slab_set(self.bufs)
-        be.bind_bcs(self.var(), self.var.bcs, 0)
-        be.set_terms(self.terms)
-        if adjust_rhs:
-            be.rhs_adjust(self.rhs)
-        self._exchange_bc_far()
-        be.apply_bc_bound(self.x)                      # linalg.py:97, before the ghosts of x move
-        self._exchange_planes(self.x[0], self.x[-1], self.bufs["x_ghost_lo"], self.bufs["x_ghost_hi"])
         be.cg_begin(self.x, self.rhs, tol, max_it)      # r, d = r, local sum r.r -> sums[1], r planes
         self._exchange_planes(self.bufs["r_send_lo"], self.bufs["r_send_hi"],
                               self.bufs["r_recv_lo"], self.bufs["r_recv_hi"])
@@ -276,18 +312,9 @@ class SlabCG(_SlabDriver):
             self._allreduce(1, 3)
             be.cg_finish_iter()                          # beta, stop test, itr (device side)
 
-    def solve(self, tol: float, max_it: int, poll: int = 8, adjust_rhs: bool = True) -> Any:
-        """Run to the reference's stop rule (tol / max_it + 1 iterations); polls the device-side
-        done flag every ``poll`` iterations -- iterations enqueued after it is set are no-ops."""
-        self.begin(tol, max_it, adjust_rhs=adjust_rhs)
-        done = 0
-        while done <= max_it:
-            n = min(poll, max_it + 1 - done)
-            self.iterate(n)
-            done += n
-            if self.be.report().itr < done:
-                break
-        return self.end()
+    @staticmethod
+    def _limit(max_it: int) -> int:
+        return max_it + 1                               # the reference's stop rule: tol, or max_it + 1 iterations
 
     def profile(self, n: int) -> dict[str, float]:
         self.be.profile(True)
@@ -296,10 +323,8 @@ class SlabCG(_SlabDriver):
         self.be.profile(False)
         return out
 
-    def end(self) -> Any:
-        rep = self.be.cg_end()
-        self.be.slab_set(None)
-        return rep
+    def _end(self) -> Any:
+        return self.be.cg_end()
 
 
 class SlabBiCGSTAB(_SlabDriver):
@@ -323,20 +348,14 @@ class SlabBiCGSTAB(_SlabDriver):
         self.v_send_lo, self.v_send_hi = buf(self.nb_lo is not None), buf(self.nb_hi is not None)
         self.v_recv_lo, self.v_recv_hi = buf(self.nb_lo is not None), buf(self.nb_hi is not None)
 
-    def begin(self, tol: float, max_it: int, adjust_rhs: bool = True) -> None:
-        be = self.be
-        be.slab_set(self.bufs)
-        be.slab_set_v(self.v_send_lo, self.v_send_hi, self.v_recv_lo, self.v_recv_hi)
-        be.bind_bcs(self.var(), self.var.bcs, 0)
-        be.set_terms(self.terms)
-        if adjust_rhs:
-            be.rhs_adjust(self.rhs)
+    def _slab_extra(self) -> None:
+        self.be.slab_set_v(self.v_send_lo, self.v_send_hi, self.v_recv_lo, self.v_recv_hi)
         for t in (self.v_recv_lo, self.v_recv_hi):      # v = 0 at the start (linalg.py:191), on the ghost planes too
             if t is not None:
                 t.zero_()
-        self._exchange_bc_far()
-        be.apply_bc_bound(self.x)                      # linalg.py:181, before the ghosts of x move
-        self._exchange_planes(self.x[0], self.x[-1], self.bufs["x_ghost_lo"], self.bufs["x_ghost_hi"])
+
+    def _start(self, tol: float, max_it: int) -> None:
+        be = self.be
         be.bicg_begin(self.x, self.rhs, tol, max_it)    # r0 = r, local r0.r0 -> sums[1], r planes
         self._exchange_planes(self.bufs["r_send_lo"], self.bufs["r_send_hi"],
                               self.bufs["r_recv_lo"], self.bufs["r_recv_hi"])
@@ -360,22 +379,12 @@ class SlabBiCGSTAB(_SlabDriver):
             self._allreduce(5, 6)
             be.bicg_finish()                             # stop test 2, beta, rho (device side)
 
-    def solve(self, tol: float, max_it: int, poll: int = 8, adjust_rhs: bool = True) -> Any:
-        """Run to the reference's stop rule (either stop test, or max_it iterations: linalg.py:262-271)."""
-        self.begin(tol, max_it, adjust_rhs=adjust_rhs)
-        done, limit = 0, max(int(max_it), 1)
-        while done < limit:
-            n = min(poll, limit - done)
-            self.iterate(n)
-            done += n
-            if self.be.report().itr < done:
-                break
-        return self.end()
+    @staticmethod
+    def _limit(max_it: int) -> int:
+        return max(max_it, 1)                           # either stop test, or max_it iterations: linalg.py:262-271
 
-    def end(self) -> Any:
-        rep = self.be.bicg_end()
-        self.be.slab_set(None)
-        return rep
+    def _end(self) -> Any:
+        return self.be.bicg_end()
 
 
 class SlabJacobi(_SlabDriver):
@@ -398,17 +407,8 @@ class SlabJacobi(_SlabDriver):
             return t[1:] if (t is not None and t.shape[0] > 1) else None
         return self._plane_ops(tail(self.send_lo), tail(self.send_hi), tail(self.recv_lo), tail(self.recv_hi))
 
-    def begin(self, tol: float, max_it: int, adjust_rhs: bool = True) -> None:
-        be = self.be
-        be.slab_set(self.bufs)
-        be.bind_bcs(self.var(), self.var.bcs, 0)
-        be.set_terms(self.terms)
-        if adjust_rhs:
-            be.rhs_adjust(self.rhs)
-        self._exchange_bc_far()
-        be.apply_bc_bound(self.x)
-        self._exchange_planes(self.x[0], self.x[-1], self.bufs["x_ghost_lo"], self.bufs["x_ghost_hi"])
-        be.jacobi_begin(self.x, self.rhs, tol, max_it, self.omega)
+    def _start(self, tol: float, max_it: int) -> None:
+        self.be.jacobi_begin(self.x, self.rhs, tol, max_it, self.omega)
 
     def iterate(self, n: int) -> None:
         be = self.be
@@ -425,22 +425,12 @@ class SlabJacobi(_SlabDriver):
                                   self.bufs["x_ghost_lo"], self.bufs["x_ghost_hi"])
             be.jacobi_finish()                           # stop test, sweep count (device side)
 
-    def solve(self, tol: float, max_it: int, poll: int = 8, adjust_rhs: bool = True) -> Any:
-        """Run to the reference's stop rule as the CG has it (tol / max_it + 1 sweeps)."""
-        self.begin(tol, max_it, adjust_rhs=adjust_rhs)
-        done = 0
-        while done <= max_it:
-            n = min(poll, max_it + 1 - done)
-            self.iterate(n)
-            done += n
-            if self.be.report().itr < done:
-                break
-        return self.end()
+    @staticmethod
+    def _limit(max_it: int) -> int:
+        return max_it + 1                               # the CG's stop rule: tol, or max_it + 1 sweeps
 
-    def end(self) -> Any:
-        rep = self.be.jacobi_end()
-        self.be.slab_set(None)
-        return rep
+    def _end(self) -> Any:
+        return self.be.jacobi_end()
 
 
 class SlabEuler(_SlabDriver):

@@ -234,6 +234,9 @@ class TorchSlabBackend:
     def cg_end(self):
         return self.report()
 
+    def cg_abort(self):   # pa_cg_abort: drop the live solve, whichever method, without reading it back
+        self.done = True
+
     # -- stepwise BiCGSTAB (linalg.py:162-279 split at its reductions and exchanges; include/pyapes_hip.h) -------
     def slab_set_v(self, v_send_lo, v_send_hi, v_recv_lo, v_recv_hi):
         self.vb = {"send_lo": v_send_lo, "send_hi": v_send_hi, "recv_lo": v_recv_lo, "recv_hi": v_recv_hi}

@@ -18,8 +18,10 @@ pytestmark = pytest.mark.gpu
 
 
 def _worker(rank, world, port, jobs, out):
-    """jobs: list of (key, BC mix, n, K, dtype, options): solved one after the other by the SAME rank processes (one
-    process group; a fresh mesh / context per job, created under that job's PYAPES_HIP_OPTIONS)."""
+    """jobs: list of (key, BC mix, n, K, dtype, options[, method, probe]): solved one after the other by the SAME rank
+    processes (one process group; a fresh mesh / context per job, created under that job's PYAPES_HIP_OPTIONS).
+    method: "cg" (default), "bicgstab" or "jacobi"; probe: after two iterations, call the CG step cg_finish_iter and
+    cg_end into the live solve and record the errors they raise, then finish the solve."""
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, here)
@@ -31,11 +33,12 @@ def _worker(rank, world, port, jobs, out):
     try:
         from pyapes_amd.geometry import Box
         from pyapes_amd.mesh import Mesh
-        from pyapes_amd.slab import SlabCG
+        from pyapes_amd.slab import SlabBiCGSTAB, SlabCG, SlabJacobi
         from pyapes_amd.variables import Field
         torch.cuda.set_device(0)
         res = {}
-        for key, name, n, K, dtype, opts in jobs:
+        for key, name, n, K, dtype, opts, *more in jobs:
+            method, probe = more or ("cg", False)
             if opts:
                 os.environ["PYAPES_HIP_OPTIONS"] = ",".join(f"{k}={int(v)}" for k, v in opts.items())
             else:
@@ -49,11 +52,28 @@ def _worker(rank, world, port, jobs, out):
             if name == "per":
                 rhs_g -= rhs_g.mean()
             rhs = rhs_g[:, mesh.i_off:mesh.i_off + mesh.nx[0]].contiguous().cuda()
-            drv = SlabCG(mesh, var, rhs, [{"kind": 0, "sign": -1.0, "coeff": 0.7}], dist)
-            rep = drv.solve(1e-30, K, poll=3)
+            cls = {"cg": SlabCG, "bicgstab": SlabBiCGSTAB, "jacobi": SlabJacobi}[method]
+            drv = cls(mesh, var, rhs, [{"kind": 0, "sign": -1.0, "coeff": 0.7}], dist)
+            errors = []
+            if probe:
+                drv.begin(1e-30, K)
+                drv.iterate(2)
+                for call in (drv.be.cg_finish_iter, drv.be.cg_end):
+                    try:
+                        call()
+                    except RuntimeError as e:
+                        errors.append(str(e))
+                done, limit = 2, drv._limit(K)
+                while done < limit and drv.be.report().itr >= done:
+                    n_it = min(3, limit - done)
+                    drv.iterate(n_it)
+                    done += n_it
+                rep = drv.end()
+            else:
+                rep = drv.solve(1e-30, K, poll=3)
             parts = [None] * world
             dist.all_gather_object(parts, var().cpu())
-            res[key] = {"x": torch.cat(parts, dim=1), "itr": int(rep.itr), "tol": float(rep.tol)}
+            res[key] = {"x": torch.cat(parts, dim=1), "itr": int(rep.itr), "tol": float(rep.tol), "errors": errors}
         if rank == 0:
             torch.save(res, out)
     finally:
@@ -119,6 +139,24 @@ def test_two_slabs_pair_bc_kernels(name, two_slabs):
     _check_against_oracle(plain, name, (24, 20, 132), "double")
     assert torch.equal(paired["x"], plain["x"])
     assert abs(paired["tol"] - plain["tol"]) <= 1e-12 * abs(plain["tol"])
+
+
+@pytest.mark.parametrize("method,kind", [("bicgstab", "BiCGSTAB"), ("jacobi", "Jacobi")])
+def test_cg_steps_refused_during_another_stepwise_solve(method, kind, tmp_path):
+    """A CG step call during a live stepwise BiCGSTAB / Jacobi solve is refused with an error that names the live kind,
+    and leaves that solve untouched: it ends bit-identical to an uninterrupted one (one rank, gloo: the Python-side
+    step sequence)."""
+    n = (24, 20, 132)
+    jobs = [("plain", "mix", n, K_IT, "double", {}, method, False), ("probed", "mix", n, K_IT, "double", {}, method, True)]
+    out = str(tmp_path / "res.pt")
+    spawn_ranks(_worker, lambda port: (1, port, jobs, out), 1)
+    res = torch.load(out)
+    plain, probed = res["plain"], res["probed"]
+    assert len(probed["errors"]) == 2, probed["errors"]
+    for what, msg in zip(("pa_cg_finish_iter", "pa_cg_end"), probed["errors"]):
+        assert what in msg and f"during a stepwise {kind} solve" in msg, msg
+    assert probed["itr"] == plain["itr"] and probed["tol"] == plain["tol"]
+    assert torch.equal(probed["x"], plain["x"])
 
 
 def _worker_rccl(rank, world, port, names, n, K, out, runs):

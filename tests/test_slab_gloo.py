@@ -61,7 +61,32 @@ def spawn_ranks(fn, args_of_port, nprocs):
             raise
 
 
-def _worker(rank, world, port, name, n, K, dtype, out):
+class _FailingOnce:
+    """The stand-in backend, raising once in the ``fail_at``-th phase B (the same step on every rank, so no rank is left
+    waiting in a collective) and recording the calls that clean up after it."""
+
+    def __init__(self, be, fail_at):
+        self.be, self.fail_at, self.n_b, self.calls = be, fail_at, 0, []
+
+    def __getattr__(self, name):
+        return getattr(self.be, name)
+
+    def cg_phase_b(self):
+        self.n_b += 1
+        if self.n_b == self.fail_at:
+            raise RuntimeError("injected failure in phase B")
+        return self.be.cg_phase_b()
+
+    def cg_abort(self):
+        self.calls.append("cg_abort")
+        return self.be.cg_abort()
+
+    def slab_set(self, bufs):
+        self.calls.append("slab_set" if bufs is not None else "slab_set(None)")
+        return self.be.slab_set(bufs)
+
+
+def _worker(rank, world, port, name, n, K, dtype, out, fail_at=0):
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, here)
@@ -85,7 +110,17 @@ def _worker(rank, world, port, name, n, K, dtype, out):
         if name == "per":
             rhs_g -= rhs_g.mean()
         rhs = rhs_g[:, mesh.i_off:mesh.i_off + mesh.nx[0]].clone()
-        drv = SlabCG(mesh, var, rhs, [{"kind": 0, "sign": -1.0, "coeff": 0.7}], dist, backend=TorchSlabBackend(mesh))
+        be = TorchSlabBackend(mesh)
+        drv = SlabCG(mesh, var, rhs, [{"kind": 0, "sign": -1.0, "coeff": 0.7}], dist, backend=be)
+        if fail_at:
+            be = _FailingOnce(be, fail_at)
+            drv.be = be
+            x0, rhs0 = var().clone(), rhs.clone()
+            with pytest.raises(RuntimeError, match="injected"):
+                drv.solve(1e-30, K, poll=3)
+            assert be.calls[-2:] == ["cg_abort", "slab_set(None)"], be.calls[-4:]
+            var()[:] = x0                   # the same start for the second solve on this driver and mesh
+            rhs[:] = rhs0
         rep = drv.solve(1e-30, K, poll=3)
         parts = [None] * world
         dist.all_gather_object(parts, var().clone())
@@ -95,11 +130,13 @@ def _worker(rank, world, port, name, n, K, dtype, out):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("name", list(CASES), ids=list(CASES))
-def test_slab_driver_two_ranks_matches_oracle(name, tmp_path):
+@pytest.mark.parametrize("name,fail_at", [(c, 0) for c in CASES] + [("mix", 4)], ids=list(CASES) + ["mix-after-error"])
+def test_slab_driver_two_ranks_matches_oracle(name, fail_at, tmp_path):
+    """(mix-after-error: a solve that raises inside ``iterate`` drops the live solve and leaves slab mode; the next
+    solve on the same driver and mesh runs as if it had not happened)"""
     n, K, dtype = (12, 9, 10), 7, "double"
     out = str(tmp_path / "x.pt")
-    spawn_ranks(_worker, lambda port: (2, port, name, n, K, dtype, out), 2)
+    spawn_ranks(_worker, lambda port: (2, port, name, n, K, dtype, out, fail_at), 2)
     res = torch.load(out)
     mesh = O.OMesh([0, 0, 0], [1, 1, 0.5], list(n), dtype)
     cfg = [{"bc_face": O.FACES[i], "bc_type": t, "bc_val": v} for i, (t, v) in enumerate(CASES[name])]
