@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench_ops.py -- secondary measurements for the other rows of SURVEY section 8 (not the driver's
 contract; bench.py is).  One JSON line per workload: explicit Laplacian apply, the explicit
-adv-diff Euler march (BASELINE config 4), Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+adv-diff Euler march (BASELINE config 4), the SSP Runge-Kutta march beside its unfused composition, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -48,8 +48,9 @@ def emit(name, cells, ms, passes, esize, extra=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--sections", default="ops,euler,small,big",
-                    help="comma-separated subset of: ops (explicit operators 512^3), euler (config 4 march), small (the reference's "
+    ap.add_argument("--sections", default="ops,euler,rk,small,big",
+                    help="comma-separated subset of: ops (explicit operators 512^3), euler (config 4 march), rk (SSP Runge-Kutta march, "
+                         "fused stages against the composition of public pieces), small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -93,6 +94,8 @@ def main():
     # --- config 4: explicit adv-diff march 256^3 fp32, upwind, Neumann / Symmetry ------------------
     if "euler" in sections:
         euler_rows(q, emit)
+    if "rk" in sections:
+        rk_rows(q, emit)
     solver_rows(q, emit, sections)
 
 
@@ -137,6 +140,53 @@ def euler_rows(q, emit):
         emit("euler_march (20 steps per call) 512^3 f32 upwind scalar u", 512 ** 3, ms, 2, 4)
         del phi, mesh
 
+def rk_rows(q, emit):
+    """rk_march (one C call per march: Euler kernel + one fused stage kernel per further stage) beside the same march made
+    of public pieces that need no stage kernel: euler_step, c0 * phi0 + c1 * E as torch ops, apply_bcs.  ms per STEP.
+    Algorithmic passes of a step: its Euler stage 2, every fused stage 3 (phi_s, phi0 in, one out), + 1 each with a
+    speed tensor -- order 3: 8 (11), order 2: 5 (7)."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.march import SSP_STAGES, euler_step, rk_march
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    bcs = mixed_bcs([0.0, 0.0, None, None, None, None],
+                    ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"])
+    cfg = {"div": {"limiter": "upwind"}}
+    nu, steps = 1e-3, 20
+
+    def unfused_march(phi, u, dt, order):
+        for _ in range(steps):
+            phi0 = phi()            # euler_step hands phi a new tensor: this one stays what it is
+            euler_step(phi, u, nu, dt, cfg)
+            for c0, c1 in SSP_STAGES[order]:
+                euler_step(phi, u, nu, dt, cfg)
+                phi.set_var_tensor(c0 * phi0 + c1 * phi())
+                phi.apply_bcs()
+
+    sizes = [(128, "single")] if q else [(256, "single"), (512, "single"), (256, "double")]
+    for n, dtype in sizes:
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", dtype)
+        es, f = (8, "f64") if dtype == "double" else (4, "f32")
+        start = torch.exp(-((mesh.X - 0.5) ** 2 + (mesh.Y - 0.5) ** 2 + (mesh.Z - 0.5) ** 2) / 0.02).unsqueeze(0).contiguous()
+        dx = mesh.dx_list[0]
+        dt = 0.2 * min(dx * dx / (6 * nu), dx / 1.0)
+        ut = torch.ones_like(start) * 0.7
+        for order in (3, 2):
+            for uname, u, extra in (("scalar u", 1.0, 0), ("speed tensor", ut, 1)):
+                phi = Field("phi", 1, mesh, {"domain": bcs, "obstacle": None})
+                phi.set_var_tensor(start.clone())
+                phi.apply_bcs()
+                passes = 2 + 3 * (order - 1) + extra * order
+                ms_f = timed(lambda: rk_march(phi, u, nu, dt, steps, cfg, order=order), 3, warm=1) / steps
+                emit(f"rk_march order {order} ({steps} steps per call) {n}^3 {f} upwind {uname} (config 4 BCs)", n ** 3, ms_f, passes, es)
+                ms_u = timed(lambda: unfused_march(phi, u, dt, order), 3, warm=1) / steps
+                emit(f"unfused order {order} (euler_step + torch combine + apply_bcs, {steps} steps) {n}^3 {f} upwind {uname}", n ** 3,
+                     ms_u, passes, es, {"fused_over_unfused": ms_f / ms_u})
+                assert bool(torch.isfinite(phi()).all())
+                del phi
+        del mesh, start, ut
+        torch.cuda.empty_cache()
 
 
 def solver_rows(q, emit, sections):

@@ -227,6 +227,22 @@ int pa_euler_step(pa_ctx* ctx, const void* phi_in, void* phi_out, int div_kind, 
 int pa_euler_march(pa_ctx* ctx, void* phi, void* tmp, int div_kind, double u, const void* u_field,
                    double nu, double dt, int64_t nsteps);
 
+/* Strong-stability-preserving Runge-Kutta steps (Shu-Osher form: every stage is the Euler step E followed by a convex
+ * combination with the field the step started from).  Single GPU: slab marching of the stages is not implemented
+ * (PA_E_STATE in slab mode).
+ *   pa_rk_stage   out = B( c0*phi0 + c1*E(phi) ) on the interior set, in ONE kernel: E as pa_euler_step forms it, then
+ *                 t0 = c0*phi0, t1 = c1*E, out = t0 + t1, each rounded in the grid dtype; the ordered BC fill follows.
+ *                 out != phi, out != phi0 (PA_E_ARG).
+ *   pa_rk_march   nsteps steps of order 1 | 2 | 3 enqueued back to back over three distinct buffers, no host
+ *                 synchronisation; *final = index (0, 1, 2 for phi, w1, w2) of the buffer that holds the result.
+ *                 order 1: pa_euler_march(phi, w1).  order 2: p1 = E(p0); p' = 1/2 p0 + 1/2 E(p1).
+ *                 order 3: p1 = E(p0); p2 = 3/4 p0 + 1/4 E(p1); p' = 1/3 p0 + 2/3 E(p2).
+ *                 PA_E_ARG: order not in {1, 2, 3}, aliased buffers, bad div_kind. */
+int pa_rk_stage(pa_ctx* ctx, const void* phi, const void* phi0, void* out, double c0, double c1, int div_kind,
+                double u, const void* u_field, double nu, double dt);
+int pa_rk_march(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double u, const void* u_field,
+                double nu, double dt, int64_t nsteps, int* final);
+
 /* ---- vector steps for a host-stepped solver loop (pyapes_amd/solver/host_stepped.py: BC callables that read the iterate
  * make the reference's loop come back to Python for every face of every fill, bcs.py:200-253; the loop's AXPYs and dot
  * products between those fills are these).  Fields of the grid's shape and dtype.

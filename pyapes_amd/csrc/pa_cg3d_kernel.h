@@ -92,6 +92,11 @@ struct Cg3dArgs {
   int pre_n, pre_nsh;
   SolverScalars* sc_w;
   double* pre_sums;
+  // Runge-Kutta stage (the STG instantiations of PHASE 3, k_cg3d and k_sf): out = stg_c0 * phi0 + stg_c1 * (Euler value),
+  // the two products and the sum rounded one by one.  phi0 (the field the step started from) is read at the cell only.
+  // (last in the struct: the offsets the other instantiations read their arguments at stay what they were)
+  const T* stg_phi0;
+  T stg_c0, stg_c1;
 };
 
 __device__ __forceinline__ int pa_xcd_remap(int b, int nb) {
@@ -118,8 +123,11 @@ __device__ __forceinline__ int64_t pa_wrapmod(int64_t v, int64_t n) {
 // three of its five streams.  A pad cell is never a neighbour anybody uses: the last real cell of a row is a
 // boundary node of a non-periodic axis, outside the interior set.  BiCGSTAB (phases 5, 6, 8): EVERY array of these
 // phases is the ctx's (r, p, v, r0, s, t) and pitched; only the x / r update (k_bicg_x, pa_bicgstab.hip) touches x.
-template <typename T, int RJ, int PHASE, bool CF = false, int KIND = 0, int LAY = 0>
+// STG (PHASE 3): the stage of an SSP Runge-Kutta step -- what the Euler step would store, e, leaves as
+// c0 * phi0 + c1 * e (Cg3dArgs::stg_*), one more read stream and three operations per cell.
+template <typename T, int RJ, int PHASE, bool CF = false, int KIND = 0, int LAY = 0, bool STG = false>
 __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
+  static_assert(!STG || PHASE == 3, "STG: the explicit Euler step");
   // PHASE 9 = the Jacobi sweep (phase 4) marching its chunks BACKWARDS: consecutive sweeps alternate, so the planes a sweep
   // wrote last -- still in the 256 MiB Infinity Cache -- are the ones the next sweep reads first (what phase B does for
   // phase A).  Everything below tests PH.
@@ -609,6 +617,12 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
                        : *reinterpret_cast<const V*>(A.aux + ii * G.s0 + jrow[jj] * G.s1 + kc);
       }
     }
+    if constexpr (STG) {   // phi0 of this plane, at the cell, into the rows phase B keeps its residual in (free here; a
+      // variable of its own, though dead in the other instantiations, moved the registers of the phase-2 Div kernels)
+#pragma unroll
+      for (int jj = 0; jj < RJ; ++jj)
+        rv[jj] = *reinterpret_cast<const V*>(A.stg_phi0 + ii * G.s0 + jrow[jj] * G.s1 + kc);
+    }
     // loads of plane m+2 (own cells + halo): in flight during the stencil below
     d_run += pstep;
     if (HAS_R) r_run += pstep;
@@ -907,6 +921,11 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
           outd[v] = (inS || !A.interior_only) ? res[jj][v] : (T)0;
         } else if (PH == 3) {
           outd[v] = inS ? res[jj][v] : xc;
+          if constexpr (STG) {
+            T t0 = A.stg_c0 * rv[jj][v];
+            T t1 = A.stg_c1 * outd[v];
+            outd[v] = t0 + t1;
+          }
         } else if (PH == 4) {
           const T xn = inS ? res[jj][v] : xc;
           const bool offshell = inS && !(iShell || (rowShell >> jj & 1) || (colShell >> v & 1));
@@ -1063,18 +1082,18 @@ static int cus_of(pa_ctx* c) {
   return cus;
 }
 
-template <typename T, int RJ, int PHASE, bool CF, int KIND = 0, int LAY = 0>
+template <typename T, int RJ, int PHASE, bool CF, int KIND = 0, int LAY = 0, bool STG = false>
 static int blocks_per_cu() {
   static int cached = 0;
   if (!cached) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_cg3d<T, RJ, PHASE, CF, KIND, LAY>, 256, 0) != hipSuccess || n <= 0) n = 2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_cg3d<T, RJ, PHASE, CF, KIND, LAY, STG>, 256, 0) != hipSuccess || n <= 0) n = 2;
     cached = n;
   }
   return cached;
 }
 
-template <typename T, int RJ, int PHASE, bool CF = false, int KIND = 0, int LAY = 0>
+template <typename T, int RJ, int PHASE, bool CF = false, int KIND = 0, int LAY = 0, bool STG = false>
 static int launch_cg3d(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr bool NARROW = LAY == 1;
   constexpr int VEC = NARROW ? 1 : VecOf<T>::N;
@@ -1094,7 +1113,7 @@ static int launch_cg3d(pa_ctx* c, Cg3dArgs<T>& A) {
   A.tiles_j = (int)((n1e + TJ - 1) / TJ);
   A.tiles_k = (int)((n2e + TK - 1) / TK);
   const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * blocks_per_cu<T, RJ, PHASE, CF, KIND, LAY>();
+  const int capacity = cus_of(c) * blocks_per_cu<T, RJ, PHASE, CF, KIND, LAY, STG>();
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
@@ -1105,12 +1124,12 @@ static int launch_cg3d(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
   if (dbg > 0) {
     --dbg;
-    fprintf(stderr, "[pyapes_hip] k_cg3d phase %c%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU x %d CUs\n",
-            (char)('A' + PHASE), LAY == 1 ? " (narrow)" : (LAY == 2 ? " (pitched)" : ""), A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
-            blocks_per_cu<T, RJ, PHASE, CF, KIND, LAY>(), cus_of(c));
+    fprintf(stderr, "[pyapes_hip] k_cg3d phase %c%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU x %d CUs\n",
+            (char)('A' + PHASE), LAY == 1 ? " (narrow)" : (LAY == 2 ? " (pitched)" : ""), STG ? " (RK stage)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
+            blocks_per_cu<T, RJ, PHASE, CF, KIND, LAY, STG>(), cus_of(c));
   }
   if (c->plan_only) return nblk;   // pa_cg_fold_plan: the grid this launch would use
-  hipLaunchKernelGGL((k_cg3d<T, RJ, PHASE, CF, KIND, LAY>), dim3(nblk), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL((k_cg3d<T, RJ, PHASE, CF, KIND, LAY, STG>), dim3(nblk), dim3(256), 0, c->stream, A);
   return nblk;
 }
 
@@ -1146,7 +1165,7 @@ static int pick_rj(pa_ctx* c, bool narrow = false, bool cg_phase = false) {
   return (chunk_len(4) < 24 && chunk_len(2) >= 24) ? 2 : 4;
 }
 
-template <typename T, int PHASE, int NARROW>   // NARROW = LAY of k_cg3d: 0 vector, 1 one cell per lane, 2 pitched
+template <typename T, int PHASE, int NARROW, bool STG = false>   // NARROW = LAY of k_cg3d: 0 vector, 1 one cell per lane, 2 pitched
 static int launch_any_w(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr bool CF_OK = (PHASE == 0 || PHASE == 1 || PHASE == 2 || PHASE == 4 || PHASE == 9);
   if (A.coeff_f) {  // tensor coefficient: separate instantiation, so the scalar-coefficient kernels stay lean
@@ -1164,9 +1183,9 @@ static int launch_any_w(pa_ctx* c, Cg3dArgs<T>& A) {
 #define PA_EULER_CASE(K)                                                   \
     case K:                                                                \
       switch (rj) {                                                        \
-        case 1: return launch_cg3d<T, 1, 3, false, K, NARROW>(c, A);       \
-        case 2: return launch_cg3d<T, 2, 3, false, K, NARROW>(c, A);       \
-        default: return launch_cg3d<T, 4, 3, false, K, NARROW>(c, A);      \
+        case 1: return launch_cg3d<T, 1, 3, false, K, NARROW, STG>(c, A);  \
+        case 2: return launch_cg3d<T, 2, 3, false, K, NARROW, STG>(c, A);  \
+        default: return launch_cg3d<T, 4, 3, false, K, NARROW, STG>(c, A); \
       }
     switch (A.kind) {
       PA_EULER_CASE(PA_OP_DIV_CENTRAL)
@@ -1215,12 +1234,12 @@ static int launch_pitched(pa_ctx* c, Cg3dArgs<T>& A) {
   }
 }
 
-template <typename T, int PHASE>
+template <typename T, int PHASE, bool STG = false>
 static int launch_any(pa_ctx* c, Cg3dArgs<T>& A, int mode) {
   if constexpr (PHASE == 0 || PHASE == 1 || PHASE == 5 || PHASE == 6 || PHASE == 8) {
     if (mode == 3) return launch_pitched<T, PHASE>(c, A);
   }
-  return mode == 2 ? launch_any_w<T, PHASE, 1>(c, A) : launch_any_w<T, PHASE, 0>(c, A);
+  return mode == 2 ? launch_any_w<T, PHASE, 1, STG>(c, A) : launch_any_w<T, PHASE, 0, STG>(c, A);
 }
 
 template <typename T>

@@ -299,7 +299,8 @@ template <typename T>
 int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd);
 template <typename T>
 int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt,
-                    int bcl = 0);   // bcl: "BC on load" (pa_sf_kernel.h); 0 is returned when that form does not apply
+                    int bcl = 0,    // bcl: "BC on load" (pa_sf_kernel.h); 0 is returned when that form does not apply
+                    const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0);   // phi0: the stage c0 phi0 + c1 E(phi) of pa_rk_stage
 template <typename T>
 int pa_tile3d_jacobi(pa_ctx* c, const DevEq<T>& E, Vec<T> x, const T* rhs, T* xnew, double omega, double* partials);
 template <typename T>

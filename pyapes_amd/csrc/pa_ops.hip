@@ -235,9 +235,13 @@ __global__ void __launch_bounds__(PA_BLOCK) k_rhs_adjust(DevGeom G, DevEq<T> E, 
 
 
 // ---- explicit Euler step [new, SURVEY a15] ----------------------------------------------
-template <typename T>
+// STG: the stage of an SSP Runge-Kutta step (pa_rk_stage) -- the value the Euler step stores, v, leaves as
+// c0 * phi0 + c1 * v, the two products and the sum rounded one by one; phi0 is read at the cell.
+template <typename T, bool STG> struct EulerStage {};
+template <typename T> struct EulerStage<T, true> { const T* phi0; T c0, c1; };
+template <typename T, bool STG = false>
 __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, DevEq<T> Eadv, Vec<T> pv,
-                                                     T* __restrict__ out, T nu, T dt) {
+                                                     T* __restrict__ out, T nu, T dt, EulerStage<T, STG> S = {}) {
   FieldAcc<T> acc{pv};
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < G.ncell;
        idx += (int64_t)gridDim.x * blockDim.x) {
@@ -253,7 +257,22 @@ __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, De
       a = dt * a;
       v = pc + a;
     }
+    if constexpr (STG) {
+      T t0 = S.c0 * S.phi0[idx];
+      T t1 = S.c1 * v;
+      v = t0 + t1;
+    }
     out[idx] = v;
+  }
+}
+
+// the stage where it cannot be fused (a periodic face, euler_t): x <- c0 * phi0 + c1 * x, x the finished Euler step
+template <typename T>
+__global__ void __launch_bounds__(PA_BLOCK) k_rk_combine(T* __restrict__ x, const T* __restrict__ phi0, T c0, T c1, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    T t0 = c0 * phi0[i];
+    T t1 = c1 * x[i];
+    x[i] = t0 + t1;
   }
 }
 
@@ -397,8 +416,32 @@ static int check_div_kind(pa_ctx* c, int kind) {
   return PA_OK;
 }
 
+// phi0 != null: the Runge-Kutta stage out = B( c0 phi0 + c1 E(in) ) (pa_rk_stage), on the path the Euler step takes
 template <typename T>
-static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const void* u_field, double nu, double dt) {
+static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const void* u_field, double nu, double dt,
+                   const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0) {
+  if (phi0) {
+    // A stage combines the Euler STEP, BC fill included.  For dirichlet / neumann / symmetry faces the fill rewrites its
+    // nodes from interior-set values alone, so filling once, after the combination, gives the same bits and the stage is
+    // one kernel.  The periodic fill is not of that kind: its lower face reads the upper face's value BEFORE the fill
+    // rewrites it (bcs.py:253-262: x[0] = x[1] - x[n-1] + x[n-2]), and those nodes belong to the interior set -- B(c0 phi0 +
+    // c1 e) would see the raw stencil value there where the Euler step hands on its filled one.  With a periodic face the
+    // stage is therefore the step itself, then the combination in place, then the fill.
+    bool periodic = false;
+    for (int f = 0; f < 6; ++f) periodic = periodic || (c->G.act[f >> 1] && c->bc[f].type == PA_BC_PERIODIC);
+    if (periodic) {
+      if (int rc = euler_t<T>(c, in, out, kind, u, u_field, nu, dt)) return rc;
+      static int dbg = -1;
+      if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
+      if (dbg > 0) { --dbg; fprintf(stderr, "[pyapes_hip] k_rk_combine (RK stage, periodic face): Euler step, then %lld cells in place\n", (long long)c->G.ncell); }
+      if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
+      hipLaunchKernelGGL(k_rk_combine<T>, dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, out, phi0, (T)c0,
+                         (T)c1, c->G.ncell);
+      if (c->profile) pa_profile_stop(c, 0);
+      PA_HIP(c, hipGetLastError());
+      return pa_bc_apply_auto<T>(c, out, false);
+    }
+  }
   pa_term tl, ta;
   memset(&tl, 0, sizeof(tl));
   memset(&ta, 0, sizeof(ta));
@@ -416,9 +459,15 @@ static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const voi
     pv.ghi = c->x_ghi ? (const T*)c->x_ghi : in + (c->G.n0 - 1) * c->G.s0;
   }
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);   // slot 0: the step kernel (without its BC fill)
-  int fr = pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt);
+  int fr = pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 0, phi0, c0, c1);
   if (fr < 0) return fr;
-  if (fr == 0)
+  if (fr == 0 && phi0) {
+    static int dbg = -1;
+    if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
+    if (dbg > 0) { --dbg; fprintf(stderr, "[pyapes_hip] k_euler (RK stage): generic kernel, %lld cells\n", (long long)c->G.ncell); }
+    hipLaunchKernelGGL((k_euler<T, true>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G, El, Ea, pv,
+                       out, (T)nu, (T)dt, EulerStage<T, true>{phi0, (T)c0, (T)c1});
+  } else if (fr == 0)
     hipLaunchKernelGGL(k_euler<T>, dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G, El, Ea, pv,
                        out, (T)nu, (T)dt);
   if (c->profile) pa_profile_stop(c, 0);
@@ -432,10 +481,11 @@ static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const voi
 // One step of the march in the "BC on load" form (pa_sf_kernel.h): the step kernel alone, no fill behind it -- the
 // boundary nodes of `out` stay whatever they were.  1: launched; 0: the form does not apply here; < 0: error.
 template <typename T>
-static int euler_bcl_t(pa_ctx* c, const T* in, T* out, int kind, double u, const void* u_field, double nu, double dt) {
+static int euler_bcl_t(pa_ctx* c, const T* in, T* out, int kind, double u, const void* u_field, double nu, double dt,
+                       const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0) {
   Vec<T> pv = pa_vec_self<T>(c, in);
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
-  const int fr = pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 1);
+  const int fr = pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 1, phi0, c0, c1);
   if (fr <= 0) return fr;
   if (c->profile) pa_profile_stop(c, 0);
   return 1;
@@ -488,6 +538,67 @@ __global__ void __launch_bounds__(PA_BLOCK) k_vec_dot_final(const double* __rest
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) t += sm[w];
     out[0] = t;
   }
+}
+
+// "BC on load" (pa_sf_kernel.h): when every face has a scalar dirichlet / neumann / symmetry BC the steps of a
+// march need no fill between them -- each forms the face values it reads from its own operands, bit for bit what
+// the fill would have stored -- and ONE ordered fill after the last step completes the result.
+static bool march_bcl_wanted(const pa_ctx* c, int kind, int64_t nsteps) {
+  bool bcl = c->bcl && c->sf && !c->slab && c->ndim == 3 && kind == PA_OP_DIV_UPWIND && nsteps >= 2 &&
+             c->G.n0 >= 5 && c->G.n1 >= 5 && c->G.n2 >= 5;
+  for (int f = 0; f < 6 && bcl; ++f)
+    bcl = c->bc[f].type >= PA_BC_DIRICHLET && c->bc[f].type <= PA_BC_SYMMETRY && !c->bc[f].vals;
+  return bcl;
+}
+
+// One launch of pa_rk_march: the Euler step (phi0 null) or a fused stage, in -> out.  *bcl: the march is in the "BC on
+// load" form.  The form is decided by the first launch (nlaunch 0); should a later one decline it (an operand the
+// vector kernel does not take), `in` gets the fill it was left without and the march goes on in the classic sequence --
+// the same bits, since the face values a BC-on-load launch forms are the ones the fill stores.
+template <typename T>
+static int rk_launch_t(pa_ctx* c, bool* bcl, int64_t nlaunch, T* in, T* out, const T* phi0, double c0, double c1, int kind,
+                       double u, const void* u_field, double nu, double dt) {
+  if (*bcl) {
+    const int fr = euler_bcl_t<T>(c, in, out, kind, u, u_field, nu, dt, phi0, c0, c1);
+    if (fr != 0) return fr < 0 ? fr : PA_OK;
+    *bcl = false;
+    if (nlaunch > 0) {
+      if (int rc = pa_bc_apply_auto<T>(c, in, false)) return rc;
+    }
+  }
+  return euler_t<T>(c, in, out, kind, u, u_field, nu, dt, phi0, c0, c1);
+}
+
+template <typename T>
+static int rk_march_t(pa_ctx* c, T* b0, T* b1, T* b2, int order, int kind, double u, const void* u_field, double nu,
+                      double dt, int64_t nsteps, int* final) {
+  // the fused stages of a step in Shu-Osher form, after its plain Euler stage: (c0, c1) of c0 phi0 + c1 E(phi_s)
+  const double st2[1][2] = {{0.5, 0.5}};
+  const double st3[2][2] = {{3.0 / 4.0, 1.0 / 4.0}, {1.0 / 3.0, 2.0 / 3.0}};
+  const double (*st)[2] = order == 2 ? st2 : st3;
+  T* buf[3] = {b0, b1, b2};
+  int base = 0, wa = 1, wb = 2;   // buffer of the step's phi0 and the two free ones
+  bool bcl = march_bcl_wanted(c, kind, nsteps);
+  int64_t nl = 0;
+  for (int64_t s = 0; s < nsteps; ++s) {
+    int rc = rk_launch_t<T>(c, &bcl, nl++, buf[base], buf[wa], nullptr, 0.0, 0.0, kind, u, u_field, nu, dt);
+    if (rc) return rc;
+    int cur = wa, free_ = wb;
+    for (int q = 0; q < order - 1; ++q) {
+      rc = rk_launch_t<T>(c, &bcl, nl++, buf[cur], buf[free_], buf[base], st[q][0], st[q][1], kind, u, u_field, nu, dt);
+      if (rc) return rc;
+      std::swap(cur, free_);
+    }
+    // cur holds the new state; the old base and the other work buffer are free
+    const int old = base;
+    base = cur; wa = old; wb = free_;
+  }
+  *final = base;
+  if (bcl && nsteps > 0) {
+    PA_HIP(c, hipGetLastError());
+    return pa_bc_apply_auto<T>(c, buf[base], false);
+  }
+  return PA_OK;
 }
 
 extern "C" {
@@ -622,13 +733,7 @@ int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const vo
   PaRange range_("pyapes explicit Euler march");
   PA_HIP(c, hipSetDevice(c->device));
   void* buf[2] = {phi, tmp};
-  // "BC on load" (pa_sf_kernel.h): when every face has a scalar dirichlet / neumann / symmetry BC the steps of a
-  // march need no fill between them -- each forms the face values it reads from its own operands, bit for bit what
-  // the fill would have stored -- and ONE ordered fill after the last step completes the result.
-  bool bcl = c->bcl && c->sf && !c->slab && c->ndim == 3 && kind == PA_OP_DIV_UPWIND && nsteps >= 2 &&
-             c->G.n0 >= 5 && c->G.n1 >= 5 && c->G.n2 >= 5;
-  for (int f = 0; f < 6 && bcl; ++f)
-    bcl = c->bc[f].type >= PA_BC_DIRICHLET && c->bc[f].type <= PA_BC_SYMMETRY && !c->bc[f].vals;
+  bool bcl = march_bcl_wanted(c, kind, nsteps);
   for (int64_t s = 0; s < nsteps; ++s) {
     if (bcl) {
       const int fr = c->dtype == PA_F64
@@ -650,6 +755,45 @@ int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const vo
                               : pa_bc_apply_auto<float>(c, (float*)buf[nsteps & 1], false);
   }
   return PA_OK;
+}
+
+int pa_rk_stage(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind, double u,
+                const void* u_field, double nu, double dt) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  int rc = check_div_kind(c, kind);
+  if (rc) return rc;
+  if (!phi || !phi0 || !out || out == phi || out == phi0) {
+    pa_set_err(c, "pa_rk_stage: out must be a buffer of its own (not phi, not phi0)");
+    return PA_E_ARG;
+  }
+  if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "pa_rk_stage: single GPU only (no slab stages)"); return PA_E_STATE; }
+  PA_HIP(c, hipSetDevice(c->device));
+  return c->dtype == PA_F64
+             ? euler_t<double>(c, (const double*)phi, (double*)out, kind, u, u_field, nu, dt, (const double*)phi0, c0, c1)
+             : euler_t<float>(c, (const float*)phi, (float*)out, kind, u, u_field, nu, dt, (const float*)phi0, c0, c1);
+}
+
+int pa_rk_march(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double u, const void* u_field, double nu,
+                double dt, int64_t nsteps, int* final) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  if (order < 1 || order > 3) { pa_set_err(c, "pa_rk_march: order %d (1, 2 or 3)", order); return PA_E_ARG; }
+  int rc = check_div_kind(c, kind);
+  if (rc) return rc;
+  if (!phi || !w1 || !w2 || !final || phi == w1 || phi == w2 || w1 == w2 || nsteps < 0) {
+    pa_set_err(c, "pa_rk_march: three distinct buffers, a place for the result index and nsteps >= 0 are needed");
+    return PA_E_ARG;
+  }
+  if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "pa_rk_march: single GPU only (no slab stages)"); return PA_E_STATE; }
+  if (order == 1) {   // plain Euler: the march as it is
+    rc = pa_euler_march(c, phi, w1, kind, u, u_field, nu, dt, nsteps);
+    if (!rc) *final = (int)(nsteps & 1);
+    return rc;
+  }
+  PaRange range_("pyapes SSP Runge-Kutta march");
+  PA_HIP(c, hipSetDevice(c->device));
+  return c->dtype == PA_F64
+             ? rk_march_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, u, u_field, nu, dt, nsteps, final)
+             : rk_march_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, u, u_field, nu, dt, nsteps, final);
 }
 
 }  // extern "C"

@@ -7,13 +7,14 @@
 #include "pa_sf_kernel.h"
 
 template <typename T>
-int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt, int bcl) {
+int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt, int bcl,
+                    const T* phi0, double c0, double c1) {
   DevEq<T> E;
   pa_term t;
   memset(&t, 0, sizeof(t));
   t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
   pa_build_eq<T>(c, 1, &t, E);
-  const int mode = cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi});
+  const int mode = cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0});   // (a stage's phi0 counts for the alignment)
   if (!mode) return 0;
   if (kind == PA_OP_DIV_CENTRAL && u_field) return 0;  // needs u at the neighbours: generic kernel
   Cg3dArgs<T> A;
@@ -21,6 +22,7 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
   fill_common<T>(c, E, A);
   fill_h<T>(c, A);
   A.d = phi; A.out = out; A.aux = (const T*)u_field; A.u = (T)u; A.p0 = (T)nu; A.p1 = (T)dt; A.kind = kind;
+  A.stg_phi0 = phi0; A.stg_c0 = (T)c0; A.stg_c1 = (T)c1;   // phi0 != null: the Runge-Kutta stage (STG instantiations)
   {  // the BC fill that follows the step kernel (euler_t) rewrites every face plane that has a BC
     int faces = 0;
     for (int f = 0; f < 6; ++f) faces += (c->G.act[f >> 1] && c->bc[f].type != PA_BC_NONE) ? 1 : 0;
@@ -43,17 +45,17 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
       }
     }
   }
-  int n = 0;
-  if (sf_applies<T, 3>(c, A, mode)) {
+  auto launch = [&](auto STGC) -> int {
+    constexpr bool STG = decltype(STGC)::value;
+    if (!sf_applies<T, 3>(c, A, mode)) return launch_any<T, 3, STG>(c, A, mode);
     switch (kind) {
-      case PA_OP_DIV_CENTRAL: n = launch_sf_any<T, 3, PA_OP_DIV_CENTRAL>(c, A); break;
-      case PA_OP_DIV_UPWIND_COMPAT: n = launch_sf_any<T, 3, PA_OP_DIV_UPWIND_COMPAT>(c, A); break;
-      case PA_OP_DIV_UPWIND: n = launch_sf_any<T, 3, PA_OP_DIV_UPWIND>(c, A); break;
+      case PA_OP_DIV_CENTRAL: return launch_sf_any<T, 3, PA_OP_DIV_CENTRAL, STG>(c, A);
+      case PA_OP_DIV_UPWIND_COMPAT: return launch_sf_any<T, 3, PA_OP_DIV_UPWIND_COMPAT, STG>(c, A);
+      case PA_OP_DIV_UPWIND: return launch_sf_any<T, 3, PA_OP_DIV_UPWIND, STG>(c, A);
       default: return 0;
     }
-  } else {
-    n = launch_any<T, 3>(c, A, mode);
-  }
+  };
+  const int n = phi0 ? launch(std::true_type{}) : launch(std::false_type{});
   if (n > 0 && hipGetLastError() != hipSuccess) { pa_set_err(c, "k_cg3d Euler launch failed"); return PA_E_HIP; }
   return n;
 }
@@ -105,8 +107,8 @@ int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd) {
   return n;
 }
 
-template int pa_tile3d_euler<float>(pa_ctx*, Vec<float>, float*, int, double, const void*, double, double, int);
-template int pa_tile3d_euler<double>(pa_ctx*, Vec<double>, double*, int, double, const void*, double, double, int);
+template int pa_tile3d_euler<float>(pa_ctx*, Vec<float>, float*, int, double, const void*, double, double, int, const float*, double, double);
+template int pa_tile3d_euler<double>(pa_ctx*, Vec<double>, double*, int, double, const void*, double, double, int, const double*, double, double);
 template int pa_tile3d_grad<float>(pa_ctx*, Vec<float>, float*, int);
 template int pa_tile3d_grad<double>(pa_ctx*, Vec<double>, double*, int);
 template int pa_tile3d_aop<float>(pa_ctx*, const DevEq<float>&, Vec<float>, float*, int);

@@ -94,12 +94,17 @@ template <> struct SfBits<double> {
 // operations of an Euler step -- is not computed, and every FINITE field gives the same bits (tests/test_gpu_tiled_ops.py
 // against the generic kernels, which form both halves).  Only a non-finite neighbour on the dead side differs: 0 x inf is
 // NaN in the literal form, nothing here.
+// STG: the stage of an SSP Runge-Kutta step (pa_rk_stage).  The row's Euler value e is in registers when it is stored; the
+// stage stores c0 * phi0 + c1 * e instead (two products, one sum, each rounded).  phi0 is read at the cell only, one
+// 16-byte lane access per row like the field's own rows, issued at the top of the plane IN FRONT of the loads of plane
+// q + 2 -- the wait for it at the end of the first row then leaves those in flight.  RJ * VEC more live registers.
 #ifndef PA_SF_USIGN
 #define PA_SF_USIGN 1
 #endif
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false>
 __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
   static_assert(!BCL || PHASE == 3, "BC on load: the Euler step");
+  static_assert(!STG || PHASE == 3, "STG: the Euler step");
   static_assert(US == 0 || (KIND == 4 && !HASU), "US: scalar speed of the upwind scheme");
   constexpr int VEC = VecOf<T>::N;
   typedef T V __attribute__((ext_vector_type(VEC)));
@@ -287,6 +292,12 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
     constexpr int C = decltype(CC)::value;
     constexpr int SB = C & 3, SC = (C + 1) & 3, SA = (C + 2) & 3, SL = (C + 3) & 3, HC = C & 3, HN = (C + 2) & 3;
     const int ii = i0 + q;
+    V Z[STG ? RJ : 1];   // STG: phi0 of THIS plane
+    if constexpr (STG) {
+      gcptr pz = (gcptr)((uintptr_t)A.stg_phi0 + (size_t)(unsigned)ii * pstride);
+#pragma unroll
+      for (int jj = 0; jj < RJ; ++jj) Z[jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(pz + off[jj]);
+    }
     // loads for later planes first: they fly during this plane's arithmetic
     load_own(std::integral_constant<int, SL>{}, ii + 2 <= i1 ? ii + 2 : i1);          // plane q + 2 (<= the one behind the chunk)
     load_halo(std::integral_constant<int, HN>{}, ii + 2 < i1 ? ii + 2 : i1 - 1);
@@ -525,6 +536,11 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
           qv = qv - adv;
           qv = A.p1 * qv;
           res = xc + qv;
+          if constexpr (STG) {
+            V t0 = A.stg_c0 * Z[jj];
+            V t1 = A.stg_c1 * res;
+            res = t0 + t1;
+          }
         } else if constexpr (KIND != 0) {
           // sum_k sign_k Aop_k (ops.py:122-154) of {Laplacian, Div}: p0 = sign of the Div term, p1 != 0: Div first
           V dv = adv * A.p0;
@@ -549,18 +565,18 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false>
 static int sf_blocks_per_cu() {
   static int cached = 0;
   if (!cached) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US>, 256, 0) != hipSuccess || n <= 0) n = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG>, 256, 0) != hipSuccess || n <= 0) n = 4;
     cached = n;
   }
   return cached;
 }
 
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false>
 static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr int VEC = VecOf<T>::N;
   constexpr int TJ = 4 * RJ, TK = 64 * VEC;
@@ -568,7 +584,7 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
   A.tiles_k = (int)((G.n2 + TK - 1) / TK);
   const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US>();
+  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG>();
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
@@ -579,11 +595,11 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
   if (dbg > 0) {
     --dbg;
-    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
-            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US>());
+    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
+            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
+            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG>());
   }
-  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US>), dim3(nblk), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG>), dim3(nblk), dim3(256), 0, c->stream, A);
   return nblk;
 }
 
@@ -592,7 +608,7 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
 //   fp64 512^3: 493 / 442 / 447 (553)   256^3: 45.3 / 45.2 / 45.5 (65.3)   128^3: 14.0 / 11.4 / 12.9 (15.1)
 // Four rows (least re-read of the rows above / below, ~230 VGPRs, two waves per SIMD) where a workgroup still
 // marches >= 32 planes, else two (the three planes of prologue weigh less on short chunks).
-template <typename T, int PHASE, int KIND>
+template <typename T, int PHASE, int KIND, bool STG = false>
 static int launch_sf_any(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr int VEC = VecOf<T>::N;
   const DevGeom& G = c->G;
@@ -609,27 +625,27 @@ static int launch_sf_any(pa_ctx* c, Cg3dArgs<T>& A) {
   if constexpr (PHASE == 3 && KIND == PA_OP_DIV_UPWIND) {   // BC on load: the upwind march (BASELINE config 4)
     if (A.bcl_type[0] | A.bcl_type[1] | A.bcl_type[2] | A.bcl_type[3] | A.bcl_type[4] | A.bcl_type[5]) {
       if (rj < 2 || (c->G.n1 - 1) % rj == 0) return 0;   // PATCH: rows n1 - 2, n1 - 1 in one wave's block
-      if (A.aux) return rj == 2 ? launch_sf<T, 2, 3, KIND, true, true>(c, A) : launch_sf<T, 4, 3, KIND, true, true>(c, A);
+      if (A.aux) return rj == 2 ? launch_sf<T, 2, 3, KIND, true, true, 0, STG>(c, A) : launch_sf<T, 4, 3, KIND, true, true, 0, STG>(c, A);
       if (PA_SF_USIGN) {   // scalar speed: its sign is a launch-time fact (US, above)
-        if (A.u < (T)0) return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 2>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 2>(c, A);
-        return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 1>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 1>(c, A);
+        if (A.u < (T)0) return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 2, STG>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 2, STG>(c, A);
+        return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 1, STG>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 1, STG>(c, A);
       }
-      return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true>(c, A) : launch_sf<T, 4, 3, KIND, false, true>(c, A);
+      return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 0, STG>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 0, STG>(c, A);
     }
   }
   if constexpr (KIND == PA_OP_DIV_UPWIND) {
     if (PA_SF_USIGN && !A.aux) {
       if (A.u < (T)0) {
         switch (rj) {
-          case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 2>(c, A);
-          case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 2>(c, A);
-          default: return launch_sf<T, 4, PHASE, KIND, false, false, 2>(c, A);
+          case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 2, STG>(c, A);
+          case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 2, STG>(c, A);
+          default: return launch_sf<T, 4, PHASE, KIND, false, false, 2, STG>(c, A);
         }
       }
       switch (rj) {
-        case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 1>(c, A);
-        case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 1>(c, A);
-        default: return launch_sf<T, 4, PHASE, KIND, false, false, 1>(c, A);
+        case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 1, STG>(c, A);
+        case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 1, STG>(c, A);
+        default: return launch_sf<T, 4, PHASE, KIND, false, false, 1, STG>(c, A);
       }
     }
   }
@@ -637,16 +653,16 @@ static int launch_sf_any(pa_ctx* c, Cg3dArgs<T>& A) {
   if constexpr (CAN_U) {
     if (A.aux) {
       switch (rj) {
-        case 1: return launch_sf<T, 1, PHASE, KIND, true>(c, A);
-        case 2: return launch_sf<T, 2, PHASE, KIND, true>(c, A);
-        default: return launch_sf<T, 4, PHASE, KIND, true>(c, A);
+        case 1: return launch_sf<T, 1, PHASE, KIND, true, false, 0, STG>(c, A);
+        case 2: return launch_sf<T, 2, PHASE, KIND, true, false, 0, STG>(c, A);
+        default: return launch_sf<T, 4, PHASE, KIND, true, false, 0, STG>(c, A);
       }
     }
   }
   switch (rj) {
-    case 1: return launch_sf<T, 1, PHASE, KIND, false>(c, A);
-    case 2: return launch_sf<T, 2, PHASE, KIND, false>(c, A);
-    default: return launch_sf<T, 4, PHASE, KIND, false>(c, A);
+    case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 0, STG>(c, A);
+    case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 0, STG>(c, A);
+    default: return launch_sf<T, 4, PHASE, KIND, false, false, 0, STG>(c, A);
   }
 }
 

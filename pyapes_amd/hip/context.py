@@ -272,6 +272,35 @@ class HipContext:
         self._rc(self.lib.pa_euler_step(self.h, self._ptr(phi), self._ptr(out), kind, us, self._ptr(uf),
                                         float(nu), float(dt)))
 
+    def rk_stage(self, phi: Tensor, phi0: Tensor, out: Tensor, c0: float, c1: float, kind: int, u: float | Tensor,
+                 nu: float, dt: float) -> None:
+        """``out = B(c0 * phi0 + c1 * E(phi))``: one fused stage of an SSP Runge-Kutta step (E: the Euler step)."""
+        phi = self._field(phi, "rk_stage")
+        phi0 = self._field(phi0, "rk_stage")
+        out = self._field(out, "rk_stage")
+        uf, us = None, 0.0
+        if isinstance(u, Tensor):
+            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
+        else:
+            us = float(u)
+        self._rc(self.lib.pa_rk_stage(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1),
+                                      kind, us, self._ptr(uf), float(nu), float(dt)))
+
+    def rk_march(self, phi: Tensor, w1: Tensor, w2: Tensor, order: int, kind: int, u: float | Tensor, nu: float,
+                 dt: float, nsteps: int) -> Tensor:
+        """``nsteps`` SSP Runge-Kutta steps of ``order`` enqueued back to back over the three buffers; returns the
+        tensor that holds the final state."""
+        bufs = [self._field(t, "rk_march") for t in (phi, w1, w2)]
+        uf, us = None, 0.0
+        if isinstance(u, Tensor):
+            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
+        else:
+            us = float(u)
+        final = C.c_int(0)
+        self._rc(self.lib.pa_rk_march(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2]), int(order),
+                                      kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), C.byref(final)))
+        return bufs[final.value]
+
     # -- solvers --------------------------------------------------------------------------
     def keep_old(self, x_old: Tensor | None) -> None:
         """Buffer that receives the iterate before the last executed solver iteration (Field.VARo), or None."""

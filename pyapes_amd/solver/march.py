@@ -3,6 +3,10 @@
 ``euler_step(phi, u, nu, dt, fdm_config)``:  phi <- B( phi + dt * ( nu * lap(phi) - div(u phi) ) )
 on the interior set, lap / div being the explicit operators (edge=False) evaluated on the current,
 BC-filled phi.  One fused kernel (``k_euler``) + the ordered BC fill.
+
+``rk_step`` / ``rk_march``: strong-stability-preserving Runge-Kutta steps of order 1, 2, 3 in Shu-Osher form -- every
+stage is the Euler step E followed by a convex combination with the state the step started from, ``c0 phi0 + c1 E(phi_s)``,
+formed inside the step kernel (``Context.rk_stage``).  Order 3 marches central ``Div`` without diffusion up to CFL sqrt(3).
 """
 from __future__ import annotations
 
@@ -15,6 +19,16 @@ from ..backend import require_gpu
 from ..hip.context import context_for
 from ..variables import Field
 from .fdc import _adv_of, div_kind
+
+
+# (c0, c1) of every FUSED stage of a step, in order; the plain Euler stage phi1 = E(phi0) in front of them is implied.
+#   order 2:  phi' = 1/2 phi0 + 1/2 E(phi1)
+#   order 3:  phi2 = 3/4 phi0 + 1/4 E(phi1);  phi' = 1/3 phi0 + 2/3 E(phi2)
+SSP_STAGES: dict[int, list[tuple[float, float]]] = {
+    1: [],
+    2: [(0.5, 0.5)],
+    3: [(3.0 / 4.0, 1.0 / 4.0), (1.0 / 3.0, 2.0 / 3.0)],
+}
 
 
 def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind: int) -> Field:
@@ -78,6 +92,58 @@ def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nst
     final = ctx.euler_march(phi()[0], tmp[0], kind, _adv_of(u, phi), nu, dt, nsteps)
     if final.data_ptr() == tmp[0].data_ptr():
         phi.set_var_tensor(tmp)
+    if hasattr(phi, "_t"):
+        phi.update_time(dt * nsteps)
+    return phi
+
+
+def _rk_args(phi: Field, config: dict | None, order: int, what: str) -> int:
+    """the checks every Runge-Kutta entry makes before it touches a device; returns the Div kind"""
+    if order not in SSP_STAGES:
+        raise ValueError(f"pyapes_amd: {what}: order {order!r} (1, 2 or 3)")
+    if phi.dim != 1:
+        raise NotImplementedError(f"pyapes_amd: {what} is for scalar fields")
+    if getattr(phi.mesh, "slab", None) is not None:
+        raise NotImplementedError(f"pyapes_amd: {what} on a slab mesh (the stages march on one GPU; euler_march does slabs)")
+    cfg = (config or {}).get("div", {"limiter": "upwind"})
+    return div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+
+
+def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config: dict | None = None,
+            order: int = 3) -> Field:
+    """Advance ``phi`` by one SSP Runge-Kutta step of ``order`` (1: the Euler step); returns ``phi``."""
+    kind = _rk_args(phi, config, order, "rk_step")
+    if order == 1:
+        return euler_step(phi, u, nu, dt, config)
+    require_gpu(phi(), "rk_step")
+    ctx = context_for(phi.mesh)
+    ctx.bind_bcs(phi(), phi.bcs, 0)
+    if not phi().is_contiguous():
+        phi.set_var_tensor(phi().contiguous())
+    w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
+    final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, 1)
+    for w in (w1, w2):
+        if final.data_ptr() == w[0].data_ptr():
+            phi.set_var_tensor(w)
+    return phi
+
+
+def rk_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps: int,
+             config: dict | None = None, order: int = 3) -> Field:
+    """``nsteps`` SSP Runge-Kutta steps of ``order`` with no host work in between (one C-ABI call enqueues the whole
+    march: the Euler kernel, then one fused stage kernel per further stage, over three buffers).  Arguments as
+    ``euler_march``; ``phi`` holds the final state on return and its time advances by ``nsteps * dt``."""
+    kind = _rk_args(phi, config, order, "rk_march")
+    require_gpu(phi(), "rk_march")
+    ctx = context_for(phi.mesh)
+    ctx.bind_bcs(phi(), phi.bcs, 0)
+    if not phi().is_contiguous():
+        phi.set_var_tensor(phi().contiguous())
+    w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
+    final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, nsteps)
+    for w in (w1, w2):
+        if final.data_ptr() == w[0].data_ptr():
+            phi.set_var_tensor(w)
     if hasattr(phi, "_t"):
         phi.update_time(dt * nsteps)
     return phi
