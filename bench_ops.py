@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench_ops.py -- secondary measurements for the other rows of SURVEY section 8 (not the driver's
 contract; bench.py is).  One JSON line per workload: explicit Laplacian apply, the explicit
-adv-diff Euler march (BASELINE config 4), the SSP Runge-Kutta march beside its unfused composition, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+adv-diff Euler march (BASELINE config 4), the SSP Runge-Kutta march beside its unfused composition, the self-advected
+march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step composition, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -50,7 +51,9 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--sections", default="ops,euler,rk,small,big",
                     help="comma-separated subset of: ops (explicit operators 512^3), euler (config 4 march), rk (SSP Runge-Kutta march, "
-                         "fused stages against the composition of public pieces), small (the reference's "
+                         "fused stages against the composition of public pieces, then the self-advected march; self: those rows "
+                         "alone; self_baselines: their two comparison rows alone, which need no self march in the library), "
+                         "small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -96,6 +99,8 @@ def main():
         euler_rows(q, emit)
     if "rk" in sections:
         rk_rows(q, emit)
+    if sections & {"rk", "self", "self_baselines"}:
+        self_rows(q, emit, with_self=bool(sections & {"rk", "self"}))
     solver_rows(q, emit, sections)
 
 
@@ -186,6 +191,84 @@ def rk_rows(q, emit):
                 assert bool(torch.isfinite(phi()).all())
                 del phi
         del mesh, start, ut
+        torch.cuda.empty_cache()
+
+
+def self_rows(q, emit, with_self=True):
+    """The self-advected march rk_march(phi, phi) -- div(phi, phi), every launch advected by its own input -- orders 1 and 3,
+    beside (a) rk_march with a SEPARATE speed tensor (a frozen speed: the launches read one more stream; central Div with a
+    foreign field runs on the generic kernel) and (b) the self-advected march composed step by step from public pieces that
+    need no self march: euler_step(phi, copy of phi), c0 * phi0 + c1 * E as torch ops, apply_bcs.  (a) and (b) use nothing
+    of the self march (with_self=False: those two alone).  ms per STEP, min and median of 5 marches of 20 steps, every march
+    from the same start.  Algorithmic passes of a self step: Euler stage 2, every fused stage 3 -- order 3: 8, order 1: 2."""
+    import statistics
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.march import SSP_STAGES, euler_step, rk_march
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    neusym = mixed_bcs([0.0, 0.0, None, None, None, None], ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"])
+    alldir = mixed_bcs([0.0] * 6, ["dirichlet"] * 6)
+    nu, steps, nrep = 1e-3, 20, 5
+
+    def composed(phi, dt, order, cfg):
+        for _ in range(steps):
+            phi0 = phi()
+            euler_step(phi, phi0.clone(), nu, dt, cfg)
+            for c0, c1 in SSP_STAGES[order]:
+                euler_step(phi, phi().clone(), nu, dt, cfg)
+                phi.set_var_tensor(c0 * phi0 + c1 * phi())
+                phi.apply_bcs()
+
+    def measure(phi, start, fn):
+        ms = []
+        for r in range(nrep + 1):          # the first march is the warm-up
+            phi.set_var_tensor(start.clone())
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1) / steps)
+        assert bool(torch.isfinite(phi()).all())
+        return min(ms[1:]), statistics.median(ms[1:])
+
+    if q:
+        sizes = [(128, "single", neusym, "upwind", "config 4 BCs"), (64, "double", alldir, "none", "dirichlet")]
+    else:
+        sizes = [(256, "single", neusym, "upwind", "config 4 BCs"), (512, "single", neusym, "upwind", "config 4 BCs"),
+                 (256, "double", alldir, "none", "dirichlet")]
+    for n, dtype, bcs, limiter, bname in sizes:
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", dtype)
+        es, f = (8, "f64") if dtype == "double" else (4, "f32")
+        cfg = {"div": {"limiter": limiter}}
+        sch = "central" if limiter == "none" else limiter
+        phi = Field("phi", 1, mesh, {"domain": bcs, "obstacle": None})
+        phi.set_var_tensor(torch.exp(-((mesh.X - 0.5) ** 2 + (mesh.Y - 0.5) ** 2 + (mesh.Z - 0.5) ** 2) / 0.02).unsqueeze(0).contiguous())
+        phi.apply_bcs()
+        start = phi().clone()
+        dx = mesh.dx_list[0]
+        dt = 0.2 * min(dx * dx / (6 * nu), dx / 1.0)
+        for order in (3, 1):
+            passes = 2 + 3 * (order - 1)
+            tag = f"order {order} ({steps} steps per call) {n}^3 {f} {sch} ({bname})"
+            res = {}
+            if with_self:
+                res["self"] = measure(phi, start, lambda: rk_march(phi, phi, nu, dt, steps, cfg, order=order))
+            ut = start.clone()
+            res["a"] = measure(phi, start, lambda: rk_march(phi, ut, nu, dt, steps, cfg, order=order))
+            del ut
+            res["b"] = measure(phi, start, lambda: composed(phi, dt, order, cfg))
+            if with_self:
+                emit(f"self-advected rk_march {tag}", n ** 3, res["self"][0], passes, es,
+                     {"ms_median": res["self"][1], "reps": nrep, "self_over_separate_speed": res["self"][0] / res["a"][0],
+                      "self_over_composition": res["self"][0] / res["b"][0]})
+            emit(f"(a) rk_march, separate speed tensor {tag}", n ** 3, res["a"][0], passes + order, es,
+                 {"ms_median": res["a"][1], "reps": nrep})
+            emit(f"(b) self-advected composition (euler_step with a copy as speed + torch combine + apply_bcs) {tag}", n ** 3,
+                 res["b"][0], passes + order, es, {"ms_median": res["b"][1], "reps": nrep})
+        del phi, mesh, start
         torch.cuda.empty_cache()
 
 

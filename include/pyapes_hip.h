@@ -219,6 +219,10 @@ int pa_jacobi(pa_ctx* ctx, void* x, const void* rhs, double tol, int64_t max_it,
  * In slab mode (pa_slab_set) the step reads the ghost planes x_ghost_lo / hi (NULL = physical end) and leaves the BC
  * fill B to the driver (pyapes_amd/slab.py SlabEuler: exchange first / last plane of phi -> step -> on a periodic axis 0
  * exchange the far planes of phi_out -> pa_apply_bc). */
+/* u_field == phi_in (the same pointer) is self-advection, Div(phi, phi) -- Burgers' term: the speed at a node and at its
+ * neighbours (central scheme: cP = phi[+1], cC = 0*phi, cM = -phi[-1] per axis) are the field's own values.  The bits are
+ * those of a separate copy of phi_in handed in as u_field; the vector kernels then read no speed stream at all, and the
+ * central scheme runs tiled.  The same holds for pa_rk_stage with u_field == phi. */
 int pa_euler_step(pa_ctx* ctx, const void* phi_in, void* phi_out, int div_kind, double u,
                   const void* u_field, double nu, double dt);
 
@@ -237,11 +241,18 @@ int pa_euler_march(pa_ctx* ctx, void* phi, void* tmp, int div_kind, double u, co
  *                 synchronisation; *final = index (0, 1, 2 for phi, w1, w2) of the buffer that holds the result.
  *                 order 1: pa_euler_march(phi, w1).  order 2: p1 = E(p0); p' = 1/2 p0 + 1/2 E(p1).
  *                 order 3: p1 = E(p0); p2 = 3/4 p0 + 1/4 E(p1); p' = 1/3 p0 + 2/3 E(p2).
- *                 PA_E_ARG: order not in {1, 2, 3}, aliased buffers, bad div_kind. */
+ *                 PA_E_ARG: order not in {1, 2, 3}, aliased buffers, bad div_kind.
+ *                 u_field stays ONE pointer for the whole march: a frozen speed.  It must not be one of the buffers.
+ *   pa_rk_march_self   the same march of a field that advects itself: every launch takes ITS OWN input buffer as the
+ *                 speed, so a stage is B( c0*phi0 + c1*E_self(phi_s) ) with E_self(p) = B( p + dt (nu lap(p) - Div(u = p, p)) )
+ *                 -- the speed is the stage's input phi_s, never phi0.  Buffers, *final, error codes as pa_rk_march; order 1
+ *                 uses phi and w1 only (w2 may be NULL). */
 int pa_rk_stage(pa_ctx* ctx, const void* phi, const void* phi0, void* out, double c0, double c1, int div_kind,
                 double u, const void* u_field, double nu, double dt);
 int pa_rk_march(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double u, const void* u_field,
                 double nu, double dt, int64_t nsteps, int* final);
+int pa_rk_march_self(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double nu, double dt,
+                     int64_t nsteps, int* final);
 
 /* ---- vector steps for a host-stepped solver loop (pyapes_amd/solver/host_stepped.py: BC callables that read the iterate
  * make the reference's loop come back to Python for every face of every fill, bcs.py:200-253; the loop's AXPYs and dot

@@ -297,6 +297,7 @@ template <typename T>
 int pa_tile3d_aop(pa_ctx* c, const DevEq<T>& E, Vec<T> x, T* y, int interior_only);
 template <typename T>
 int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd);
+// u_field == phi.p: the field advects itself -- k_sf's SELF instantiations (pa_sf_self.hip), central Div included
 template <typename T>
 int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt,
                     int bcl = 0,    // bcl: "BC on load" (pa_sf_kernel.h); 0 is returned when that form does not apply

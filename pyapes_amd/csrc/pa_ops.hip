@@ -569,9 +569,10 @@ static int rk_launch_t(pa_ctx* c, bool* bcl, int64_t nlaunch, T* in, T* out, con
   return euler_t<T>(c, in, out, kind, u, u_field, nu, dt, phi0, c0, c1);
 }
 
+// self: the field advects itself -- every launch takes its own input buffer as the speed field (pa_rk_march_self)
 template <typename T>
 static int rk_march_t(pa_ctx* c, T* b0, T* b1, T* b2, int order, int kind, double u, const void* u_field, double nu,
-                      double dt, int64_t nsteps, int* final) {
+                      double dt, int64_t nsteps, int* final, bool self = false) {
   // the fused stages of a step in Shu-Osher form, after its plain Euler stage: (c0, c1) of c0 phi0 + c1 E(phi_s)
   const double st2[1][2] = {{0.5, 0.5}};
   const double st3[2][2] = {{3.0 / 4.0, 1.0 / 4.0}, {1.0 / 3.0, 2.0 / 3.0}};
@@ -581,11 +582,12 @@ static int rk_march_t(pa_ctx* c, T* b0, T* b1, T* b2, int order, int kind, doubl
   bool bcl = march_bcl_wanted(c, kind, nsteps);
   int64_t nl = 0;
   for (int64_t s = 0; s < nsteps; ++s) {
-    int rc = rk_launch_t<T>(c, &bcl, nl++, buf[base], buf[wa], nullptr, 0.0, 0.0, kind, u, u_field, nu, dt);
+    int rc = rk_launch_t<T>(c, &bcl, nl++, buf[base], buf[wa], nullptr, 0.0, 0.0, kind, u, self ? buf[base] : u_field, nu, dt);
     if (rc) return rc;
     int cur = wa, free_ = wb;
     for (int q = 0; q < order - 1; ++q) {
-      rc = rk_launch_t<T>(c, &bcl, nl++, buf[cur], buf[free_], buf[base], st[q][0], st[q][1], kind, u, u_field, nu, dt);
+      rc = rk_launch_t<T>(c, &bcl, nl++, buf[cur], buf[free_], buf[base], st[q][0], st[q][1], kind, u, self ? buf[cur] : u_field, nu,
+                          dt);
       if (rc) return rc;
       std::swap(cur, free_);
     }
@@ -724,17 +726,16 @@ int pa_euler_step(pa_ctx* c, const void* in, void* out, int kind, double u, cons
                             : euler_t<float>(c, (const float*)in, (float*)out, kind, u, u_field, nu, dt);
 }
 
-int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field, double nu, double dt,
-                   int64_t nsteps) {
-  if (!c || !c->grid_set) return PA_E_STATE;
-  int rc = check_div_kind(c, kind);
-  if (rc) return rc;
-  if (phi == tmp || nsteps < 0) { pa_set_err(c, "pa_euler_march: bad buffers / step count"); return PA_E_ARG; }
+// self: every step takes its own input buffer as the speed field (order 1 of pa_rk_march_self)
+static int euler_march_impl(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field_, double nu, double dt,
+                            int64_t nsteps, bool self) {
+  int rc;
   PaRange range_("pyapes explicit Euler march");
   PA_HIP(c, hipSetDevice(c->device));
   void* buf[2] = {phi, tmp};
   bool bcl = march_bcl_wanted(c, kind, nsteps);
   for (int64_t s = 0; s < nsteps; ++s) {
+    const void* u_field = self ? buf[s & 1] : u_field_;
     if (bcl) {
       const int fr = c->dtype == PA_F64
                          ? euler_bcl_t<double>(c, (const double*)buf[s & 1], (double*)buf[(s + 1) & 1], kind, u, u_field, nu, dt)
@@ -755,6 +756,15 @@ int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const vo
                               : pa_bc_apply_auto<float>(c, (float*)buf[nsteps & 1], false);
   }
   return PA_OK;
+}
+
+int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field, double nu, double dt,
+                   int64_t nsteps) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  int rc = check_div_kind(c, kind);
+  if (rc) return rc;
+  if (phi == tmp || nsteps < 0) { pa_set_err(c, "pa_euler_march: bad buffers / step count"); return PA_E_ARG; }
+  return euler_march_impl(c, phi, tmp, kind, u, u_field, nu, dt, nsteps, false);
 }
 
 int pa_rk_stage(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind, double u,
@@ -794,6 +804,30 @@ int pa_rk_march(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, d
   return c->dtype == PA_F64
              ? rk_march_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, u, u_field, nu, dt, nsteps, final)
              : rk_march_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, u, u_field, nu, dt, nsteps, final);
+}
+
+int pa_rk_march_self(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double nu, double dt, int64_t nsteps,
+                     int* final) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  if (order < 1 || order > 3) { pa_set_err(c, "pa_rk_march_self: order %d (1, 2 or 3)", order); return PA_E_ARG; }
+  int rc = check_div_kind(c, kind);
+  if (rc) return rc;
+  if (!phi || !w1 || !final || phi == w1 || nsteps < 0 || (order > 1 && (!w2 || phi == w2 || w1 == w2))) {
+    pa_set_err(c, "pa_rk_march_self: distinct buffers (two for order 1, else three), a place for the result index and "
+                  "nsteps >= 0 are needed");
+    return PA_E_ARG;
+  }
+  if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "pa_rk_march_self: single GPU only (no slab stages)"); return PA_E_STATE; }
+  if (order == 1) {   // plain Euler, the speed ping-pongs with the field
+    rc = euler_march_impl(c, phi, w1, kind, 0.0, nullptr, nu, dt, nsteps, true);
+    if (!rc) *final = (int)(nsteps & 1);
+    return rc;
+  }
+  PaRange range_("pyapes SSP Runge-Kutta march, self-advected");
+  PA_HIP(c, hipSetDevice(c->device));
+  return c->dtype == PA_F64
+             ? rk_march_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, 0.0, nullptr, nu, dt, nsteps, final, true)
+             : rk_march_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, 0.0, nullptr, nu, dt, nsteps, final, true);
 }
 
 }  // extern "C"

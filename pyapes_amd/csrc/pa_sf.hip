@@ -3,7 +3,8 @@
 // run on k_sf (pa_sf_kernel.h: wave-autonomous marching, no LDS, no barrier) where rows are whole 16-byte
 // vectors; the Laplacian alone and the gradient stay on k_cg3d's phases 2 / 7 (pa_cg3d_kernel.h), which move
 // their 2 / 4 passes at the speed of a device copy, as does everything k_sf does not take (odd row lengths,
-// unaligned operands, tensor coefficient, 2-D meshes).
+// unaligned operands, tensor coefficient, 2-D meshes).  The Euler step of a field that advects itself (u_field == phi) has
+// k_sf instantiations of its own, SELF, in pa_sf_self.hip.
 #include "pa_sf_kernel.h"
 
 template <typename T>
@@ -16,7 +17,9 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
   pa_build_eq<T>(c, 1, &t, E);
   const int mode = cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0});   // (a stage's phi0 counts for the alignment)
   if (!mode) return 0;
-  if (kind == PA_OP_DIV_CENTRAL && u_field) return 0;  // needs u at the neighbours: generic kernel
+  // the field advects itself: the speed at the cell and at its neighbours are the stencil's own operands (k_sf SELF)
+  const bool self = u_field && u_field == (const void*)phi.p;
+  if (kind == PA_OP_DIV_CENTRAL && u_field && !self) return 0;  // needs a foreign u at the neighbours: generic kernel
   Cg3dArgs<T> A;
   memset(&A, 0, sizeof(A));
   fill_common<T>(c, E, A);
@@ -28,8 +31,13 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
     for (int f = 0; f < 6; ++f) faces += (c->G.act[f >> 1] && c->bc[f].type != PA_BC_NONE) ? 1 : 0;
     A.out_all = faces == 2 * c->ndim ? 1 : 0;
   }
+  const bool sf = sf_applies<T, 3>(c, A, mode);
+  // central self off k_sf: k_cg3d reads the speed at the cell only.  On a slab the generic kernel takes u's axis-0
+  // neighbours from the rank's own planes, k_sf would take the ghost planes: the generic kernel keeps its bits
+  if (kind == PA_OP_DIV_CENTRAL && self && (!sf || c->G.n0 != c->G.g0)) return 0;
+  if (self && sf) A.aux = nullptr;   // nothing is loaded through aux (k_cg3d, upwind: aux stays the field)
   if (bcl) {   // BC on load (k_sf only): the fill values of the face interiors are formed from the stencil's own operands
-    if (!A.out_all || !sf_applies<T, 3>(c, A, mode) || kind != PA_OP_DIV_UPWIND) return 0;
+    if (!A.out_all || !sf || kind != PA_OP_DIV_UPWIND) return 0;
     A.bcl_c43 = (T)(4.0 / 3.0);
     A.bcl_c13 = (T)(1.0 / 3.0);
     for (int f = 0; f < 6; ++f) {
@@ -47,7 +55,8 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
   }
   auto launch = [&](auto STGC) -> int {
     constexpr bool STG = decltype(STGC)::value;
-    if (!sf_applies<T, 3>(c, A, mode)) return launch_any<T, 3, STG>(c, A, mode);
+    if (!sf) return launch_any<T, 3, STG>(c, A, mode);
+    if (self) return pa_sf_euler_self<T>(c, A, kind, STG);
     switch (kind) {
       case PA_OP_DIV_CENTRAL: return launch_sf_any<T, 3, PA_OP_DIV_CENTRAL, STG>(c, A);
       case PA_OP_DIV_UPWIND_COMPAT: return launch_sf_any<T, 3, PA_OP_DIV_UPWIND_COMPAT, STG>(c, A);

@@ -98,11 +98,19 @@ template <> struct SfBits<double> {
 // stage stores c0 * phi0 + c1 * e instead (two products, one sum, each rounded).  phi0 is read at the cell only, one
 // 16-byte lane access per row like the field's own rows, issued at the top of the plane IN FRONT of the loads of plane
 // q + 2 -- the wait for it at the end of the first row then leaves those in flight.  RJ * VEC more live registers.
+// SELF: the field advects itself (Burgers' term Div(phi, phi); pa_euler_step / pa_rk_stage with u_field == phi_in, every
+// launch of pa_rk_march_self).  The speed at the cell and at its six neighbours are the stencil operands the row holds
+// anyway, so there is no U plane and no load through A.aux: the upwind schemes take uc = xc, the central scheme its per-axis
+// rows cP = x[+1], cC = 0 * x, cM = -x[-1] from the neighbour operands xp3 / xm3 -- across lanes, tiles and row blocks those
+// come from the DPP moves, the edge cells He and the rows Hu / Hd like every other neighbour.  Operation for operation what
+// HASU (upwind) and the generic k_euler (central) compute with u_field a copy of the field: the same bits
+// (tests/test_gpu_self_march.py).  With BCL the centre of an interior node is an interior node: its value is genuine.
 #ifndef PA_SF_USIGN
 #define PA_SF_USIGN 1
 #endif
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false>
 __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
+  static_assert(!SELF || (PHASE == 3 && !HASU && US == 0), "SELF: the Euler step, no other speed");
   static_assert(!BCL || PHASE == 3, "BC on load: the Euler step");
   static_assert(!STG || PHASE == 3, "STG: the Euler step");
   static_assert(US == 0 || (KIND == 4 && !HASU), "US: scalar speed of the upwind scheme");
@@ -237,7 +245,7 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 
   // scalar speed: u+ / u- (upwind) or the three rows (literal upwind) once
   V uplC = (V)(T)0, umiC = (V)(T)0;
-  if (DIV && !HASU) {
+  if (DIV && !HASU && !SELF) {
     const T u = A.u;
     uplC = (V)(u > (T)0 ? u : (T)0);
     umiC = (V)(u < (T)0 ? u : (T)0);
@@ -459,8 +467,9 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
           const V xp3[3] = {xpi, dn, xpk}, xm3[3] = {xmi, up, xmk};
           if (KIND == 4) {
             V upl = uplC, umi = umiC;
-            if constexpr (HASU) {
-              const V uc = U[HC][jj];
+            if constexpr (HASU || SELF) {
+              V uc;
+              if constexpr (SELF) uc = xc; else uc = U[HC][jj];
 #pragma unroll
               for (int v = 0; v < VEC; ++v) {
                 upl[v] = uc[v] > (T)0 ? uc[v] : (T)0;
@@ -488,7 +497,7 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
             }
           } else if (KIND == 3) {
             V uc;
-            if constexpr (HASU) uc = U[HC][jj]; else uc = (V)A.u;
+            if constexpr (SELF) uc = xc; else if constexpr (HASU) uc = U[HC][jj]; else uc = (V)A.u;
             V cP, cC, cM;
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
@@ -507,10 +516,11 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
             }
           } else {
             V uc;
-            if constexpr (HASU) uc = U[HC][jj]; else uc = (V)A.u;
+            if constexpr (SELF) uc = xc; else if constexpr (HASU) uc = U[HC][jj]; else uc = (V)A.u;
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
               V cP = uc, cC = (T)0 * uc, cM = -uc;
+              if constexpr (SELF) { cP = xp3[a]; cM = -xm3[a]; }   // the speed at the axis' two neighbours
 #pragma unroll
               for (int v = 0; v < VEC; ++v) {
                 const bool lo = a == 0 ? iPLo : (a == 1 ? rPLo[jj] : cPLo[v]);
@@ -565,18 +575,18 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false>
 static int sf_blocks_per_cu() {
   static int cached = 0;
   if (!cached) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG>, 256, 0) != hipSuccess || n <= 0) n = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>, 256, 0) != hipSuccess || n <= 0) n = 4;
     cached = n;
   }
   return cached;
 }
 
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false>
 static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr int VEC = VecOf<T>::N;
   constexpr int TJ = 4 * RJ, TK = 64 * VEC;
@@ -584,7 +594,7 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
   A.tiles_k = (int)((G.n2 + TK - 1) / TK);
   const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG>();
+  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>();
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
@@ -595,11 +605,11 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
   if (dbg > 0) {
     --dbg;
-    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
-            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG>());
+    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
+            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
+            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>());
   }
-  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG>), dim3(nblk), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>), dim3(nblk), dim3(256), 0, c->stream, A);
   return nblk;
 }
 
@@ -608,20 +618,20 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
 //   fp64 512^3: 493 / 442 / 447 (553)   256^3: 45.3 / 45.2 / 45.5 (65.3)   128^3: 14.0 / 11.4 / 12.9 (15.1)
 // Four rows (least re-read of the rows above / below, ~230 VGPRs, two waves per SIMD) where a workgroup still
 // marches >= 32 planes, else two (the three planes of prologue weigh less on short chunks).
-template <typename T, int PHASE, int KIND, bool STG = false>
-static int launch_sf_any(pa_ctx* c, Cg3dArgs<T>& A) {
+template <typename T>
+static int sf_rows_per_wave(pa_ctx* c) {
   constexpr int VEC = VecOf<T>::N;
   const DevGeom& G = c->G;
-  int rj;
-  if (G.n1 <= 4) {
-    rj = 1;
-  } else if (G.n1 <= 8) {
-    rj = 2;
-  } else {
-    const int64_t tiles4 = ((G.n1 + 15) / 16) * ((G.n2 + 64 * VEC - 1) / (64 * VEC));
-    const int64_t chunks4 = std::max<int64_t>(1, (int64_t)cus_of(c) * 2 / tiles4);
-    rj = G.n0 / chunks4 >= 32 ? 4 : 2;
-  }
+  if (G.n1 <= 4) return 1;
+  if (G.n1 <= 8) return 2;
+  const int64_t tiles4 = ((G.n1 + 15) / 16) * ((G.n2 + 64 * VEC - 1) / (64 * VEC));
+  const int64_t chunks4 = std::max<int64_t>(1, (int64_t)cus_of(c) * 2 / tiles4);
+  return G.n0 / chunks4 >= 32 ? 4 : 2;
+}
+
+template <typename T, int PHASE, int KIND, bool STG = false>
+static int launch_sf_any(pa_ctx* c, Cg3dArgs<T>& A) {
+  const int rj = sf_rows_per_wave<T>(c);
   if constexpr (PHASE == 3 && KIND == PA_OP_DIV_UPWIND) {   // BC on load: the upwind march (BASELINE config 4)
     if (A.bcl_type[0] | A.bcl_type[1] | A.bcl_type[2] | A.bcl_type[3] | A.bcl_type[4] | A.bcl_type[5]) {
       if (rj < 2 || (c->G.n1 - 1) % rj == 0) return 0;   // PATCH: rows n1 - 2, n1 - 1 in one wave's block
@@ -665,6 +675,27 @@ static int launch_sf_any(pa_ctx* c, Cg3dArgs<T>& A) {
     default: return launch_sf<T, 4, PHASE, KIND, false, false, 0, STG>(c, A);
   }
 }
+
+// The Euler step / stage of a field that advects itself (SELF), rows per wave and the BC-on-load condition as above.  The
+// instantiations live in a translation unit of their own (pa_sf_self.hip), behind pa_sf_euler_self.
+template <typename T, int KIND, bool STG>
+static int launch_sf_self(pa_ctx* c, Cg3dArgs<T>& A) {
+  const int rj = sf_rows_per_wave<T>(c);
+  if constexpr (KIND == PA_OP_DIV_UPWIND) {
+    if (A.bcl_type[0] | A.bcl_type[1] | A.bcl_type[2] | A.bcl_type[3] | A.bcl_type[4] | A.bcl_type[5]) {
+      if (rj < 2 || (c->G.n1 - 1) % rj == 0) return 0;   // PATCH: rows n1 - 2, n1 - 1 in one wave's block
+      return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 0, STG, true>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 0, STG, true>(c, A);
+    }
+  }
+  switch (rj) {
+    case 1: return launch_sf<T, 1, 3, KIND, false, false, 0, STG, true>(c, A);
+    case 2: return launch_sf<T, 2, 3, KIND, false, false, 0, STG, true>(c, A);
+    default: return launch_sf<T, 4, 3, KIND, false, false, 0, STG, true>(c, A);
+  }
+}
+// blocks launched, or 0 when k_sf does not take the launch (A as pa_tile3d_euler fills it; aux is not read)
+template <typename T>
+int pa_sf_euler_self(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage);
 
 // can k_sf take this launch?  Full 16-byte vectors only (mode 1 of cg3d_mode), scalar coefficient.
 template <typename T, int PHASE>

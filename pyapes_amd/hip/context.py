@@ -301,6 +301,19 @@ class HipContext:
                                       kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), C.byref(final)))
         return bufs[final.value]
 
+    def rk_march_self(self, phi: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int, nu: float, dt: float,
+                      nsteps: int) -> Tensor:
+        """``rk_march`` of a field that advects itself: every launch takes its own input buffer as the speed.  Order 1
+        needs no ``w2``.  Returns the tensor that holds the final state."""
+        bufs = [self._field(t, "rk_march_self") for t in (phi, w1)]
+        if w2 is not None:
+            bufs.append(self._field(w2, "rk_march_self"))
+        final = C.c_int(0)
+        self._rc(self.lib.pa_rk_march_self(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]),
+                                           self._ptr(bufs[2] if len(bufs) > 2 else None), int(order), kind, float(nu),
+                                           float(dt), int(nsteps), C.byref(final)))
+        return bufs[final.value]
+
     # -- solvers --------------------------------------------------------------------------
     def keep_old(self, x_old: Tensor | None) -> None:
         """Buffer that receives the iterate before the last executed solver iteration (Field.VARo), or None."""

@@ -100,6 +100,7 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "pa_rk_stage": (C.c_int, [_VP, _VP, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_double, _VP, C.c_double, C.c_double]),
     "pa_rk_march": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, _VP, C.c_double, C.c_double, C.c_int64,
                               C.POINTER(C.c_int)]),
+    "pa_rk_march_self": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int)]),
     "pa_cg_begin": (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_int64]),
     "pa_cg_phase_a": (C.c_int, [_VP]),
     "pa_cg_phase_b": (C.c_int, [_VP]),

@@ -7,6 +7,11 @@ BC-filled phi.  One fused kernel (``k_euler``) + the ordered BC fill.
 ``rk_step`` / ``rk_march``: strong-stability-preserving Runge-Kutta steps of order 1, 2, 3 in Shu-Osher form -- every
 stage is the Euler step E followed by a convex combination with the state the step started from, ``c0 phi0 + c1 E(phi_s)``,
 formed inside the step kernel (``Context.rk_stage``).  Order 3 marches central ``Div`` without diffusion up to CFL sqrt(3).
+
+Self-advection, ``div(phi, phi)`` (Burgers' term): pass the field itself as ``u`` -- ``euler_march(phi, phi, ...)``,
+``rk_march(phi, phi, ...)`` -- or a Tensor / Field on ``phi()``'s own storage (``advects_itself``).  Every step and every
+stage is then advected by ITS OWN input, ``B(c0 phi0 + c1 E_self(phi_s))`` with the speed ``phi_s``, through
+``Context.rk_march_self``.  A clone of ``phi`` is a speed frozen at the start of the call, as any other tensor.
 """
 from __future__ import annotations
 
@@ -29,6 +34,23 @@ SSP_STAGES: dict[int, list[tuple[float, float]]] = {
     2: [(0.5, 0.5)],
     3: [(3.0 / 4.0, 1.0 / 4.0), (1.0 / 3.0, 2.0 / 3.0)],
 }
+
+
+def advects_itself(phi: Field, u: Any) -> bool:
+    """``u`` is ``phi`` -- the same Field object, or a Tensor / Field whose storage is ``phi()``'s own (same ``data_ptr``,
+    same shape) -- so the march advects the field by itself.  A clone is not: it stays what it was."""
+    if u is phi:
+        return True
+    t = u() if isinstance(u, Field) else u
+    if not isinstance(t, Tensor):
+        return False
+    p = phi()
+    return t.data_ptr() == p.data_ptr() and tuple(t.shape) == tuple(p.shape)
+
+
+def _no_self_on_slabs(phi: Field, what: str) -> None:
+    if getattr(phi.mesh, "slab", None) is not None:
+        raise NotImplementedError(f"pyapes_amd: {what}: self-advection on a slab mesh (single GPU only)")
 
 
 def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind: int) -> Field:
@@ -78,6 +100,9 @@ def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nst
         raise NotImplementedError("pyapes_amd: euler_march is for scalar fields")
     cfg = (config or {}).get("div", {"limiter": "upwind"})
     kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+    self_adv = advects_itself(phi, u)
+    if self_adv:
+        _no_self_on_slabs(phi, "euler_march")
     if getattr(phi.mesh, "slab", None) is not None:
         phi = _march_on_slabs(phi, u, nu, dt, nsteps, kind)
         if hasattr(phi, "_t"):
@@ -89,7 +114,10 @@ def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nst
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
     tmp = torch.empty_like(phi())
-    final = ctx.euler_march(phi()[0], tmp[0], kind, _adv_of(u, phi), nu, dt, nsteps)
+    if self_adv:   # the speed ping-pongs with the field: no single pointer names it
+        final = ctx.rk_march_self(phi()[0], tmp[0], None, 1, kind, nu, dt, nsteps)
+    else:
+        final = ctx.euler_march(phi()[0], tmp[0], kind, _adv_of(u, phi), nu, dt, nsteps)
     if final.data_ptr() == tmp[0].data_ptr():
         phi.set_var_tensor(tmp)
     if hasattr(phi, "_t"):
@@ -114,14 +142,18 @@ def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config:
     """Advance ``phi`` by one SSP Runge-Kutta step of ``order`` (1: the Euler step); returns ``phi``."""
     kind = _rk_args(phi, config, order, "rk_step")
     if order == 1:
-        return euler_step(phi, u, nu, dt, config)
+        return euler_step(phi, u, nu, dt, config)   # (a speed on phi's own storage is self-advection at the C ABI)
+    self_adv = advects_itself(phi, u)
     require_gpu(phi(), "rk_step")
     ctx = context_for(phi.mesh)
     ctx.bind_bcs(phi(), phi.bcs, 0)
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
     w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
-    final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, 1)
+    if self_adv:
+        final = ctx.rk_march_self(phi()[0], w1[0], w2[0], order, kind, nu, dt, 1)
+    else:
+        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, 1)
     for w in (w1, w2):
         if final.data_ptr() == w[0].data_ptr():
             phi.set_var_tensor(w)
@@ -132,15 +164,20 @@ def rk_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps
              config: dict | None = None, order: int = 3) -> Field:
     """``nsteps`` SSP Runge-Kutta steps of ``order`` with no host work in between (one C-ABI call enqueues the whole
     march: the Euler kernel, then one fused stage kernel per further stage, over three buffers).  Arguments as
-    ``euler_march``; ``phi`` holds the final state on return and its time advances by ``nsteps * dt``."""
+    ``euler_march``; ``phi`` holds the final state on return and its time advances by ``nsteps * dt``.  ``u`` being
+    ``phi`` itself (``advects_itself``) marches ``div(phi, phi)``: every stage is advected by its own input."""
     kind = _rk_args(phi, config, order, "rk_march")
+    self_adv = advects_itself(phi, u)
     require_gpu(phi(), "rk_march")
     ctx = context_for(phi.mesh)
     ctx.bind_bcs(phi(), phi.bcs, 0)
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
     w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
-    final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, nsteps)
+    if self_adv:
+        final = ctx.rk_march_self(phi()[0], w1[0], None if order == 1 else w2[0], order, kind, nu, dt, nsteps)
+    else:
+        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, nsteps)
     for w in (w1, w2):
         if final.data_ptr() == w[0].data_ptr():
             phi.set_var_tensor(w)
