@@ -53,7 +53,8 @@ def main():
                     help="comma-separated subset of: ops (explicit operators 512^3), euler (config 4 march), rk (SSP Runge-Kutta march, "
                          "fused stages against the composition of public pieces, then the self-advected march; self: those rows "
                          "alone; self_baselines: their two comparison rows alone, which need no self march in the library), "
-                         "small (the reference's "
+                         "quick (the QUICK Euler step and order-3 march on k_sfq beside the generic kernel and beside upwind; not in "
+                         "the default list; quick_baseline: the upwind rows alone, which a library without QUICK can run), small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -99,6 +100,8 @@ def main():
         euler_rows(q, emit)
     if "rk" in sections:
         rk_rows(q, emit)
+    if sections & {"quick", "quick_baseline"}:
+        quick_rows(q, emit, with_quick="quick" in sections)
     if sections & {"rk", "self", "self_baselines"}:
         self_rows(q, emit, with_self=bool(sections & {"rk", "self"}))
     solver_rows(q, emit, sections)
@@ -190,6 +193,61 @@ def rk_rows(q, emit):
                      ms_u, passes, es, {"fused_over_unfused": ms_f / ms_u})
                 assert bool(torch.isfinite(phi()).all())
                 del phi
+        del mesh, start, ut
+        torch.cuda.empty_cache()
+
+
+def quick_rows(q, emit, with_quick=True):
+    """Div limiter "quick" (k_sfq, csrc/pa_sfq_kernel.h) with the config-4 BCs, fp32: the Euler step with a scalar speed and with a
+    speed tensor, and rk_march order 3 (20 steps per call, ms per STEP) -- each beside (a) the upwind row with "bcl": 0 (step +
+    fill per launch, what QUICK does too) and (b) QUICK on the generic kernel ("sfq": 0); "sfq": 2 / 4 force the rows per
+    wave.  The variants of a row are timed in turn, three rounds; "ms" is the median, "ms_rounds" all three.  Algorithmic
+    passes as for upwind: step 2 (3 with a speed tensor), order-3 step 8."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.march import euler_step, rk_march
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    bcs = mixed_bcs([0.0, 0.0, None, None, None, None],
+                    ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"])
+    up, qk = {"div": {"limiter": "upwind"}}, {"div": {"limiter": "quick"}}
+    nu, steps = 1e-3, 20
+    variants = [("upwind bcl 0", up, {"bcl": 0, "sfq": 1}), ("quick", qk, {"bcl": 1, "sfq": 1}), ("quick sfq 0", qk, {"sfq": 0}),
+                ("quick sfq 2", qk, {"sfq": 2}), ("quick sfq 4", qk, {"sfq": 4})]
+    if not with_quick:   # (a library from before QUICK knows neither the kind nor the option)
+        variants = [("upwind bcl 0", up, {"bcl": 0})]
+    for n in ([128] if q else [256, 512]):
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", "single")
+        ctx = context_for(mesh)
+        start = torch.exp(-((mesh.X - 0.5) ** 2 + (mesh.Y - 0.5) ** 2 + (mesh.Z - 0.5) ** 2) / 0.02).unsqueeze(0).contiguous()
+        dx = mesh.dx_list[0]
+        dt = 0.2 * min(dx * dx / (6 * nu), dx / 1.0)
+        ut = torch.ones_like(start) * 0.7
+        iters = 400 if n <= 256 else 60
+        works = [("euler step", "scalar u", 2, lambda phi, cfg: timed(lambda: euler_step(phi, 1.0, nu, dt, cfg), iters, warm=5)),
+                 ("euler step", "speed tensor", 3, lambda phi, cfg: timed(lambda: euler_step(phi, ut, nu, dt, cfg), iters, warm=5)),
+                 (f"rk_march order 3 ({steps} steps per call)", "scalar u", 8,
+                  lambda phi, cfg: timed(lambda: rk_march(phi, 1.0, nu, dt, steps, cfg, order=3), 3 if n <= 256 else 1, warm=1) / steps)]
+        for what, uname, passes, run in works:
+            rounds = {v[0]: [] for v in variants}
+            for _ in range(3):
+                for vname, cfg, opts in variants:
+                    for k, v in opts.items():
+                        ctx.set_option(k, v)
+                    phi = Field("phi", 1, mesh, {"domain": bcs, "obstacle": None})
+                    phi.set_var_tensor(start.clone())
+                    phi.apply_bcs()
+                    rounds[vname].append(run(phi, cfg))
+                    assert bool(torch.isfinite(phi()).all())
+                    del phi
+            base = sorted(rounds["upwind bcl 0"])[1]
+            for vname, _, opts in variants:
+                ms = sorted(rounds[vname])[1]
+                emit(f"{what} {n}^3 f32 {vname} {uname} (config 4 BCs)", n ** 3, ms, passes, 4,
+                     {"ms_rounds": rounds[vname], "over_upwind_bcl0": ms / base, "options": opts})
+        for k, v in (("sfq", 1), ("bcl", 1)) if with_quick else (("bcl", 1),):
+            ctx.set_option(k, v)
         del mesh, start, ut
         torch.cuda.empty_cache()
 

@@ -43,7 +43,11 @@ enum {
   PA_OP_GRAD = 1,          /* solver use is 1-D only (ops.py:145-147) */
   PA_OP_DIV_CENTRAL = 2,   /* limiter "none"  (fdc.py:708-743) */
   PA_OP_DIV_UPWIND_COMPAT = 3, /* limiter "upwind", literal reference output (fdc.py:746-772) */
-  PA_OP_DIV_UPWIND = 4     /* first-order upwind as the reference's test states it (tests/test_fdm.py:239) */
+  PA_OP_DIV_UPWIND = 4,    /* first-order upwind as the reference's test states it (tests/test_fdm.py:239) */
+  /* QUICK, advective form, the speed taken at the node (DESIGN.md "QUICK"): explicit entry points only -- pa_div,
+   * pa_euler_step / _march, pa_rk_stage / _march / _march_self -- on one GPU and an xyz mesh, every active axis with at
+   * least 5 nodes.  pa_eq_set, pa_rhs_adjust and pa_div_general refuse it (PA_E_ARG), a slab does (PA_E_STATE). */
+  PA_OP_DIV_QUICK = 5
 };
 
 enum {
@@ -86,7 +90,7 @@ int pa_ctx_destroy(pa_ctx* ctx);
  * (bit-identical paths; tests/test_gpu_properties.py, test_gpu_fold.py); "resident" changes the grouping of
  * the global sums only (tests/test_gpu_resident.py).  Round 3: "pitch" 0 = odd row lengths on the one-cell-per-lane
  * kernels (else pitched ctx-owned buffers), "cg2d_mincells" = 2-D marching kernel from this many cells on (< 0:
- * never), "bcl" 0 = Euler march with a BC fill per step, "place" 0 = no online placement search in large CG solves
+ * never), "sfq" 0 = the generic kernel instead of k_sfq for the QUICK Euler step / stage (same bits), "bcl" 0 = Euler march with a BC fill per step, "place" 0 = no online placement search in large CG solves
  * (which allocations r / d live in beside the caller's x: csrc/pa_place.hip; results do not depend on it,
  * tests/test_gpu_place.py) with "place_minbytes" (arrays of at least this size; default 128 MiB), "place_blocks"
  * (candidate allocations per role, default 3) and "place_budget" (what the trials may cost, per cent of the time
@@ -173,7 +177,7 @@ int pa_rhs_adjust(pa_ctx* ctx, void* rhs);
 int pa_laplacian(pa_ctx* ctx, const void* x, void* y, int edge);
 /* y is (ndim, n...) */
 int pa_grad(pa_ctx* ctx, const void* x, void* y, int edge);
-/* kind = PA_OP_DIV_*; u_field NULL -> scalar u */
+/* kind = PA_OP_DIV_* (QUICK included); u_field NULL -> scalar u */
 int pa_div(pa_ctx* ctx, int kind, double u, const void* u_field, const void* x, void* y);
 /* edge=True post-pass of Div (fdc.py:290-361): overwrites the two end nodes of y with the one-sided
  * 2nd-order formula times the advection value.  1-D only, like the reference for scalar fields. */

@@ -149,6 +149,23 @@ __device__ __forceinline__ void pa_nbrs(const DevGeom& G, const Acc& a, int ax, 
   }
 }
 
+// the neighbours at distance 2 (QUICK), wrap-around indices on every axis.  Axis 0 has no ghost planes at that distance:
+// the callers keep this off slabs (pa_ops.hip check_quick), so the rank's own planes are the whole axis.
+template <typename T, class Acc>
+__device__ __forceinline__ void pa_nbrs2(const DevGeom& G, const Acc& a, int ax, int64_t i, int64_t j,
+                                         int64_t k, T& xpp, T& xmm) {
+  if (ax == 0) {
+    xpp = a.at(G, pa_wrap(i + 2, G.n0), j, k);
+    xmm = a.at(G, pa_wrap(i - 2, G.n0), j, k);
+  } else if (ax == 1) {
+    xpp = a.at(G, i, pa_wrap(j + 2, G.n1), k);
+    xmm = a.at(G, i, pa_wrap(j - 2, G.n1), k);
+  } else {
+    xpp = a.at(G, i, j, pa_wrap(k + 2, G.n2));
+    xmm = a.at(G, i, j, pa_wrap(k - 2, G.n2));
+  }
+}
+
 __device__ __forceinline__ void pa_gidx(const DevGeom& G, int64_t i, int64_t j, int64_t k, int64_t* g,
                                         int64_t* N) {
   g[0] = i + G.off0; g[1] = j; g[2] = k;
@@ -282,6 +299,40 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
         s = s + m;
         m = cM * xm;
         s = s + m;
+        ax = ax + s;
+      }
+    } else if (t.kind == 5) {  // PA_OP_DIV_QUICK (DESIGN.md "QUICK"): advective form, the speed at the node
+      T ucen = t.u_f ? t.u_f[o] : t.u;
+      T upl = ucen > (T)0 ? ucen : (T)0;
+      T umi = ucen < (T)0 ? ucen : (T)0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (!G.act[a]) continue;
+        T xp, xm, xpp, xmm;
+        pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
+        pa_nbrs2<T>(G, acc, a, i, j, k, xpp, xmm);
+        // a half whose far-upwind node would wrap on an axis that is not periodic falls back to central
+        const bool per = G.bct[2 * a] == 4 || G.bct[2 * a + 1] == 4;
+        T cen = xp - xm;
+        cen = (T)0.5 * cen;
+        T tq = xp + xc;
+        tq = (T)0.375 * tq;
+        T sq = (T)0.875 * xm;
+        tq = tq - sq;
+        sq = (T)0.125 * xmm;
+        T bq = tq + sq;
+        if (!per && g[a] <= 1) bq = cen;
+        tq = xm + xc;
+        tq = (T)0.375 * tq;
+        sq = (T)0.875 * xp;
+        tq = sq - tq;
+        sq = (T)0.125 * xpp;
+        T fq = tq - sq;
+        if (!per && g[a] >= N[a] - 2) fq = cen;
+        T s = upl * bq;
+        T m = umi * fq;
+        s = s + m;
+        s = s * E.grd.ih[a];
         ax = ax + s;
       }
     } else {  // PA_OP_DIV_UPWIND (tests/test_fdm.py:239)

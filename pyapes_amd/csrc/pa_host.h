@@ -189,6 +189,7 @@ struct pa_ctx {
   int64_t prof_n[2] = {0, 0};
   // 3-D fast path switch (PYAPES_HIP_FASTPATH=0 disables; tests compare both)
   int fastpath = 1;
+  int sfq = 1;                   // option "sfq": k_sfq for the QUICK Euler step / stage (0: the generic k_euler; 2 / 4: rows per wave forced); pa_sfq_kernel.h
   int sf = 1;                    // k_sf for the Div-carrying single-field operations (else k_cg3d's phases)
   int resident = 1;              // small meshes: the whole CG / Jacobi solve in one cooperative launch (pa_resident.hip)
   // 1: hipLaunchCooperativeKernel (the runtime guarantees co-residency).  0: a plain launch of the same grid, which
@@ -297,6 +298,10 @@ template <typename T>
 int pa_tile3d_aop(pa_ctx* c, const DevEq<T>& E, Vec<T> x, T* y, int interior_only);
 template <typename T>
 int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd);
+// the QUICK Euler step / stage on k_sfq (pa_sfq.hip): blocks launched, 0 when k_sfq does not take the launch
+template <typename T>
+int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, double nu, double dt, const T* phi0 = nullptr,
+                 double c0 = 0.0, double c1 = 0.0);
 // u_field == phi.p: the field advects itself -- k_sf's SELF instantiations (pa_sf_self.hip), central Div included
 template <typename T>
 int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt,

@@ -402,7 +402,18 @@ static int grad_t(pa_ctx* c, const T* x, T* y, int edge) {
   return PA_OK;
 }
 
-static int check_div_kind(pa_ctx* c, int kind) {
+// `who`: the entry point, for the messages of the QUICK checks
+static int check_div_kind(pa_ctx* c, int kind, const char* who = "pa_div") {
+  if (kind == PA_OP_DIV_QUICK) {
+    // the reach of 2: no ghost planes at that distance, no r-dependent rows.  Neumann / symmetry faces are allowed -- the
+    // fallback next to a face reads BC-filled values only
+    if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "%s: Div quick is single GPU only (no slabs)", who); return PA_E_STATE; }
+    if (c->coord != PA_COORD_XYZ) { pa_set_err(c, "%s: Div quick is for xyz meshes (no axisymmetric rows)", who); return PA_E_ARG; }
+    const int64_t n[3] = {c->G.n0, c->G.n1, c->G.n2};
+    for (int a = 0; a < 3; ++a)
+      if (c->G.act[a] && n[a] < 5) { pa_set_err(c, "%s: Div quick needs at least 5 nodes per axis (%lld)", who, (long long)n[a]); return PA_E_ARG; }
+    return PA_OK;
+  }
   if (kind != PA_OP_DIV_CENTRAL && kind != PA_OP_DIV_UPWIND_COMPAT && kind != PA_OP_DIV_UPWIND) {
     pa_set_err(c, "bad div kind %d", kind);
     return PA_E_ARG;
@@ -459,7 +470,9 @@ static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const voi
     pv.ghi = c->x_ghi ? (const T*)c->x_ghi : in + (c->G.n0 - 1) * c->G.s0;
   }
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);   // slot 0: the step kernel (without its BC fill)
-  int fr = pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 0, phi0, c0, c1);
+  // QUICK: k_sfq or the generic kernel (the tiled paths of pa_tile3d_euler do not know the kind and decline it)
+  int fr = kind == PA_OP_DIV_QUICK ? pa_sfq_euler<T>(c, pv, out, u, u_field, nu, dt, phi0, c0, c1)
+                                   : pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 0, phi0, c0, c1);
   if (fr < 0) return fr;
   if (fr == 0 && phi0) {
     static int dbg = -1;
@@ -540,6 +553,7 @@ __global__ void __launch_bounds__(PA_BLOCK) k_vec_dot_final(const double* __rest
   }
 }
 
+// (QUICK marches with a BC fill per step or stage: kind == PA_OP_DIV_UPWIND below)
 // "BC on load" (pa_sf_kernel.h): when every face has a scalar dirichlet / neumann / symmetry BC the steps of a
 // march need no fill between them -- each forms the face values it reads from its own operands, bit for bit what
 // the fill would have stored -- and ONE ordered fill after the last step completes the result.
@@ -659,6 +673,8 @@ int pa_aop(pa_ctx* c, const void* x, void* y, int interior_only) {
 
 int pa_rhs_adjust(pa_ctx* c, void* rhs) {
   if (!c || !c->grid_set || !c->eq_set) { if (c) pa_set_err(c, "pa_rhs_adjust: grid/equation not set"); return PA_E_STATE; }
+  for (int q = 0; q < c->nterms; ++q)
+    if (c->terms[q].kind == PA_OP_DIV_QUICK) { pa_set_err(c, "pa_rhs_adjust: Div quick is explicit-only"); return PA_E_ARG; }
   PA_HIP(c, hipSetDevice(c->device));
   return c->dtype == PA_F64 ? rhs_adjust_t<double>(c, (double*)rhs) : rhs_adjust_t<float>(c, (float*)rhs);
 }
@@ -718,7 +734,7 @@ int pa_div_edge(pa_ctx* c, double u, const void* u_field, const void* x, void* y
 int pa_euler_step(pa_ctx* c, const void* in, void* out, int kind, double u, const void* u_field, double nu,
                   double dt) {
   if (!c || !c->grid_set) return PA_E_STATE;
-  int rc = check_div_kind(c, kind);
+  int rc = check_div_kind(c, kind, "pa_euler_step");
   if (rc) return rc;
   if (in == out) { pa_set_err(c, "pa_euler_step: in-place step is not allowed"); return PA_E_ARG; }
   PA_HIP(c, hipSetDevice(c->device));
@@ -761,7 +777,7 @@ static int euler_march_impl(pa_ctx* c, void* phi, void* tmp, int kind, double u,
 int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field, double nu, double dt,
                    int64_t nsteps) {
   if (!c || !c->grid_set) return PA_E_STATE;
-  int rc = check_div_kind(c, kind);
+  int rc = check_div_kind(c, kind, "pa_euler_march");
   if (rc) return rc;
   if (phi == tmp || nsteps < 0) { pa_set_err(c, "pa_euler_march: bad buffers / step count"); return PA_E_ARG; }
   return euler_march_impl(c, phi, tmp, kind, u, u_field, nu, dt, nsteps, false);
@@ -770,7 +786,7 @@ int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const vo
 int pa_rk_stage(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind, double u,
                 const void* u_field, double nu, double dt) {
   if (!c || !c->grid_set) return PA_E_STATE;
-  int rc = check_div_kind(c, kind);
+  int rc = check_div_kind(c, kind, "pa_rk_stage");
   if (rc) return rc;
   if (!phi || !phi0 || !out || out == phi || out == phi0) {
     pa_set_err(c, "pa_rk_stage: out must be a buffer of its own (not phi, not phi0)");
@@ -787,7 +803,7 @@ int pa_rk_march(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, d
                 double dt, int64_t nsteps, int* final) {
   if (!c || !c->grid_set) return PA_E_STATE;
   if (order < 1 || order > 3) { pa_set_err(c, "pa_rk_march: order %d (1, 2 or 3)", order); return PA_E_ARG; }
-  int rc = check_div_kind(c, kind);
+  int rc = check_div_kind(c, kind, "pa_rk_march");
   if (rc) return rc;
   if (!phi || !w1 || !w2 || !final || phi == w1 || phi == w2 || w1 == w2 || nsteps < 0) {
     pa_set_err(c, "pa_rk_march: three distinct buffers, a place for the result index and nsteps >= 0 are needed");
@@ -810,7 +826,7 @@ int pa_rk_march_self(pa_ctx* c, void* phi, void* w1, void* w2, int order, int ki
                      int* final) {
   if (!c || !c->grid_set) return PA_E_STATE;
   if (order < 1 || order > 3) { pa_set_err(c, "pa_rk_march_self: order %d (1, 2 or 3)", order); return PA_E_ARG; }
-  int rc = check_div_kind(c, kind);
+  int rc = check_div_kind(c, kind, "pa_rk_march_self");
   if (rc) return rc;
   if (!phi || !w1 || !final || phi == w1 || nsteps < 0 || (order > 1 && (!w2 || phi == w2 || w1 == w2))) {
     pa_set_err(c, "pa_rk_march_self: distinct buffers (two for order 1, else three), a place for the result index and "

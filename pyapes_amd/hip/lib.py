@@ -18,6 +18,7 @@ BC_NONE, BC_DIRICHLET, BC_NEUMANN, BC_SYMMETRY, BC_PERIODIC = 0, 1, 2, 3, 4
 BC_CODE = {"dirichlet": BC_DIRICHLET, "neumann": BC_NEUMANN, "symmetry": BC_SYMMETRY,
            "periodic": BC_PERIODIC}
 OP_LAPLACIAN, OP_GRAD, OP_DIV_CENTRAL, OP_DIV_UPWIND_COMPAT, OP_DIV_UPWIND = 0, 1, 2, 3, 4
+OP_DIV_QUICK = 5   # explicit operators and marches only (include/pyapes_hip.h)
 PA_COORD_XYZ, PA_COORD_RZ = 0, 1
 PA_OK, PA_E_ARG, PA_E_HIP, PA_E_STATE, PA_E_NONFINITE = 0, -1, -2, -3, -4
 PA_NSUM = 8

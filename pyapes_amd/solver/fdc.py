@@ -38,8 +38,26 @@ def div_kind(limiter: str, compat: bool) -> int:
     if limiter == "upwind":
         return L.OP_DIV_UPWIND_COMPAT if compat else L.OP_DIV_UPWIND
     if limiter == "quick":
-        raise NotImplementedError("FDC Div: quick scheme is not implemented yet.")
+        if compat:
+            raise ValueError('FDC Div: limiter "quick" has no compat form (the reference has no quick scheme to reproduce)')
+        return L.OP_DIV_QUICK
     raise RuntimeError(f"FDC Div: {limiter=} is an unknown limiter type.")
+
+
+def quick_explicit_only(kind: int, what: str) -> None:
+    """QUICK exists as an explicit operator only: no stencil rows for a solver equation, no rhs adjustment."""
+    if kind == L.OP_DIV_QUICK:
+        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter quick is explicit-only")
+
+
+def quick_mesh_check(kind: int, mesh: Any, what: str) -> None:
+    """the meshes QUICK's reach of 2 does not cover, refused before a device is touched"""
+    if kind != L.OP_DIV_QUICK:
+        return
+    if getattr(mesh, "slab", None) is not None:
+        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter quick on a slab mesh (single GPU only)")
+    if mesh.coord_sys != "xyz":
+        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter quick on a Cylinder (rz) mesh")
 
 
 def _adv_of(var_j: Any, var_i: Field) -> float | Tensor:
@@ -237,14 +255,20 @@ class Div(Discretizer):
     def adjust_rhs(var_j: Any, var_i: Field, config: DiscretizerConfigType | None = None) -> Tensor:
         assert config is not None and "div" in config, "FDC Div: config should contain 'div' key."
         limiter, compat = _limiter(config["div"])
-        return _rhs_adjust(var_i, {"kind": div_kind(limiter, compat), "u": _adv_of(var_j, var_i)},
-                           var_i.bcs or [])
+        kind = div_kind(limiter, compat)
+        quick_explicit_only(kind, "Div.adjust_rhs")
+        return _rhs_adjust(var_i, {"kind": kind, "u": _adv_of(var_j, var_i)}, var_i.bcs or [])
 
     def apply(self, A_coeffs: StencilSpec, var: Field) -> Tensor:
         assert A_coeffs is not None, "FDC: A_A_coeffs is not defined!"
-        require_gpu(var(), "FDC.div")
         edge = self._edge()
         kind = div_kind(A_coeffs.limiter, A_coeffs.compat)
+        if kind == L.OP_DIV_QUICK:   # a scalar field, the speed a float / Tensor / Field: the explicit operator, no edge form
+            quick_mesh_check(kind, var.mesh, "FDC.div")
+            if var.dim != 1 or edge or isinstance(A_coeffs.var_j, (Jac, Hess)):
+                raise NotImplementedError("pyapes_amd: FDC.div: limiter quick is for scalar fields with a float / Tensor / Field "
+                                          "speed and edge=False")
+        require_gpu(var(), "FDC.div")
         ctx = context_for(var.mesh)
         ctx.bind_bcs(var(), A_coeffs.bcs, 0)
         out = torch.empty((1, *var.mesh.nx), dtype=var().dtype, device=var().device)

@@ -18,7 +18,7 @@ from ..hip import lib as L
 from ..hip.context import context_for
 from ..mesh.tools import boundary_slicer
 from ..variables import Field
-from .fdc import _adv_of, div_kind
+from .fdc import _adv_of, div_kind, quick_explicit_only
 from .tools import FDMSolverConfig
 from .types import OPStype
 
@@ -50,6 +50,7 @@ def terms_of(eqs: dict[int, OPStype]) -> tuple[list[dict], list]:
         elif name == "div":
             var_j, cfg = op["param"]
             lim = cfg["div"]["limiter"].lower() if "limiter" in cfg["div"] else "none"
+            quick_explicit_only(div_kind(lim, bool(cfg["div"].get("compat", False))), "solver equation")
             terms.append({"kind": div_kind(lim, bool(cfg["div"].get("compat", False))), "sign": op["sign"],
                           "u": _adv_of(var_j, op["target"])})
         else:

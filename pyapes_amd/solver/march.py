@@ -23,7 +23,7 @@ from torch import Tensor
 from ..backend import require_gpu
 from ..hip.context import context_for
 from ..variables import Field
-from .fdc import _adv_of, div_kind
+from .fdc import _adv_of, div_kind, quick_mesh_check
 
 
 # (c0, c1) of every FUSED stage of a step, in order; the plain Euler stage phi1 = E(phi0) in front of them is implied.
@@ -78,12 +78,15 @@ def euler_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float,
     """Advance ``phi`` in place by one explicit Euler step; returns ``phi``."""
     if getattr(phi.mesh, "slab", None) is not None:
         cfg = (config or {}).get("div", {"limiter": "upwind"})
-        return _march_on_slabs(phi, u, nu, dt, 1, div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False))))
+        kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+        quick_mesh_check(kind, phi.mesh, "euler_step")
+        return _march_on_slabs(phi, u, nu, dt, 1, kind)
+    cfg = (config or {}).get("div", {"limiter": "upwind"})
+    kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+    quick_mesh_check(kind, phi.mesh, "euler_step")
     require_gpu(phi(), "euler_step")
     if phi.dim != 1:
         raise NotImplementedError("pyapes_amd: euler_step is for scalar fields")
-    cfg = (config or {}).get("div", {"limiter": "upwind"})
-    kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
     ctx = context_for(phi.mesh)
     ctx.bind_bcs(phi(), phi.bcs, 0)
     out = torch.empty_like(phi())
@@ -100,6 +103,7 @@ def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nst
         raise NotImplementedError("pyapes_amd: euler_march is for scalar fields")
     cfg = (config or {}).get("div", {"limiter": "upwind"})
     kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+    quick_mesh_check(kind, phi.mesh, "euler_march")
     self_adv = advects_itself(phi, u)
     if self_adv:
         _no_self_on_slabs(phi, "euler_march")
@@ -134,7 +138,9 @@ def _rk_args(phi: Field, config: dict | None, order: int, what: str) -> int:
     if getattr(phi.mesh, "slab", None) is not None:
         raise NotImplementedError(f"pyapes_amd: {what} on a slab mesh (the stages march on one GPU; euler_march does slabs)")
     cfg = (config or {}).get("div", {"limiter": "upwind"})
-    return div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+    kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+    quick_mesh_check(kind, phi.mesh, what)
+    return kind
 
 
 def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config: dict | None = None,

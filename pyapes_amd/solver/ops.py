@@ -5,6 +5,7 @@ import torch
 from torch import Tensor
 
 from ..variables import Field
+from .fdc import _limiter, div_kind, quick_explicit_only
 from .fdm import Operators
 from .linalg import ReportType, solve
 from .tools import SolverConfig
@@ -24,6 +25,9 @@ class Solver:
         """Take var / ops / rhs from the DSL object and add every operator's BC adjustment
         to the rhs IN PLACE -- the caller's tensor is modified, as in the reference
         (ops.py:61-77)."""
+        for op in eq.ops.values():   # Div limiter quick is explicit-only: refused before anything is taken over
+            if op["name"] == "Div":
+                quick_explicit_only(div_kind(*_limiter(op["param"][1]["div"])), "Solver.set_eq")
         self.var = eq.var
         self.eqs = eq.ops
         self.rhs = eq.rhs
