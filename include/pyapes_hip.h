@@ -104,7 +104,10 @@ int pa_ctx_set_option(pa_ctx* ctx, const char* name, int value);
  * sweeps in opposite directions; the iterates are the same bits, the stop-test sums are added in another order), "rhs_full" 1 = pa_rhs_adjust over the whole mesh, "res_cells" / "res_nt" /
  * "res_nt_cells" / "res_spin" / "res_rzlean" (box plan, threads per workgroup, spin bound, rz stencil of the resident
  * solver), "comm" / "slab_fold" (read back by the slab driver: library-side RCCL loop, folded sequence), "comm_overlap"
- * (-1 auto), "comm_timeout" (s), "roctx" (process-wide).  pa_ctx_get_option reads a value back. */
+ * (-1 auto), "comm_timeout" (s), "roctx" (process-wide), "chunks" N > 0 = at most N axis-0 chunks in k_sf / k_sfq / k_cg3d (a cap behind
+ * their rule, which on small meshes gives one plane per chunk; same bits in the single-field kernels, another grouping of
+ * the partial sums in the solver phases; tests/test_gpu_chunks.py), "sf" 2 / 4 = k_sf with that many rows per wave.
+ * pa_ctx_get_option reads a value back. */
 int pa_ctx_get_option(const pa_ctx* ctx, const char* name, int* value);
 /* Accounts of the online placement search of this ctx, out[10]: state (-1 off, 0 not begun / arrays too small,
  * 1 searching, 2 pass over), trials, trials kept, allocations made, microseconds the trials have cost (copies,

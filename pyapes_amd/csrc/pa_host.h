@@ -190,7 +190,8 @@ struct pa_ctx {
   // 3-D fast path switch (PYAPES_HIP_FASTPATH=0 disables; tests compare both)
   int fastpath = 1;
   int sfq = 1;                   // option "sfq": k_sfq for the QUICK Euler step / stage (0: the generic k_euler; 2 / 4: rows per wave forced); pa_sfq_kernel.h
-  int sf = 1;                    // k_sf for the Div-carrying single-field operations (else k_cg3d's phases)
+  int sf = 1;                    // option "sf": k_sf for the Div-carrying single-field operations (0: k_cg3d's phases; 2 / 4: rows per wave forced, pa_sf_kernel.h sf_rows_per_wave)
+  int chunks = 0;                // option "chunks": N > 0 caps the axis-0 chunk count of k_sf / k_sfq / k_cg3d behind their rule (0: the rule alone)
   int resident = 1;              // small meshes: the whole CG / Jacobi solve in one cooperative launch (pa_resident.hip)
   // 1: hipLaunchCooperativeKernel (the runtime guarantees co-residency).  0: a plain launch of the same grid, which
   // the occupancy query of pa_resident_launch has already shown to fit an idle device; the bounded waits make a

@@ -598,6 +598,7 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
+  if (c->chunks > 0 && chunks > c->chunks) chunks = c->chunks;   // option "chunks": a cap behind the rule (tests: chunks longer than one plane on small meshes)
   A.chunks = chunks;
   const int nblk = tiles * chunks;
   if (nblk > PA_MAX_PARTIALS) return 0;
@@ -624,6 +625,7 @@ static int sf_rows_per_wave(pa_ctx* c) {
   const DevGeom& G = c->G;
   if (G.n1 <= 4) return 1;
   if (G.n1 <= 8) return 2;
+  if (c->sf == 2 || c->sf == 4) return c->sf;   // option "sf" 2 / 4: forced (tests)
   const int64_t tiles4 = ((G.n1 + 15) / 16) * ((G.n2 + 64 * VEC - 1) / (64 * VEC));
   const int64_t chunks4 = std::max<int64_t>(1, (int64_t)cus_of(c) * 2 / tiles4);
   return G.n0 / chunks4 >= 32 ? 4 : 2;

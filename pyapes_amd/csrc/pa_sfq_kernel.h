@@ -355,6 +355,7 @@ static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
+  if (c->chunks > 0 && chunks > c->chunks) chunks = c->chunks;   // option "chunks": a cap behind the rule (tests: chunks longer than one plane on small meshes)
   A.chunks = chunks;
   const int nblk = tiles * chunks;
   if (nblk > PA_MAX_PARTIALS) return 0;

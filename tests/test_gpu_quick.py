@@ -49,7 +49,8 @@ CASES = [
     ("sfq_f32_two_ktiles", [9, 40, 264], "single", R.ALLDIR, 1.3, False, {}, "k_sfq"),
     ("sfq_f64_six_rows", [80, 6, 32], "double", R.MIXED, 1.0, False, {}, "k_sfq"),                 # halo rows wrap in the tile
     ("sfq_f64_five_rows", [16, 5, 32], "double", R.MIXED, -1.0, False, {}, "k_sfq"),
-    ("sfq_f64_short_chunks_upos", [6, 12, 32], "double", R.ALLDIR, 1.0, False, {}, "k_sfq"),       # chunks of 1-2 planes
+    ("sfq_f64_short_chunks_upos", [6, 12, 32], "double", R.ALLDIR, 1.0, False, {}, "k_sfq"),       # six planes: both axis-0 fallback pairs adjacent (chunks of ONE plane, like every
+                                                                                                   # case here: 256 CUs x 2 blocks >= tiles x n0; longer chunks: test_gpu_chunks.py)
     ("sfq_f64_short_chunks_uneg", [6, 12, 32], "double", R.ALLDIR, -1.0, False, {}, "k_sfq"),
     ("sfq_f64_yperiodic", [16, 20, 40], "double", R.YPER, -1.1, False, {}, "k_sfq"),               # (stage: + k_rk_combine)
     ("sfq_f32_kperiodic", [12, 16, 64], "single", R.DIRPER, 1.2, False, {}, "k_sfq"),
