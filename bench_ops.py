@@ -2,7 +2,8 @@
 """bench_ops.py -- secondary measurements for the other rows of SURVEY section 8 (not the driver's
 contract; bench.py is).  One JSON line per workload: explicit Laplacian apply, the explicit
 adv-diff Euler march (BASELINE config 4), the SSP Runge-Kutta march beside its unfused composition, the self-advected
-march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step composition, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step composition, the marches with a source term
+(--sections source) beside the three-launch workaround and the generic kernel, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -54,7 +55,10 @@ def main():
                          "fused stages against the composition of public pieces, then the self-advected march; self: those rows "
                          "alone; self_baselines: their two comparison rows alone, which need no self march in the library), "
                          "quick (the QUICK Euler step and order-3 march on k_sfq beside the generic kernel and beside upwind; not in "
-                         "the default list; quick_baseline: the upwind rows alone, which a library without QUICK can run), small (the reference's "
+                         "the default list; quick_baseline: the upwind rows alone, which a library without QUICK can run), source (euler_march "
+                         "and rk_march order 3 with a scalar source and a source field, beside no source, the euler_step + torch add + "
+                         "apply_bcs workaround and the generic kernel; not in the default list; source_baseline: the no-source rows alone, "
+                         "which a library without the source term can run), small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -104,6 +108,8 @@ def main():
         quick_rows(q, emit, with_quick="quick" in sections)
     if sections & {"rk", "self", "self_baselines"}:
         self_rows(q, emit, with_self=bool(sections & {"rk", "self"}))
+    if sections & {"source", "source_baseline"}:
+        source_rows(q, emit, with_source="source" in sections)
     solver_rows(q, emit, sections)
 
 
@@ -249,6 +255,76 @@ def quick_rows(q, emit, with_quick=True):
         for k, v in (("sfq", 1), ("bcl", 1)) if with_quick else (("bcl", 1),):
             ctx.set_option(k, v)
         del mesh, start, ut
+        torch.cuda.empty_cache()
+
+
+def source_rows(q, emit, with_source=True):
+    """The source term S of the marches (``source=``; the SRC instantiations of k_sf, csrc/pa_sf_kernel.h), upwind, config-4
+    BCs, fp32: euler_march and rk_march order 3 (20 steps per call, ms per STEP) without a source, with a scalar source, with
+    a source field, with a source field on the generic kernel ("fastpath": 0) and -- the Euler rows -- beside what a user
+    could do before: euler_step, a torch add of dt * S on the interior set, apply_bcs, per step.  The variants of a row are
+    timed in turn, three rounds; "ms" is the median, "ms_rounds" all three.  Algorithmic passes: Euler step 2, order-3 step
+    8, + 1 per launch with a source field."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.march import euler_march, euler_step, rk_march
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    bcs = mixed_bcs([0.0, 0.0, None, None, None, None],
+                    ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"])
+    cfg = {"div": {"limiter": "upwind"}}
+    nu, steps = 1e-3, 20
+    for n in ([128] if q else [256, 512]):
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", "single")
+        ctx = context_for(mesh)
+        start = torch.exp(-((mesh.X - 0.5) ** 2 + (mesh.Y - 0.5) ** 2 + (mesh.Z - 0.5) ** 2) / 0.02).unsqueeze(0).contiguous()
+        dx = mesh.dx_list[0]
+        dt = 0.2 * min(dx * dx / (6 * nu), dx / 1.0)
+        S = (torch.sin(3.0 * mesh.X) * torch.cos(2.0 * mesh.Y)).unsqueeze(0).contiguous()
+        dtS = (dt * S)[0][1:-1, 1:-1, 1:-1].contiguous()
+        reps = 3 if n <= 256 else 1
+
+        def workaround(phi):
+            for _ in range(steps):
+                euler_step(phi, 1.0, nu, dt, cfg)
+                phi()[0][1:-1, 1:-1, 1:-1] += dtS
+                phi.apply_bcs()
+
+        def euler(src):
+            return lambda phi: timed(lambda: euler_march(phi, 1.0, nu, dt, steps, cfg, **src), reps, warm=1) / steps
+
+        def rk3(src):
+            return lambda phi: timed(lambda: rk_march(phi, 1.0, nu, dt, steps, cfg, order=3, **src), reps, warm=1) / steps
+
+        for what, make, lanes, base_passes in ((f"euler_march ({steps} steps per call)", euler, 1, 2),
+                                               (f"rk_march order 3 ({steps} steps per call)", rk3, 3, 8)):
+            variants = [("no source", make({}), {"fastpath": 1}, base_passes)]
+            if with_source:   # (a library from before the source term has no entry point that takes one)
+                variants += [("scalar source", make({"source": 0.5}), {"fastpath": 1}, base_passes),
+                             ("source field", make({"source": S}), {"fastpath": 1}, base_passes + lanes),
+                             ("source field fastpath 0", make({"source": S}), {"fastpath": 0}, base_passes + lanes)]
+                if lanes == 1:
+                    variants.append(("workaround euler_step + torch interior add + apply_bcs",
+                                     lambda phi: timed(lambda: workaround(phi), reps, warm=1) / steps, {"fastpath": 1}, 5))
+            rounds = {v[0]: [] for v in variants}
+            for _ in range(3):
+                for vname, run, opts, _ in variants:
+                    for k, v in opts.items():
+                        ctx.set_option(k, v)
+                    phi = Field("phi", 1, mesh, {"domain": bcs, "obstacle": None})
+                    phi.set_var_tensor(start.clone())
+                    phi.apply_bcs()
+                    rounds[vname].append(run(phi))
+                    assert bool(torch.isfinite(phi()).all())
+                    del phi
+            base = sorted(rounds["no source"])[1]
+            for vname, _, opts, passes in variants:
+                ms = sorted(rounds[vname])[1]
+                emit(f"{what} {n}^3 f32 upwind scalar u, {vname} (config 4 BCs)", n ** 3, ms, passes, 4,
+                     {"ms_rounds": rounds[vname], "over_no_source": ms / base, "options": opts})
+        ctx.set_option("fastpath", 1)
+        del mesh, start, S, dtS
         torch.cuda.empty_cache()
 
 

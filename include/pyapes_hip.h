@@ -261,6 +261,36 @@ int pa_rk_march(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_k
 int pa_rk_march_self(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double nu, double dt,
                      int64_t nsteps, int* final);
 
+/* Source term S of the explicit steps:  d(phi)/dt = nu lap(phi) - div(u phi) + S.  On the interior set every operation is
+ * rounded on its own in the grid dtype, the Euler step's order with one more step:
+ *     a = nu * lap;  a = a - adv;  a = a + s;  a = dt * a;  v = phi + a
+ * s = field[cell] (a field of the grid's shape and dtype, read on the interior set only -- no stencil reach, no halo), or,
+ * field == NULL, `value` rounded to the grid dtype.  The BC fill follows as without a source; a Runge-Kutta stage stays
+ * B( c0*phi0 + c1*E_S(phi_s) ) with E_S in every stage.  S is FROZEN for the whole call: a forcing that depends on time is
+ * supplied anew per step (pa_rk_march_src with nsteps = 1).
+ * Every pa_*_src entry point is its sibling plus a trailing source: NULL or has == 0 IS the sibling -- the same kernel
+ * instantiations, the same bits (the siblings forward with NULL).  With a source:
+ *     PA_E_ARG    `field` is one of the call's buffers (input, output, w1, w2, phi0, u_field), or the mesh is axisymmetric
+ *     PA_E_STATE  slab mode
+ * and the context stays usable after either.  Kernels: the vector kernels k_sf (upwind, central) and k_sfq (QUICK, two rows
+ * per wave) have SRC instantiations; everything else -- 1-D / 2-D meshes, odd row lengths, unaligned operands, the literal
+ * upwind form, central Div with a foreign speed field -- runs the generic kernel (k_cg3d's Euler phase takes no source). */
+typedef struct {
+  int32_t has;        /* 0: no source (value and field are not read) */
+  double value;       /* the scalar source, used when field == NULL */
+  const void* field;  /* per-cell source or NULL */
+} pa_source;
+int pa_euler_step_src(pa_ctx* ctx, const void* phi_in, void* phi_out, int div_kind, double u, const void* u_field,
+                      double nu, double dt, const pa_source* src);
+int pa_euler_march_src(pa_ctx* ctx, void* phi, void* tmp, int div_kind, double u, const void* u_field, double nu,
+                       double dt, int64_t nsteps, const pa_source* src);
+int pa_rk_stage_src(pa_ctx* ctx, const void* phi, const void* phi0, void* out, double c0, double c1, int div_kind,
+                    double u, const void* u_field, double nu, double dt, const pa_source* src);
+int pa_rk_march_src(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double u, const void* u_field,
+                    double nu, double dt, int64_t nsteps, int* final, const pa_source* src);
+int pa_rk_march_self_src(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double nu, double dt,
+                         int64_t nsteps, int* final, const pa_source* src);
+
 /* ---- vector steps for a host-stepped solver loop (pyapes_amd/solver/host_stepped.py: BC callables that read the iterate
  * make the reference's loop come back to Python for every face of every fill, bcs.py:200-253; the loop's AXPYs and dot
  * products between those fills are these).  Fields of the grid's shape and dtype.

@@ -97,6 +97,10 @@ struct Cg3dArgs {
   // (last in the struct: the offsets the other instantiations read their arguments at stay what they were)
   const T* stg_phi0;
   T stg_c0, stg_c1;
+  // source term of the Euler step (the SRC instantiations of k_sf / k_sfq): a = nu lap - adv; a = a + s; a = dt a, with
+  // s = src[cell], or the splat of src_val when src is null (behind the stage's members for the same reason)
+  const T* src;
+  T src_val;
 };
 
 __device__ __forceinline__ int pa_xcd_remap(int b, int nb) {

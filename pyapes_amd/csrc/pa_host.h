@@ -302,12 +302,13 @@ int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd);
 // the QUICK Euler step / stage on k_sfq (pa_sfq.hip): blocks launched, 0 when k_sfq does not take the launch
 template <typename T>
 int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, double nu, double dt, const T* phi0 = nullptr,
-                 double c0 = 0.0, double c1 = 0.0);
+                 double c0 = 0.0, double c1 = 0.0, const pa_source* src = nullptr);   // src: the source term (pa_*_src) or null
 // u_field == phi.p: the field advects itself -- k_sf's SELF instantiations (pa_sf_self.hip), central Div included
 template <typename T>
 int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt,
                     int bcl = 0,    // bcl: "BC on load" (pa_sf_kernel.h); 0 is returned when that form does not apply
-                    const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0);   // phi0: the stage c0 phi0 + c1 E(phi) of pa_rk_stage
+                    const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0,    // phi0: the stage c0 phi0 + c1 E(phi) of pa_rk_stage
+                    const pa_source* src = nullptr);   // src: the source term (pa_*_src) or null; k_sf's SRC instantiations or 0
 template <typename T>
 int pa_tile3d_jacobi(pa_ctx* c, const DevEq<T>& E, Vec<T> x, const T* rhs, T* xnew, double omega, double* partials);
 template <typename T>

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <new>
 
 // ---- y = A(x) (pyapes/solver/ops.py:122-154) -----------------------------------------
@@ -239,9 +240,14 @@ __global__ void __launch_bounds__(PA_BLOCK) k_rhs_adjust(DevGeom G, DevEq<T> E, 
 // c0 * phi0 + c1 * v, the two products and the sum rounded one by one; phi0 is read at the cell.
 template <typename T, bool STG> struct EulerStage {};
 template <typename T> struct EulerStage<T, true> { const T* phi0; T c0, c1; };
-template <typename T, bool STG = false>
+// SRC: the source term (pa_*_src) -- a = nu lap - adv; a = a + s; a = dt a, with s read at the cell on the interior set, or
+// the scalar source; the instantiations without it are the code they were
+template <typename T, bool SRC> struct EulerSrc {};
+template <typename T> struct EulerSrc<T, true> { const T* f; T val; };
+template <typename T, bool STG = false, bool SRC = false>
 __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, DevEq<T> Eadv, Vec<T> pv,
-                                                     T* __restrict__ out, T nu, T dt, EulerStage<T, STG> S = {}) {
+                                                     T* __restrict__ out, T nu, T dt, EulerStage<T, STG> S = {},
+                                                     EulerSrc<T, SRC> Q = {}) {
   FieldAcc<T> acc{pv};
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < G.ncell;
        idx += (int64_t)gridDim.x * blockDim.x) {
@@ -254,6 +260,10 @@ __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, De
       T adv = pa_apply_terms<T>(G, Eadv, acc, i, j, k, pc);
       T a = nu * lap;
       a = a - adv;
+      if constexpr (SRC) {
+        const T s = Q.f ? Q.f[idx] : Q.val;
+        a = a + s;
+      }
       a = dt * a;
       v = pc + a;
     }
@@ -430,7 +440,7 @@ static int check_div_kind(pa_ctx* c, int kind, const char* who = "pa_div") {
 // phi0 != null: the Runge-Kutta stage out = B( c0 phi0 + c1 E(in) ) (pa_rk_stage), on the path the Euler step takes
 template <typename T>
 static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const void* u_field, double nu, double dt,
-                   const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0) {
+                   const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0, const pa_source* src = nullptr) {
   if (phi0) {
     // A stage combines the Euler STEP, BC fill included.  For dirichlet / neumann / symmetry faces the fill rewrites its
     // nodes from interior-set values alone, so filling once, after the combination, gives the same bits and the stage is
@@ -441,7 +451,7 @@ static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const voi
     bool periodic = false;
     for (int f = 0; f < 6; ++f) periodic = periodic || (c->G.act[f >> 1] && c->bc[f].type == PA_BC_PERIODIC);
     if (periodic) {
-      if (int rc = euler_t<T>(c, in, out, kind, u, u_field, nu, dt)) return rc;
+      if (int rc = euler_t<T>(c, in, out, kind, u, u_field, nu, dt, nullptr, 0.0, 0.0, src)) return rc;   // the source enters in the step only
       static int dbg = -1;
       if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
       if (dbg > 0) { --dbg; fprintf(stderr, "[pyapes_hip] k_rk_combine (RK stage, periodic face): Euler step, then %lld cells in place\n", (long long)c->G.ncell); }
@@ -471,10 +481,22 @@ static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const voi
   }
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);   // slot 0: the step kernel (without its BC fill)
   // QUICK: k_sfq or the generic kernel (the tiled paths of pa_tile3d_euler do not know the kind and decline it)
-  int fr = kind == PA_OP_DIV_QUICK ? pa_sfq_euler<T>(c, pv, out, u, u_field, nu, dt, phi0, c0, c1)
-                                   : pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 0, phi0, c0, c1);
+  // a source: the SRC instantiations of k_sf / k_sfq or the generic kernel (k_cg3d's Euler phase takes none)
+  int fr = kind == PA_OP_DIV_QUICK ? pa_sfq_euler<T>(c, pv, out, u, u_field, nu, dt, phi0, c0, c1, src)
+                                   : pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 0, phi0, c0, c1, src);
   if (fr < 0) return fr;
-  if (fr == 0 && phi0) {
+  if (fr == 0 && src) {
+    static int dbg = -1;   // (one budget for every mesh and both forms: larger than an instantiation's 8)
+    if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 64 : 0;
+    if (dbg > 0) { --dbg; fprintf(stderr, "[pyapes_hip] k_euler%s (source): generic kernel, %lld cells\n", phi0 ? " (RK stage)" : "", (long long)c->G.ncell); }
+    const EulerSrc<T, true> Q{(const T*)src->field, (T)src->value};
+    if (phi0)
+      hipLaunchKernelGGL((k_euler<T, true, true>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G, El, Ea,
+                         pv, out, (T)nu, (T)dt, EulerStage<T, true>{phi0, (T)c0, (T)c1}, Q);
+    else
+      hipLaunchKernelGGL((k_euler<T, false, true>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G, El, Ea,
+                         pv, out, (T)nu, (T)dt, EulerStage<T, false>{}, Q);
+  } else if (fr == 0 && phi0) {
     static int dbg = -1;
     if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
     if (dbg > 0) { --dbg; fprintf(stderr, "[pyapes_hip] k_euler (RK stage): generic kernel, %lld cells\n", (long long)c->G.ncell); }
@@ -495,10 +517,10 @@ static int euler_t(pa_ctx* c, const T* in, T* out, int kind, double u, const voi
 // boundary nodes of `out` stay whatever they were.  1: launched; 0: the form does not apply here; < 0: error.
 template <typename T>
 static int euler_bcl_t(pa_ctx* c, const T* in, T* out, int kind, double u, const void* u_field, double nu, double dt,
-                       const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0) {
+                       const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0, const pa_source* src = nullptr) {
   Vec<T> pv = pa_vec_self<T>(c, in);
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
-  const int fr = pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 1, phi0, c0, c1);
+  const int fr = pa_tile3d_euler<T>(c, pv, out, kind, u, u_field, nu, dt, 1, phi0, c0, c1, src);
   if (fr <= 0) return fr;
   if (c->profile) pa_profile_stop(c, 0);
   return 1;
@@ -556,7 +578,8 @@ __global__ void __launch_bounds__(PA_BLOCK) k_vec_dot_final(const double* __rest
 // (QUICK marches with a BC fill per step or stage: kind == PA_OP_DIV_UPWIND below)
 // "BC on load" (pa_sf_kernel.h): when every face has a scalar dirichlet / neumann / symmetry BC the steps of a
 // march need no fill between them -- each forms the face values it reads from its own operands, bit for bit what
-// the fill would have stored -- and ONE ordered fill after the last step completes the result.
+// the fill would have stored -- and ONE ordered fill after the last step completes the result.  (A source term is read on
+// the interior set only: it changes nothing here.)
 static bool march_bcl_wanted(const pa_ctx* c, int kind, int64_t nsteps) {
   bool bcl = c->bcl && c->sf && !c->slab && c->ndim == 3 && kind == PA_OP_DIV_UPWIND && nsteps >= 2 &&
              c->G.n0 >= 5 && c->G.n1 >= 5 && c->G.n2 >= 5;
@@ -571,22 +594,22 @@ static bool march_bcl_wanted(const pa_ctx* c, int kind, int64_t nsteps) {
 // the same bits, since the face values a BC-on-load launch forms are the ones the fill stores.
 template <typename T>
 static int rk_launch_t(pa_ctx* c, bool* bcl, int64_t nlaunch, T* in, T* out, const T* phi0, double c0, double c1, int kind,
-                       double u, const void* u_field, double nu, double dt) {
+                       double u, const void* u_field, double nu, double dt, const pa_source* src) {
   if (*bcl) {
-    const int fr = euler_bcl_t<T>(c, in, out, kind, u, u_field, nu, dt, phi0, c0, c1);
+    const int fr = euler_bcl_t<T>(c, in, out, kind, u, u_field, nu, dt, phi0, c0, c1, src);
     if (fr != 0) return fr < 0 ? fr : PA_OK;
     *bcl = false;
     if (nlaunch > 0) {
       if (int rc = pa_bc_apply_auto<T>(c, in, false)) return rc;
     }
   }
-  return euler_t<T>(c, in, out, kind, u, u_field, nu, dt, phi0, c0, c1);
+  return euler_t<T>(c, in, out, kind, u, u_field, nu, dt, phi0, c0, c1, src);
 }
 
 // self: the field advects itself -- every launch takes its own input buffer as the speed field (pa_rk_march_self)
 template <typename T>
 static int rk_march_t(pa_ctx* c, T* b0, T* b1, T* b2, int order, int kind, double u, const void* u_field, double nu,
-                      double dt, int64_t nsteps, int* final, bool self = false) {
+                      double dt, int64_t nsteps, int* final, bool self, const pa_source* src) {
   // the fused stages of a step in Shu-Osher form, after its plain Euler stage: (c0, c1) of c0 phi0 + c1 E(phi_s)
   const double st2[1][2] = {{0.5, 0.5}};
   const double st3[2][2] = {{3.0 / 4.0, 1.0 / 4.0}, {1.0 / 3.0, 2.0 / 3.0}};
@@ -596,12 +619,12 @@ static int rk_march_t(pa_ctx* c, T* b0, T* b1, T* b2, int order, int kind, doubl
   bool bcl = march_bcl_wanted(c, kind, nsteps);
   int64_t nl = 0;
   for (int64_t s = 0; s < nsteps; ++s) {
-    int rc = rk_launch_t<T>(c, &bcl, nl++, buf[base], buf[wa], nullptr, 0.0, 0.0, kind, u, self ? buf[base] : u_field, nu, dt);
+    int rc = rk_launch_t<T>(c, &bcl, nl++, buf[base], buf[wa], nullptr, 0.0, 0.0, kind, u, self ? buf[base] : u_field, nu, dt, src);
     if (rc) return rc;
     int cur = wa, free_ = wb;
     for (int q = 0; q < order - 1; ++q) {
       rc = rk_launch_t<T>(c, &bcl, nl++, buf[cur], buf[free_], buf[base], st[q][0], st[q][1], kind, u, self ? buf[cur] : u_field, nu,
-                          dt);
+                          dt, src);
       if (rc) return rc;
       std::swap(cur, free_);
     }
@@ -731,20 +754,45 @@ int pa_div_edge(pa_ctx* c, double u, const void* u_field, const void* x, void* y
   return PA_OK;
 }
 
-int pa_euler_step(pa_ctx* c, const void* in, void* out, int kind, double u, const void* u_field, double nu,
-                  double dt) {
+// The source of a pa_*_src call.  NULL or has == 0: *src becomes null and the call is its sibling.  Else slab mode
+// (PA_E_STATE), an axisymmetric mesh and a field that overlaps one of the call's buffers (PA_E_ARG) are refused before
+// anything is enqueued.
+static int check_source(pa_ctx* c, const pa_source** src, const char* who, std::initializer_list<const void*> bufs) {
+  if (!*src || !(*src)->has) { *src = nullptr; return PA_OK; }
+  if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "%s: a source term is single GPU only (no slabs)", who); return PA_E_STATE; }
+  if (c->coord != PA_COORD_XYZ) { pa_set_err(c, "%s: a source term is for xyz meshes (no axisymmetric rows)", who); return PA_E_ARG; }
+  const char* f = (const char*)(*src)->field;
+  if (!f) return PA_OK;
+  const size_t bytes = (size_t)c->G.ncell * (c->dtype == PA_F64 ? 8 : 4);
+  for (const void* b : bufs)
+    if (b && f < (const char*)b + bytes && (const char*)b < f + bytes) {
+      pa_set_err(c, "%s: the source field must not be one of the call's buffers", who);
+      return PA_E_ARG;
+    }
+  return PA_OK;
+}
+
+int pa_euler_step_src(pa_ctx* c, const void* in, void* out, int kind, double u, const void* u_field, double nu, double dt,
+                      const pa_source* src) {
   if (!c || !c->grid_set) return PA_E_STATE;
   int rc = check_div_kind(c, kind, "pa_euler_step");
   if (rc) return rc;
   if (in == out) { pa_set_err(c, "pa_euler_step: in-place step is not allowed"); return PA_E_ARG; }
+  if ((rc = check_source(c, &src, "pa_euler_step_src", {in, out, u_field}))) return rc;
   PA_HIP(c, hipSetDevice(c->device));
-  return c->dtype == PA_F64 ? euler_t<double>(c, (const double*)in, (double*)out, kind, u, u_field, nu, dt)
-                            : euler_t<float>(c, (const float*)in, (float*)out, kind, u, u_field, nu, dt);
+  return c->dtype == PA_F64
+             ? euler_t<double>(c, (const double*)in, (double*)out, kind, u, u_field, nu, dt, nullptr, 0.0, 0.0, src)
+             : euler_t<float>(c, (const float*)in, (float*)out, kind, u, u_field, nu, dt, nullptr, 0.0, 0.0, src);
+}
+
+int pa_euler_step(pa_ctx* c, const void* in, void* out, int kind, double u, const void* u_field, double nu,
+                  double dt) {
+  return pa_euler_step_src(c, in, out, kind, u, u_field, nu, dt, nullptr);
 }
 
 // self: every step takes its own input buffer as the speed field (order 1 of pa_rk_march_self)
 static int euler_march_impl(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field_, double nu, double dt,
-                            int64_t nsteps, bool self) {
+                            int64_t nsteps, bool self, const pa_source* src) {
   int rc;
   PaRange range_("pyapes explicit Euler march");
   PA_HIP(c, hipSetDevice(c->device));
@@ -754,16 +802,16 @@ static int euler_march_impl(pa_ctx* c, void* phi, void* tmp, int kind, double u,
     const void* u_field = self ? buf[s & 1] : u_field_;
     if (bcl) {
       const int fr = c->dtype == PA_F64
-                         ? euler_bcl_t<double>(c, (const double*)buf[s & 1], (double*)buf[(s + 1) & 1], kind, u, u_field, nu, dt)
-                         : euler_bcl_t<float>(c, (const float*)buf[s & 1], (float*)buf[(s + 1) & 1], kind, u, u_field, nu, dt);
+                         ? euler_bcl_t<double>(c, (const double*)buf[s & 1], (double*)buf[(s + 1) & 1], kind, u, u_field, nu, dt, nullptr, 0.0, 0.0, src)
+                         : euler_bcl_t<float>(c, (const float*)buf[s & 1], (float*)buf[(s + 1) & 1], kind, u, u_field, nu, dt, nullptr, 0.0, 0.0, src);
       if (fr < 0) return fr;
       if (fr > 0) continue;
       if (s > 0) { pa_set_err(c, "pa_euler_march: the BC-on-load step declined in the middle of a march"); return PA_E_STATE; }
       bcl = false;   // not for k_sf (row length, alignment ...): the classic sequence from the first step on
     }
     rc = c->dtype == PA_F64
-             ? euler_t<double>(c, (const double*)buf[s & 1], (double*)buf[(s + 1) & 1], kind, u, u_field, nu, dt)
-             : euler_t<float>(c, (const float*)buf[s & 1], (float*)buf[(s + 1) & 1], kind, u, u_field, nu, dt);
+             ? euler_t<double>(c, (const double*)buf[s & 1], (double*)buf[(s + 1) & 1], kind, u, u_field, nu, dt, nullptr, 0.0, 0.0, src)
+             : euler_t<float>(c, (const float*)buf[s & 1], (float*)buf[(s + 1) & 1], kind, u, u_field, nu, dt, nullptr, 0.0, 0.0, src);
     if (rc) return rc;
   }
   if (bcl && nsteps > 0) {
@@ -774,17 +822,23 @@ static int euler_march_impl(pa_ctx* c, void* phi, void* tmp, int kind, double u,
   return PA_OK;
 }
 
-int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field, double nu, double dt,
-                   int64_t nsteps) {
+int pa_euler_march_src(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field, double nu, double dt,
+                       int64_t nsteps, const pa_source* src) {
   if (!c || !c->grid_set) return PA_E_STATE;
   int rc = check_div_kind(c, kind, "pa_euler_march");
   if (rc) return rc;
   if (phi == tmp || nsteps < 0) { pa_set_err(c, "pa_euler_march: bad buffers / step count"); return PA_E_ARG; }
-  return euler_march_impl(c, phi, tmp, kind, u, u_field, nu, dt, nsteps, false);
+  if ((rc = check_source(c, &src, "pa_euler_march_src", {phi, tmp, u_field}))) return rc;
+  return euler_march_impl(c, phi, tmp, kind, u, u_field, nu, dt, nsteps, false, src);
 }
 
-int pa_rk_stage(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind, double u,
-                const void* u_field, double nu, double dt) {
+int pa_euler_march(pa_ctx* c, void* phi, void* tmp, int kind, double u, const void* u_field, double nu, double dt,
+                   int64_t nsteps) {
+  return pa_euler_march_src(c, phi, tmp, kind, u, u_field, nu, dt, nsteps, nullptr);
+}
+
+int pa_rk_stage_src(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind, double u,
+                    const void* u_field, double nu, double dt, const pa_source* src) {
   if (!c || !c->grid_set) return PA_E_STATE;
   int rc = check_div_kind(c, kind, "pa_rk_stage");
   if (rc) return rc;
@@ -793,14 +847,20 @@ int pa_rk_stage(pa_ctx* c, const void* phi, const void* phi0, void* out, double 
     return PA_E_ARG;
   }
   if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "pa_rk_stage: single GPU only (no slab stages)"); return PA_E_STATE; }
+  if ((rc = check_source(c, &src, "pa_rk_stage_src", {phi, phi0, out, u_field}))) return rc;
   PA_HIP(c, hipSetDevice(c->device));
   return c->dtype == PA_F64
-             ? euler_t<double>(c, (const double*)phi, (double*)out, kind, u, u_field, nu, dt, (const double*)phi0, c0, c1)
-             : euler_t<float>(c, (const float*)phi, (float*)out, kind, u, u_field, nu, dt, (const float*)phi0, c0, c1);
+             ? euler_t<double>(c, (const double*)phi, (double*)out, kind, u, u_field, nu, dt, (const double*)phi0, c0, c1, src)
+             : euler_t<float>(c, (const float*)phi, (float*)out, kind, u, u_field, nu, dt, (const float*)phi0, c0, c1, src);
 }
 
-int pa_rk_march(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double u, const void* u_field, double nu,
-                double dt, int64_t nsteps, int* final) {
+int pa_rk_stage(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind, double u,
+                const void* u_field, double nu, double dt) {
+  return pa_rk_stage_src(c, phi, phi0, out, c0, c1, kind, u, u_field, nu, dt, nullptr);
+}
+
+int pa_rk_march_src(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double u, const void* u_field, double nu,
+                    double dt, int64_t nsteps, int* final, const pa_source* src) {
   if (!c || !c->grid_set) return PA_E_STATE;
   if (order < 1 || order > 3) { pa_set_err(c, "pa_rk_march: order %d (1, 2 or 3)", order); return PA_E_ARG; }
   int rc = check_div_kind(c, kind, "pa_rk_march");
@@ -810,20 +870,26 @@ int pa_rk_march(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, d
     return PA_E_ARG;
   }
   if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "pa_rk_march: single GPU only (no slab stages)"); return PA_E_STATE; }
+  if ((rc = check_source(c, &src, "pa_rk_march_src", {phi, w1, w2, u_field}))) return rc;
   if (order == 1) {   // plain Euler: the march as it is
-    rc = pa_euler_march(c, phi, w1, kind, u, u_field, nu, dt, nsteps);
+    rc = pa_euler_march_src(c, phi, w1, kind, u, u_field, nu, dt, nsteps, src);
     if (!rc) *final = (int)(nsteps & 1);
     return rc;
   }
   PaRange range_("pyapes SSP Runge-Kutta march");
   PA_HIP(c, hipSetDevice(c->device));
   return c->dtype == PA_F64
-             ? rk_march_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, u, u_field, nu, dt, nsteps, final)
-             : rk_march_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, u, u_field, nu, dt, nsteps, final);
+             ? rk_march_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, u, u_field, nu, dt, nsteps, final, false, src)
+             : rk_march_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, u, u_field, nu, dt, nsteps, final, false, src);
 }
 
-int pa_rk_march_self(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double nu, double dt, int64_t nsteps,
-                     int* final) {
+int pa_rk_march(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double u, const void* u_field, double nu,
+                double dt, int64_t nsteps, int* final) {
+  return pa_rk_march_src(c, phi, w1, w2, order, kind, u, u_field, nu, dt, nsteps, final, nullptr);
+}
+
+int pa_rk_march_self_src(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double nu, double dt, int64_t nsteps,
+                         int* final, const pa_source* src) {
   if (!c || !c->grid_set) return PA_E_STATE;
   if (order < 1 || order > 3) { pa_set_err(c, "pa_rk_march_self: order %d (1, 2 or 3)", order); return PA_E_ARG; }
   int rc = check_div_kind(c, kind, "pa_rk_march_self");
@@ -834,16 +900,22 @@ int pa_rk_march_self(pa_ctx* c, void* phi, void* w1, void* w2, int order, int ki
     return PA_E_ARG;
   }
   if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "pa_rk_march_self: single GPU only (no slab stages)"); return PA_E_STATE; }
+  if ((rc = check_source(c, &src, "pa_rk_march_self_src", {phi, w1, order > 1 ? w2 : nullptr}))) return rc;
   if (order == 1) {   // plain Euler, the speed ping-pongs with the field
-    rc = euler_march_impl(c, phi, w1, kind, 0.0, nullptr, nu, dt, nsteps, true);
+    rc = euler_march_impl(c, phi, w1, kind, 0.0, nullptr, nu, dt, nsteps, true, src);
     if (!rc) *final = (int)(nsteps & 1);
     return rc;
   }
   PaRange range_("pyapes SSP Runge-Kutta march, self-advected");
   PA_HIP(c, hipSetDevice(c->device));
   return c->dtype == PA_F64
-             ? rk_march_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, 0.0, nullptr, nu, dt, nsteps, final, true)
-             : rk_march_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, 0.0, nullptr, nu, dt, nsteps, final, true);
+             ? rk_march_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, 0.0, nullptr, nu, dt, nsteps, final, true, src)
+             : rk_march_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, 0.0, nullptr, nu, dt, nsteps, final, true, src);
+}
+
+int pa_rk_march_self(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double nu, double dt, int64_t nsteps,
+                     int* final) {
+  return pa_rk_march_self_src(c, phi, w1, w2, order, kind, nu, dt, nsteps, final, nullptr);
 }
 
 }  // extern "C"

@@ -4,19 +4,21 @@
 // vectors; the Laplacian alone and the gradient stay on k_cg3d's phases 2 / 7 (pa_cg3d_kernel.h), which move
 // their 2 / 4 passes at the speed of a device copy, as does everything k_sf does not take (odd row lengths,
 // unaligned operands, tensor coefficient, 2-D meshes).  The Euler step of a field that advects itself (u_field == phi) has
-// k_sf instantiations of its own, SELF, in pa_sf_self.hip.
+// k_sf instantiations of its own, SELF, in pa_sf_self.hip; the step with a source term (SRC) in pa_sf_src.hip and
+// pa_sf_src_bcl.hip.
 #include "pa_sf_kernel.h"
 
 template <typename T>
 int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt, int bcl,
-                    const T* phi0, double c0, double c1) {
+                    const T* phi0, double c0, double c1, const pa_source* src) {
   DevEq<T> E;
   pa_term t;
   memset(&t, 0, sizeof(t));
   t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
   pa_build_eq<T>(c, 1, &t, E);
-  const int mode = cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0});   // (a stage's phi0 counts for the alignment)
+  const int mode = cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0, src ? src->field : nullptr});   // (a stage's phi0 and a source field count for the alignment)
   if (!mode) return 0;
+  if (src && kind == PA_OP_DIV_UPWIND_COMPAT) return 0;   // no SRC instantiation of the literal form: generic kernel
   // the field advects itself: the speed at the cell and at its neighbours are the stencil's own operands (k_sf SELF)
   const bool self = u_field && u_field == (const void*)phi.p;
   if (kind == PA_OP_DIV_CENTRAL && u_field && !self) return 0;  // needs a foreign u at the neighbours: generic kernel
@@ -26,12 +28,14 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
   fill_h<T>(c, A);
   A.d = phi; A.out = out; A.aux = (const T*)u_field; A.u = (T)u; A.p0 = (T)nu; A.p1 = (T)dt; A.kind = kind;
   A.stg_phi0 = phi0; A.stg_c0 = (T)c0; A.stg_c1 = (T)c1;   // phi0 != null: the Runge-Kutta stage (STG instantiations)
+  if (src) { A.src = (const T*)src->field; A.src_val = (T)src->value; }   // the SRC instantiations of k_sf
   {  // the BC fill that follows the step kernel (euler_t) rewrites every face plane that has a BC
     int faces = 0;
     for (int f = 0; f < 6; ++f) faces += (c->G.act[f >> 1] && c->bc[f].type != PA_BC_NONE) ? 1 : 0;
     A.out_all = faces == 2 * c->ndim ? 1 : 0;
   }
   const bool sf = sf_applies<T, 3>(c, A, mode);
+  if (src && !sf) return 0;   // k_cg3d's Euler phase takes no source: the generic kernel does
   // central self off k_sf: k_cg3d reads the speed at the cell only.  On a slab the generic kernel takes u's axis-0
   // neighbours from the rank's own planes, k_sf would take the ghost planes: the generic kernel keeps its bits
   if (kind == PA_OP_DIV_CENTRAL && self && (!sf || c->G.n0 != c->G.g0)) return 0;
@@ -56,6 +60,14 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
   auto launch = [&](auto STGC) -> int {
     constexpr bool STG = decltype(STGC)::value;
     if (!sf) return launch_any<T, 3, STG>(c, A, mode);
+    if (src) {
+      if (bcl) {   // the condition of launch_sf_any: rows n1 - 2, n1 - 1 in one wave's block
+        const int rj = sf_rows_per_wave<T>(c);
+        if (rj < 2 || (c->G.n1 - 1) % rj == 0) return 0;
+        return pa_sf_euler_src_bcl<T>(c, A, rj, STG, self);
+      }
+      return pa_sf_euler_src<T>(c, A, kind, STG, self);
+    }
     if (self) return pa_sf_euler_self<T>(c, A, kind, STG);
     switch (kind) {
       case PA_OP_DIV_CENTRAL: return launch_sf_any<T, 3, PA_OP_DIV_CENTRAL, STG>(c, A);
@@ -116,8 +128,8 @@ int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd) {
   return n;
 }
 
-template int pa_tile3d_euler<float>(pa_ctx*, Vec<float>, float*, int, double, const void*, double, double, int, const float*, double, double);
-template int pa_tile3d_euler<double>(pa_ctx*, Vec<double>, double*, int, double, const void*, double, double, int, const double*, double, double);
+template int pa_tile3d_euler<float>(pa_ctx*, Vec<float>, float*, int, double, const void*, double, double, int, const float*, double, double, const pa_source*);
+template int pa_tile3d_euler<double>(pa_ctx*, Vec<double>, double*, int, double, const void*, double, double, int, const double*, double, double, const pa_source*);
 template int pa_tile3d_grad<float>(pa_ctx*, Vec<float>, float*, int);
 template int pa_tile3d_grad<double>(pa_ctx*, Vec<double>, double*, int);
 template int pa_tile3d_aop<float>(pa_ctx*, const DevEq<float>&, Vec<float>, float*, int);

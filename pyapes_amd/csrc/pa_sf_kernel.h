@@ -105,14 +105,20 @@ template <> struct SfBits<double> {
 // come from the DPP moves, the edge cells He and the rows Hu / Hd like every other neighbour.  Operation for operation what
 // HASU (upwind) and the generic k_euler (central) compute with u_field a copy of the field: the same bits
 // (tests/test_gpu_self_march.py).  With BCL the centre of an interior node is an interior node: its value is genuine.
+// SRC: the source term of the Euler step, d(phi)/dt = nu lap - div + S.  One more operand read at the cell -- a 16-byte lane
+// access per row and plane through A.src, issued beside phi0's -- and one more rounded operation, a = a + s, between
+// nu lap - adv and the product with dt.  A.src == nullptr is a scalar source: the splat of A.src_val (wave-uniform select;
+// the load then reads the field's own rows and is dropped, so that no branch sits between a load and its use).  RJ * VEC
+// more live registers for one plane.  The SRC = false instantiations are the code they were.
 #ifndef PA_SF_USIGN
 #define PA_SF_USIGN 1
 #endif
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false>
 __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
   static_assert(!SELF || (PHASE == 3 && !HASU && US == 0), "SELF: the Euler step, no other speed");
   static_assert(!BCL || PHASE == 3, "BC on load: the Euler step");
   static_assert(!STG || PHASE == 3, "STG: the Euler step");
+  static_assert(!SRC || (PHASE == 3 && KIND != 3), "SRC: the Euler step, not the literal upwind form");
   static_assert(US == 0 || (KIND == 4 && !HASU), "US: scalar speed of the upwind scheme");
   constexpr int VEC = VecOf<T>::N;
   typedef T V __attribute__((ext_vector_type(VEC)));
@@ -305,6 +311,13 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
       gcptr pz = (gcptr)((uintptr_t)A.stg_phi0 + (size_t)(unsigned)ii * pstride);
 #pragma unroll
       for (int jj = 0; jj < RJ; ++jj) Z[jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(pz + off[jj]);
+    }
+    V Sv[SRC ? RJ : 1];   // SRC: the source of THIS plane, issued where phi0's rows are and for the same reason
+    if constexpr (SRC) {
+      // unconditional, like every load here: a scalar source reads the field's own rows (cache hits) and drops them below
+      gcptr ps = (gcptr)((uintptr_t)(A.src ? A.src : A.d.p) + (size_t)(unsigned)ii * pstride);
+#pragma unroll
+      for (int jj = 0; jj < RJ; ++jj) Sv[jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(ps + off[jj]);
     }
     // loads for later planes first: they fly during this plane's arithmetic
     load_own(std::integral_constant<int, SL>{}, ii + 2 <= i1 ? ii + 2 : i1);          // plane q + 2 (<= the one behind the chunk)
@@ -544,6 +557,13 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
         if constexpr (PHASE == 3) {
           V qv = A.p0 * axv;
           qv = qv - adv;
+          if constexpr (SRC) {   // a = a + s, between nu lap - adv and the product with dt
+            const bool hasF = A.src != nullptr;   // wave-uniform: a source field, else the splat of src_val
+            V sv;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) sv[v] = hasF ? Sv[jj][v] : A.src_val;
+            qv = qv + sv;
+          }
           qv = A.p1 * qv;
           res = xc + qv;
           if constexpr (STG) {
@@ -575,18 +595,18 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false>
 static int sf_blocks_per_cu() {
   static int cached = 0;
   if (!cached) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>, 256, 0) != hipSuccess || n <= 0) n = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>, 256, 0) != hipSuccess || n <= 0) n = 4;
     cached = n;
   }
   return cached;
 }
 
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false>
 static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr int VEC = VecOf<T>::N;
   constexpr int TJ = 4 * RJ, TK = 64 * VEC;
@@ -594,7 +614,7 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
   A.tiles_k = (int)((G.n2 + TK - 1) / TK);
   const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>();
+  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>();
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
@@ -606,11 +626,11 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
   if (dbg > 0) {
     --dbg;
-    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
-            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>());
+    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
+            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", SRC ? " (source)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
+            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>());
   }
-  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF>), dim3(nblk), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>), dim3(nblk), dim3(256), 0, c->stream, A);
   return nblk;
 }
 
@@ -698,6 +718,13 @@ static int launch_sf_self(pa_ctx* c, Cg3dArgs<T>& A) {
 // blocks launched, or 0 when k_sf does not take the launch (A as pa_tile3d_euler fills it; aux is not read)
 template <typename T>
 int pa_sf_euler_self(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage);
+// The Euler step / stage with a source term (SRC; A.src / A.src_val set): upwind with a scalar speed (US 1 / 2), a speed
+// field or SELF, central with a scalar speed or SELF.  Translation units of their own: pa_sf_src.hip, and pa_sf_src_bcl.hip
+// for the BC-on-load instantiations (rj 2 / 4, the condition of launch_sf_any checked by the caller).
+template <typename T>
+int pa_sf_euler_src(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage, bool self);
+template <typename T>
+int pa_sf_euler_src_bcl(pa_ctx* c, Cg3dArgs<T>& A, int rj, bool stage, bool self);
 
 // can k_sf take this launch?  Full 16-byte vectors only (mode 1 of cg3d_mode), scalar coefficient.
 template <typename T, int PHASE>

@@ -24,7 +24,7 @@ static int launch_sfq_any(pa_ctx* c, Cg3dArgs<T>& A) {
 
 template <typename T>
 int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, double nu, double dt, const T* phi0, double c0,
-                 double c1) {
+                 double c1, const pa_source* src) {
   const DevGeom& G = c->G;
   if (!c->sfq || !c->sf || c->slab || c->ndim != 3 || !G.act[0] || G.n0 != G.g0 || G.off0 != 0) return 0;
   if (G.n0 < 5 || G.n1 < 5 || G.n2 < 5) return 0;
@@ -35,7 +35,7 @@ int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, d
   t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
   pa_build_eq<T>(c, 1, &t, E);
   // whole 16-byte vectors, aligned operands (mode 1), option "fastpath"
-  if (cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0}) != 1) return 0;
+  if (cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0, src ? src->field : nullptr}) != 1) return 0;
   Cg3dArgs<T> A;
   memset(&A, 0, sizeof(A));
   fill_common<T>(c, E, A);
@@ -48,10 +48,16 @@ int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, d
     A.out_all = faces == 6 ? 1 : 0;
   }
   if (!sf_applies<T, 3>(c, A, 1)) return 0;
-  const int n = phi0 ? launch_sfq_any<T, true>(c, A) : launch_sfq_any<T, false>(c, A);
+  int n;
+  if (src) {   // the SRC instantiations (pa_sfq_src.hip): two rows per wave, whatever option "sfq" says
+    A.src = (const T*)src->field; A.src_val = (T)src->value;
+    n = pa_sfq_launch_src<T>(c, A, phi0 != nullptr);
+  } else {
+    n = phi0 ? launch_sfq_any<T, true>(c, A) : launch_sfq_any<T, false>(c, A);
+  }
   if (n > 0 && hipGetLastError() != hipSuccess) { pa_set_err(c, "k_sfq launch failed"); return PA_E_HIP; }
   return n;
 }
 
-template int pa_sfq_euler<float>(pa_ctx*, Vec<float>, float*, double, const void*, double, double, const float*, double, double);
-template int pa_sfq_euler<double>(pa_ctx*, Vec<double>, double*, double, const void*, double, double, const double*, double, double);
+template int pa_sfq_euler<float>(pa_ctx*, Vec<float>, float*, double, const void*, double, double, const float*, double, double, const pa_source*);
+template int pa_sfq_euler<double>(pa_ctx*, Vec<double>, double*, double, const void*, double, double, const double*, double, double, const pa_source*);

@@ -37,10 +37,11 @@
 // Two rows per wave: two waves per SIMD.  Four rows: the six plane slots alone are 96 VGPRs, the allocator fills the 256-VGPR
 // file and parks values in AGPRs -- ONE wave per SIMD.  The rows-per-wave rule and what was measured: pa_sfq.hip, DESIGN.md
 // section 4 "QUICK".
+// SRC: the source term, k_sf's (pa_sf_kernel.h "SRC") word for word; instantiated for two rows per wave only (pa_sfq_src.hip).
 #pragma once
 #include "pa_sf_kernel.h"
 
-template <typename T, int RJ, bool HASU, int US, bool STG>
+template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false>
 __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
   static_assert(US == 0 || !HASU, "US: scalar speed");
   static_assert(HASU || US != 0, "a scalar speed has a sign");
@@ -185,6 +186,12 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
 #pragma unroll
       for (int jj = 0; jj < RJ; ++jj) Z[jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(pz + off[jj]);
     }
+    V Sv[SRC ? RJ : 1];   // SRC: the source of THIS plane (pa_sf_kernel.h "SRC"; a scalar source reads the field's own rows)
+    if constexpr (SRC) {
+      gcptr ps = (gcptr)((uintptr_t)(A.src ? A.src : A.d.p) + (size_t)(unsigned)ii * pstride);
+#pragma unroll
+      for (int jj = 0; jj < RJ; ++jj) Sv[jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(ps + off[jj]);
+    }
     // loads for the next plane first: they fly during this plane's arithmetic
     load_own(std::integral_constant<int, SL>{}, ii + 3 <= i1 + 1 ? ii + 3 : i1 + 1);   // plane q + 3 (<= two behind the chunk)
     load_halo(std::integral_constant<int, HN>{}, ii + 1 < i1 ? ii + 1 : i1 - 1);
@@ -308,6 +315,13 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
       axis(std::true_type{}, xpk, xmk, xppk, xmmk, [&](int v) { return cLo[v]; }, [&](int v) { return cHi[v]; }, A.ih[2]);
       V qv = A.p0 * axv;
       qv = qv - adv;
+      if constexpr (SRC) {   // a = a + s
+        const bool hasF = A.src != nullptr;   // wave-uniform: a source field, else the splat of src_val
+        V sv;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) sv[v] = hasF ? Sv[jj][v] : A.src_val;
+        qv = qv + sv;
+      }
       qv = A.p1 * qv;
       V res = xc + qv;
       if constexpr (STG) {
@@ -332,18 +346,21 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-template <typename T, int RJ, bool HASU, int US, bool STG>
+// the SRC instantiations (two rows per wave), in pa_sfq_src.hip: A as pa_sfq_euler fills it, A.src / A.src_val set
+template <typename T>
+int pa_sfq_launch_src(pa_ctx* c, Cg3dArgs<T>& A, bool stage);
+template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false>
 static int sfq_blocks_per_cu() {
   static int cached = 0;
   if (!cached) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sfq<T, RJ, HASU, US, STG>, 256, 0) != hipSuccess || n <= 0) n = 2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sfq<T, RJ, HASU, US, STG, SRC>, 256, 0) != hipSuccess || n <= 0) n = 2;
     cached = n;
   }
   return cached;
 }
 
-template <typename T, int RJ, bool HASU, int US, bool STG>
+template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false>
 static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr int VEC = VecOf<T>::N;
   constexpr int TJ = 4 * RJ, TK = 64 * VEC;
@@ -351,7 +368,7 @@ static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
   A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
   A.tiles_k = (int)((G.n2 + TK - 1) / TK);
   const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sfq_blocks_per_cu<T, RJ, HASU, US, STG>();
+  const int capacity = cus_of(c) * sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC>();
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
@@ -363,11 +380,11 @@ static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
   if (dbg > 0) {
     --dbg;
-    fprintf(stderr, "[pyapes_hip] k_sfq phase 3 kind %d RJ %d%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
+    fprintf(stderr, "[pyapes_hip] k_sfq phase 3 kind %d RJ %d%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
             PA_OP_DIV_QUICK, RJ, HASU ? " (speed field)" : (US == 1 ? " (u >= 0)" : " (u < 0)"), STG ? " (RK stage)" : "",
-            A.aux && (const void*)A.aux == (const void*)A.d.p ? " (self)" : "", A.tiles_j, A.tiles_k, chunks,
-            (long long)(G.n0 / chunks), nblk, sfq_blocks_per_cu<T, RJ, HASU, US, STG>());
+            A.aux && (const void*)A.aux == (const void*)A.d.p ? " (self)" : "", SRC ? " (source)" : "", A.tiles_j, A.tiles_k, chunks,
+            (long long)(G.n0 / chunks), nblk, sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC>());
   }
-  hipLaunchKernelGGL((k_sfq<T, RJ, HASU, US, STG>), dim3(nblk), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL((k_sfq<T, RJ, HASU, US, STG, SRC>), dim3(nblk), dim3(256), 0, c->stream, A);
   return nblk;
 }

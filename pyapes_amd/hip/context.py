@@ -246,10 +246,24 @@ class HipContext:
         self._rc(self.lib.pa_limiter(self.h, int(which), self._ptr(a), self._ptr(b), self._ptr(out), a.numel()))
         return out
 
+    def _source(self, source: float | Tensor | None, what: str) -> tuple[Any, Tensor | None]:
+        """``pa_source`` of a call (None: no source, the sibling entry point runs) and the tensor it points into"""
+        if source is None:
+            return None, None
+        ps = L.PaSource()
+        ps.has = 1
+        if isinstance(source, Tensor):
+            sf = self._field(source if source.dim() == self.mesh.dim else source[0], "source term")
+            ps.value, ps.field = 0.0, sf.data_ptr()
+            return ps, sf
+        ps.value, ps.field = float(source), None
+        return ps, None
+
     def euler_march(self, phi: Tensor, tmp: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
-                    nsteps: int) -> Tensor:
+                    nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``nsteps`` explicit Euler steps enqueued back to back, ping-ponging phi <-> tmp; returns the
-        tensor that holds the final state."""
+        tensor that holds the final state.  ``source``: the term S of ``+ S``, a scalar or a field-shaped tensor, frozen
+        for the whole call."""
         phi = self._field(phi, "euler_march")
         tmp = self._field(tmp, "euler_march")
         uf, us = None, 0.0
@@ -257,11 +271,17 @@ class HipContext:
             uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
         else:
             us = float(u)
-        self._rc(self.lib.pa_euler_march(self.h, self._ptr(phi), self._ptr(tmp), kind, us, self._ptr(uf),
-                                         float(nu), float(dt), int(nsteps)))
+        ps, _keep = self._source(source, "euler_march")
+        if ps is None:
+            self._rc(self.lib.pa_euler_march(self.h, self._ptr(phi), self._ptr(tmp), kind, us, self._ptr(uf),
+                                             float(nu), float(dt), int(nsteps)))
+        else:
+            self._rc(self.lib.pa_euler_march_src(self.h, self._ptr(phi), self._ptr(tmp), kind, us, self._ptr(uf),
+                                                 float(nu), float(dt), int(nsteps), C.byref(ps)))
         return phi if nsteps % 2 == 0 else tmp
 
-    def euler_step(self, phi: Tensor, out: Tensor, kind: int, u: float | Tensor, nu: float, dt: float) -> None:
+    def euler_step(self, phi: Tensor, out: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
+                   source: float | Tensor | None = None) -> None:
         phi = self._field(phi, "euler_step")
         out = self._field(out, "euler_step")
         uf, us = None, 0.0
@@ -269,12 +289,18 @@ class HipContext:
             uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
         else:
             us = float(u)
-        self._rc(self.lib.pa_euler_step(self.h, self._ptr(phi), self._ptr(out), kind, us, self._ptr(uf),
-                                        float(nu), float(dt)))
+        ps, _keep = self._source(source, "euler_step")
+        if ps is None:
+            self._rc(self.lib.pa_euler_step(self.h, self._ptr(phi), self._ptr(out), kind, us, self._ptr(uf),
+                                            float(nu), float(dt)))
+        else:
+            self._rc(self.lib.pa_euler_step_src(self.h, self._ptr(phi), self._ptr(out), kind, us, self._ptr(uf),
+                                                float(nu), float(dt), C.byref(ps)))
 
     def rk_stage(self, phi: Tensor, phi0: Tensor, out: Tensor, c0: float, c1: float, kind: int, u: float | Tensor,
-                 nu: float, dt: float) -> None:
-        """``out = B(c0 * phi0 + c1 * E(phi))``: one fused stage of an SSP Runge-Kutta step (E: the Euler step)."""
+                 nu: float, dt: float, source: float | Tensor | None = None) -> None:
+        """``out = B(c0 * phi0 + c1 * E(phi))``: one fused stage of an SSP Runge-Kutta step (E: the Euler step, with
+        ``source`` the step ``E_S`` that adds it)."""
         phi = self._field(phi, "rk_stage")
         phi0 = self._field(phi0, "rk_stage")
         out = self._field(out, "rk_stage")
@@ -283,13 +309,18 @@ class HipContext:
             uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
         else:
             us = float(u)
-        self._rc(self.lib.pa_rk_stage(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1),
-                                      kind, us, self._ptr(uf), float(nu), float(dt)))
+        ps, _keep = self._source(source, "rk_stage")
+        if ps is None:
+            self._rc(self.lib.pa_rk_stage(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1),
+                                          kind, us, self._ptr(uf), float(nu), float(dt)))
+        else:
+            self._rc(self.lib.pa_rk_stage_src(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1),
+                                              kind, us, self._ptr(uf), float(nu), float(dt), C.byref(ps)))
 
     def rk_march(self, phi: Tensor, w1: Tensor, w2: Tensor, order: int, kind: int, u: float | Tensor, nu: float,
-                 dt: float, nsteps: int) -> Tensor:
+                 dt: float, nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``nsteps`` SSP Runge-Kutta steps of ``order`` enqueued back to back over the three buffers; returns the
-        tensor that holds the final state."""
+        tensor that holds the final state.  ``source``: frozen for the whole call, in every stage."""
         bufs = [self._field(t, "rk_march") for t in (phi, w1, w2)]
         uf, us = None, 0.0
         if isinstance(u, Tensor):
@@ -297,21 +328,31 @@ class HipContext:
         else:
             us = float(u)
         final = C.c_int(0)
-        self._rc(self.lib.pa_rk_march(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2]), int(order),
-                                      kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), C.byref(final)))
+        ps, _keep = self._source(source, "rk_march")
+        if ps is None:
+            self._rc(self.lib.pa_rk_march(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2]), int(order),
+                                          kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), C.byref(final)))
+        else:
+            self._rc(self.lib.pa_rk_march_src(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2]), int(order),
+                                              kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), C.byref(final),
+                                              C.byref(ps)))
         return bufs[final.value]
 
     def rk_march_self(self, phi: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int, nu: float, dt: float,
-                      nsteps: int) -> Tensor:
+                      nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``rk_march`` of a field that advects itself: every launch takes its own input buffer as the speed.  Order 1
         needs no ``w2``.  Returns the tensor that holds the final state."""
         bufs = [self._field(t, "rk_march_self") for t in (phi, w1)]
         if w2 is not None:
             bufs.append(self._field(w2, "rk_march_self"))
         final = C.c_int(0)
-        self._rc(self.lib.pa_rk_march_self(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]),
-                                           self._ptr(bufs[2] if len(bufs) > 2 else None), int(order), kind, float(nu),
-                                           float(dt), int(nsteps), C.byref(final)))
+        ps, _keep = self._source(source, "rk_march_self")
+        args = (self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2] if len(bufs) > 2 else None), int(order),
+                kind, float(nu), float(dt), int(nsteps), C.byref(final))
+        if ps is None:
+            self._rc(self.lib.pa_rk_march_self(*args))
+        else:
+            self._rc(self.lib.pa_rk_march_self_src(*args, C.byref(ps)))
         return bufs[final.value]
 
     # -- solvers --------------------------------------------------------------------------

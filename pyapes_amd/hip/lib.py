@@ -43,6 +43,11 @@ class PaTerm(C.Structure):
                 ("u_field", C.c_void_p)]
 
 
+class PaSource(C.Structure):
+    """``pa_source``: the source term of the explicit steps (``has`` 0: none; ``field`` NULL: the scalar ``value``)"""
+    _fields_ = [("has", C.c_int32), ("value", C.c_double), ("field", C.c_void_p)]
+
+
 class PaSlab(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "sums", "r_send_lo", "r_send_hi", "r_recv_lo", "r_recv_hi", "x_ghost_lo", "x_ghost_hi",
@@ -102,6 +107,15 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
     "pa_rk_march": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, _VP, C.c_double, C.c_double, C.c_int64,
                               C.POINTER(C.c_int)]),
     "pa_rk_march_self": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int)]),
+    "pa_euler_step_src": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_double, _VP, C.c_double, C.c_double, C.POINTER(PaSource)]),
+    "pa_euler_march_src": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_double, _VP, C.c_double, C.c_double, C.c_int64,
+                                     C.POINTER(PaSource)]),
+    "pa_rk_stage_src": (C.c_int, [_VP, _VP, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_double, _VP, C.c_double, C.c_double,
+                                  C.POINTER(PaSource)]),
+    "pa_rk_march_src": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, _VP, C.c_double, C.c_double, C.c_int64,
+                                  C.POINTER(C.c_int), C.POINTER(PaSource)]),
+    "pa_rk_march_self_src": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int),
+                                       C.POINTER(PaSource)]),
     "pa_cg_begin": (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_int64]),
     "pa_cg_phase_a": (C.c_int, [_VP]),
     "pa_cg_phase_b": (C.c_int, [_VP]),
@@ -165,7 +179,12 @@ def load_library(path: str | None = None) -> C.CDLL:
             f"pyapes_amd: {p} not found. Build it with pyapes_amd/csrc/build.sh "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(p)
+    # an A/B library named by PYAPES_HIP_LIB (bench_ops.py *_baseline sections) may predate the source term: it runs
+    # everything but a call with a source, which then fails on the missing symbol
+    older = p != LIB_PATH
     for name, (res, args) in SIGNATURES.items():
+        if older and name.endswith("_src") and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -12,6 +12,12 @@ Self-advection, ``div(phi, phi)`` (Burgers' term): pass the field itself as ``u`
 ``rk_march(phi, phi, ...)`` -- or a Tensor / Field on ``phi()``'s own storage (``advects_itself``).  Every step and every
 stage is then advected by ITS OWN input, ``B(c0 phi0 + c1 E_self(phi_s))`` with the speed ``phi_s``, through
 ``Context.rk_march_self``.  A clone of ``phi`` is a speed frozen at the start of the call, as any other tensor.
+
+Source term, ``source=S`` (keyword only) on all four entry points:  d(phi)/dt = nu lap(phi) - div(u phi) + S.  On the interior
+set  a = nu*lap; a = a - adv; a = a + s; a = dt*a; v = phi + a,  every operation rounded in the mesh dtype, inside the step
+kernel; a Runge-Kutta stage is ``B(c0 phi0 + c1 E_S(phi_s))`` with the source in every stage.  ``S`` is a float / int, a Tensor
+shaped like ``phi()`` or like one component, or a scalar Field on the same mesh.  It is FROZEN for the whole call: a forcing
+that depends on time is supplied anew per ``rk_step``.  ``None`` is the call without the argument, bit for bit.
 """
 from __future__ import annotations
 
@@ -53,6 +59,42 @@ def _no_self_on_slabs(phi: Field, what: str) -> None:
         raise NotImplementedError(f"pyapes_amd: {what}: self-advection on a slab mesh (single GPU only)")
 
 
+def _source_of(phi: Field, source: Any, what: str) -> float | Tensor | None:
+    """the checks of ``source=`` -- made before a device is touched -- and what the Context methods take: None, a float or
+    a contiguous tensor of one component's shape"""
+    if source is None:
+        return None
+    mesh = phi.mesh
+    if getattr(mesh, "slab", None) is not None:
+        raise NotImplementedError(f"pyapes_amd: {what}: a source term on a slab mesh (single GPU only)")
+    if mesh.coord_sys == "rz":
+        raise NotImplementedError(f"pyapes_amd: {what}: a source term on an axisymmetric (rz) mesh")
+    if isinstance(source, Field):
+        if source.dim != 1:
+            raise NotImplementedError(f"pyapes_amd: {what}: the source is a scalar field (got {source.dim} components)")
+        if source.mesh is not mesh:
+            raise ValueError(f"pyapes_amd: {what}: the source Field lives on another mesh")
+        source = source()
+    if isinstance(source, bool):
+        raise TypeError(f"pyapes_amd: {what}: source is a float, a Tensor or a scalar Field")
+    if isinstance(source, (float, int)):
+        return float(source)
+    if not isinstance(source, Tensor):
+        raise TypeError(f"pyapes_amd: {what}: source is a float, a Tensor or a scalar Field (got {type(source).__name__})")
+    p = phi()
+    if tuple(source.shape) == tuple(p.shape):
+        source = source[0]
+    elif phi.dim != 1 or tuple(source.shape) != tuple(p.shape[1:]):
+        raise ValueError(f"pyapes_amd: {what}: source shape {tuple(source.shape)}, expected {tuple(p.shape)} or {tuple(p.shape[1:])}")
+    if source.dtype != p.dtype:
+        raise ValueError(f"pyapes_amd: {what}: source dtype {source.dtype} != mesh dtype {p.dtype}")
+    if source.device != p.device:
+        raise ValueError(f"pyapes_amd: {what}: source on {source.device}, the field on {p.device}")
+    if source.untyped_storage().data_ptr() == p.untyped_storage().data_ptr():
+        raise ValueError(f"pyapes_amd: {what}: the source shares phi's storage (the step kernels read it while they write phi)")
+    return source.contiguous()
+
+
 def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind: int) -> Field:
     """``Mesh(..., slab=(rank, world))``: the same call on every rank of the process group (pyapes_amd/slab.py SlabEuler)."""
     import torch.distributed as dist
@@ -74,8 +116,10 @@ def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind:
 
 
 def euler_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float,
-               config: dict | None = None) -> Field:
-    """Advance ``phi`` in place by one explicit Euler step; returns ``phi``."""
+               config: dict | None = None, *, source: float | Tensor | Field | None = None) -> Field:
+    """Advance ``phi`` in place by one explicit Euler step; returns ``phi``.  ``source``: the term S of ``+ S`` (module
+    docstring), frozen for the call."""
+    src = _source_of(phi, source, "euler_step")
     if getattr(phi.mesh, "slab", None) is not None:
         cfg = (config or {}).get("div", {"limiter": "upwind"})
         kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
@@ -90,17 +134,19 @@ def euler_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float,
     ctx = context_for(phi.mesh)
     ctx.bind_bcs(phi(), phi.bcs, 0)
     out = torch.empty_like(phi())
-    ctx.euler_step(phi()[0], out[0], kind, _adv_of(u, phi), nu, dt)
+    ctx.euler_step(phi()[0], out[0], kind, _adv_of(u, phi), nu, dt, source=src)
     phi.set_var_tensor(out)
     return phi
 
 
 def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps: int,
-                config: dict | None = None) -> Field:
+                config: dict | None = None, *, source: float | Tensor | Field | None = None) -> Field:
     """``nsteps`` explicit Euler steps with no host work in between (the whole march is enqueued by one
-    C-ABI call: fused step kernel + ordered BC fill per step, ping-pong buffers)."""
+    C-ABI call: fused step kernel + ordered BC fill per step, ping-pong buffers).  ``source``: the term S of ``+ S``
+    (module docstring), frozen for the whole call -- the same S in every step."""
     if phi.dim != 1:
         raise NotImplementedError("pyapes_amd: euler_march is for scalar fields")
+    src = _source_of(phi, source, "euler_march")
     cfg = (config or {}).get("div", {"limiter": "upwind"})
     kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
     quick_mesh_check(kind, phi.mesh, "euler_march")
@@ -119,9 +165,9 @@ def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nst
         phi.set_var_tensor(phi().contiguous())
     tmp = torch.empty_like(phi())
     if self_adv:   # the speed ping-pongs with the field: no single pointer names it
-        final = ctx.rk_march_self(phi()[0], tmp[0], None, 1, kind, nu, dt, nsteps)
+        final = ctx.rk_march_self(phi()[0], tmp[0], None, 1, kind, nu, dt, nsteps, source=src)
     else:
-        final = ctx.euler_march(phi()[0], tmp[0], kind, _adv_of(u, phi), nu, dt, nsteps)
+        final = ctx.euler_march(phi()[0], tmp[0], kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
     if final.data_ptr() == tmp[0].data_ptr():
         phi.set_var_tensor(tmp)
     if hasattr(phi, "_t"):
@@ -144,11 +190,14 @@ def _rk_args(phi: Field, config: dict | None, order: int, what: str) -> int:
 
 
 def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config: dict | None = None,
-            order: int = 3) -> Field:
-    """Advance ``phi`` by one SSP Runge-Kutta step of ``order`` (1: the Euler step); returns ``phi``."""
+            order: int = 3, *, source: float | Tensor | Field | None = None) -> Field:
+    """Advance ``phi`` by one SSP Runge-Kutta step of ``order`` (1: the Euler step); returns ``phi``.  ``source``: the term S
+    of ``+ S`` (module docstring), the same in every stage of the step; a forcing that depends on time is handed in anew
+    with each call."""
     kind = _rk_args(phi, config, order, "rk_step")
+    src = _source_of(phi, source, "rk_step")
     if order == 1:
-        return euler_step(phi, u, nu, dt, config)   # (a speed on phi's own storage is self-advection at the C ABI)
+        return euler_step(phi, u, nu, dt, config, source=src)   # (a speed on phi's own storage is self-advection at the C ABI)
     self_adv = advects_itself(phi, u)
     require_gpu(phi(), "rk_step")
     ctx = context_for(phi.mesh)
@@ -157,9 +206,9 @@ def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config:
         phi.set_var_tensor(phi().contiguous())
     w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
     if self_adv:
-        final = ctx.rk_march_self(phi()[0], w1[0], w2[0], order, kind, nu, dt, 1)
+        final = ctx.rk_march_self(phi()[0], w1[0], w2[0], order, kind, nu, dt, 1, source=src)
     else:
-        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, 1)
+        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, 1, source=src)
     for w in (w1, w2):
         if final.data_ptr() == w[0].data_ptr():
             phi.set_var_tensor(w)
@@ -167,12 +216,15 @@ def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config:
 
 
 def rk_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps: int,
-             config: dict | None = None, order: int = 3) -> Field:
+             config: dict | None = None, order: int = 3, *, source: float | Tensor | Field | None = None) -> Field:
     """``nsteps`` SSP Runge-Kutta steps of ``order`` with no host work in between (one C-ABI call enqueues the whole
     march: the Euler kernel, then one fused stage kernel per further stage, over three buffers).  Arguments as
     ``euler_march``; ``phi`` holds the final state on return and its time advances by ``nsteps * dt``.  ``u`` being
-    ``phi`` itself (``advects_itself``) marches ``div(phi, phi)``: every stage is advected by its own input."""
+    ``phi`` itself (``advects_itself``) marches ``div(phi, phi)``: every stage is advected by its own input.  ``source``:
+    the term S of ``+ S`` (module docstring), in every stage of every step and FROZEN for the whole call -- a forcing that
+    depends on time is re-supplied per ``rk_step``."""
     kind = _rk_args(phi, config, order, "rk_march")
+    src = _source_of(phi, source, "rk_march")
     self_adv = advects_itself(phi, u)
     require_gpu(phi(), "rk_march")
     ctx = context_for(phi.mesh)
@@ -181,9 +233,9 @@ def rk_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps
         phi.set_var_tensor(phi().contiguous())
     w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
     if self_adv:
-        final = ctx.rk_march_self(phi()[0], w1[0], None if order == 1 else w2[0], order, kind, nu, dt, nsteps)
+        final = ctx.rk_march_self(phi()[0], w1[0], None if order == 1 else w2[0], order, kind, nu, dt, nsteps, source=src)
     else:
-        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, nsteps)
+        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
     for w in (w1, w2):
         if final.data_ptr() == w[0].data_ptr():
             phi.set_var_tensor(w)
