@@ -3,7 +3,8 @@
 contract; bench.py is).  One JSON line per workload: explicit Laplacian apply, the explicit
 adv-diff Euler march (BASELINE config 4), the SSP Runge-Kutta march beside its unfused composition, the self-advected
 march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step composition, the marches with a source term
-(--sections source) beside the three-launch workaround and the generic kernel, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+(--sections source) beside the three-launch workaround and the generic kernel, the marches in a velocity field (--sections
+velocity) beside the one-speed marches and the generic kernel, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -58,7 +59,10 @@ def main():
                          "the default list; quick_baseline: the upwind rows alone, which a library without QUICK can run), source (euler_march "
                          "and rk_march order 3 with a scalar source and a source field, beside no source, the euler_step + torch add + "
                          "apply_bcs workaround and the generic kernel; not in the default list; source_baseline: the no-source rows alone, "
-                         "which a library without the source term can run), small (the reference's "
+                         "which a library without the source term can run), velocity (euler_march and rk_march order 3 with a "
+                         "velocity of three equal scalars and of three fields, each on k_sf and with fastpath 0, beside the scalar-speed "
+                         "and speed-tensor marches; not in the default list; velocity_baseline: the no-velocity rows alone, which a "
+                         "library without the velocity entry points can run), small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -110,6 +114,8 @@ def main():
         self_rows(q, emit, with_self=bool(sections & {"rk", "self"}))
     if sections & {"source", "source_baseline"}:
         source_rows(q, emit, with_source="source" in sections)
+    if sections & {"velocity", "velocity_baseline"}:
+        velocity_rows(q, emit, with_velocity="velocity" in sections)
     solver_rows(q, emit, sections)
 
 
@@ -325,6 +331,76 @@ def source_rows(q, emit, with_source=True):
                      {"ms_rounds": rounds[vname], "over_no_source": ms / base, "options": opts})
         ctx.set_option("fastpath", 1)
         del mesh, start, S, dtS
+        torch.cuda.empty_cache()
+
+
+def velocity_rows(q, emit, with_velocity=True):
+    """The marches in a velocity field, one advection speed per mesh axis (``u`` a tuple; the VEL instantiations of k_sf,
+    csrc/pa_sf_kernel.h), upwind, config-4 BCs, fp32: euler_march and rk_march order 3 (20 steps per call, ms per STEP).  The
+    no-velocity rows: a scalar speed with "bcl": 0 (a velocity march fills per step or stage, so that is its like-for-like
+    twin), and a speed tensor with and without BC on load.  The velocity rows: three equal scalars (beside the scalar-speed
+    row) and three fields (beside the speed-tensor row), each on k_sf and on the generic kernel ("fastpath": 0).  The
+    variants of a row are timed in turn, three rounds; "ms" is the median, "ms_rounds" all three.  Algorithmic passes per
+    launch: 2, + 1 for a speed tensor, + 3 for three velocity fields, + 1 for phi0 in a stage (12 -> 20 B per cell in fp32
+    for the Euler step with a speed tensor -> three fields)."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.march import euler_march, rk_march
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    bcs = mixed_bcs([0.0, 0.0, None, None, None, None],
+                    ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"])
+    cfg = {"div": {"limiter": "upwind"}}
+    nu, steps = 1e-3, 20
+    for n in ([128] if q else [256, 512]):
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", "single")
+        ctx = context_for(mesh)
+        start = torch.exp(-((mesh.X - 0.5) ** 2 + (mesh.Y - 0.5) ** 2 + (mesh.Z - 0.5) ** 2) / 0.02).unsqueeze(0).contiguous()
+        dx = mesh.dx_list[0]
+        dt = 0.2 * min(dx * dx / (6 * nu), dx / 1.0)
+        U = (0.5 + 0.5 * torch.sin(3.0 * mesh.X) * torch.cos(2.0 * mesh.Y)).unsqueeze(0).contiguous()   # 0 <= u <= 1
+        V3 = (U[0], (0.8 * torch.cos(2.0 * mesh.Z)).contiguous(), (-0.6 * torch.sin(mesh.X + mesh.Y)).contiguous())
+        reps = 3 if n <= 256 else 1
+
+        def euler(u):
+            return lambda phi: timed(lambda: euler_march(phi, u, nu, dt, steps, cfg), reps, warm=1) / steps
+
+        def rk3(u):
+            return lambda phi: timed(lambda: rk_march(phi, u, nu, dt, steps, cfg, order=3), reps, warm=1) / steps
+
+        for what, make, launches, extra0 in ((f"euler_march ({steps} steps per call)", euler, 1, 0),
+                                             (f"rk_march order 3 ({steps} steps per call)", rk3, 3, 2)):
+            base_passes = 2 * launches + extra0
+            variants = [("scalar speed, bcl 0", make(1.0), {"fastpath": 1, "bcl": 0}, base_passes),
+                        ("speed tensor", make(U), {"fastpath": 1, "bcl": 1}, base_passes + launches),
+                        ("speed tensor, bcl 0", make(U), {"fastpath": 1, "bcl": 0}, base_passes + launches)]
+            if with_velocity:   # (a library from before the velocity has no entry point that takes one)
+                variants += [("velocity of three equal scalars", make((1.0, 1.0, 1.0)), {"fastpath": 1, "bcl": 1}, base_passes),
+                             ("velocity of three equal scalars, fastpath 0", make((1.0, 1.0, 1.0)), {"fastpath": 0, "bcl": 1}, base_passes),
+                             ("velocity of three fields", make(V3), {"fastpath": 1, "bcl": 1}, base_passes + 3 * launches),
+                             ("velocity of three fields, fastpath 0", make(V3), {"fastpath": 0, "bcl": 1}, base_passes + 3 * launches)]
+            rounds = {v[0]: [] for v in variants}
+            for _ in range(3):
+                for vname, run, opts, _ in variants:
+                    for k, v in opts.items():
+                        ctx.set_option(k, v)
+                    phi = Field("phi", 1, mesh, {"domain": bcs, "obstacle": None})
+                    phi.set_var_tensor(start.clone())
+                    phi.apply_bcs()
+                    rounds[vname].append(run(phi))
+                    assert bool(torch.isfinite(phi()).all())
+                    del phi
+            scalar = sorted(rounds["scalar speed, bcl 0"])[1]
+            tensor = sorted(rounds["speed tensor, bcl 0"])[1]
+            for vname, _, opts, passes in variants:
+                ms = sorted(rounds[vname])[1]
+                emit(f"{what} {n}^3 f32 upwind, {vname} (config 4 BCs)", n ** 3, ms, passes, 4,
+                     {"ms_rounds": rounds[vname], "over_scalar_speed_bcl0": ms / scalar, "over_speed_tensor_bcl0": ms / tensor,
+                      "options": opts})
+        ctx.set_option("fastpath", 1)
+        ctx.set_option("bcl", 1)
+        del mesh, start, U, V3
         torch.cuda.empty_cache()
 
 

@@ -291,6 +291,34 @@ int pa_rk_march_src(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int d
 int pa_rk_march_self_src(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double nu, double dt,
                          int64_t nsteps, int* final, const pa_source* src);
 
+/* ---- velocity: one advection speed per mesh axis.  The entry points above take ONE speed per node and use it on every
+ * axis (a scalar is transported along the (1, 1, 1) diagonal).  With a velocity (u_0, u_1, u_2), for each active axis a the
+ * scheme's own per-axis term, operation for operation and every operation rounded in the grid dtype (no FMA), with the speed
+ * operand replaced by that axis's component u_a (value[a] rounded to the grid dtype, or field[a][cell]):
+ *     upwind   t_a = (max(u_a,0)*(x - x[-1]_a) + min(u_a,0)*(x[+1]_a - x)) * fl(1/dx_a)     (both halves always formed)
+ *     quick    the bq / fq / fallback halves of PA_OP_DIV_QUICK with u_a+ / u_a-, times fl(1/dx_a)
+ *     central  cP = u_a[+1]_a, cC = 0*u_a, cM = -u_a[-1]_a, periodic-face zeroing, each / fl(2 dx_a);
+ *              t_a = (cP*x[+1]_a + cC*x) + cM*x[-1]_a                       (u_a read at the axis's own two neighbours)
+ *     adv = (+0) + t_0 + t_1 + t_2;   a = nu*lap; a = a - adv; [a = a + s;] a = dt*a; v = phi + a   on the interior set,
+ * then the ordered BC fill; a stage is B( c0*phi0 + c1*E(phi_s) ).  Upwind and quick are the advective form u.grad(phi),
+ * central the conservative form, as with one speed.  value / field are indexed by MESH axis (entries >= the mesh dimension
+ * are not read); the velocity is FROZEN for the whole call.  `src` as in the pa_*_src block (NULL: none).
+ *     PA_E_ARG    vel == NULL or has == 0; PA_OP_DIV_UPWIND_COMPAT; a velocity field equal to or overlapping a buffer of the
+ *                 call (input, output, w1, w2, phi0) or the source field; an axisymmetric mesh
+ *     PA_E_STATE  slab mode
+ * and the context stays usable.  pa_rk_march_vel with order 1 is the Euler march over phi / w1 (w2 may be NULL). */
+typedef struct {
+  int32_t has;           /* 0: not a velocity (an error here) */
+  double value[3];       /* per mesh axis: the scalar component, used when field[a] == NULL */
+  const void* field[3];  /* per mesh axis: the per-cell component or NULL */
+} pa_velocity;
+int pa_euler_step_vel(pa_ctx* ctx, const void* phi_in, void* phi_out, int div_kind, const pa_velocity* vel, double nu,
+                      double dt, const pa_source* src);
+int pa_rk_stage_vel(pa_ctx* ctx, const void* phi, const void* phi0, void* out, double c0, double c1, int div_kind,
+                    const pa_velocity* vel, double nu, double dt, const pa_source* src);
+int pa_rk_march_vel(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, const pa_velocity* vel, double nu,
+                    double dt, int64_t nsteps, int* final, const pa_source* src);
+
 /* ---- vector steps for a host-stepped solver loop (pyapes_amd/solver/host_stepped.py: BC callables that read the iterate
  * make the reference's loop come back to Python for every face of every fill, bcs.py:200-253; the loop's AXPYs and dot
  * products between those fills are these).  Fields of the grid's shape and dtype.

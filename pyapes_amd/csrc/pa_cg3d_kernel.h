@@ -101,6 +101,10 @@ struct Cg3dArgs {
   // s = src[cell], or the splat of src_val when src is null (behind the stage's members for the same reason)
   const T* src;
   T src_val;
+  // velocity of the Euler step (the VEL instantiations of k_sf, pa_sf_vel.hip): one speed per INTERNAL axis, three scalars
+  // (VEL 1) or three fields read at the cell (VEL 2); behind everything else for the same reason
+  const T* vel_f[3];
+  T vel_v[3];
 };
 
 __device__ __forceinline__ int pa_xcd_remap(int b, int nb) {

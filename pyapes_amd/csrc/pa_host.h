@@ -309,6 +309,11 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
                     int bcl = 0,    // bcl: "BC on load" (pa_sf_kernel.h); 0 is returned when that form does not apply
                     const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0,    // phi0: the stage c0 phi0 + c1 E(phi) of pa_rk_stage
                     const pa_source* src = nullptr);   // src: the source term (pa_*_src) or null; k_sf's SRC instantiations or 0
+// the upwind Euler step / stage with a velocity (pa_*_vel; vel indexed by INTERNAL axis) on k_sf's VEL instantiations
+// (pa_sf_vel.hip): blocks launched, 0 when k_sf does not take the launch (the generic k_euler then runs)
+template <typename T>
+int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_velocity* vel, double nu, double dt, const T* phi0,
+                        double c0, double c1, const pa_source* src);
 template <typename T>
 int pa_tile3d_jacobi(pa_ctx* c, const DevEq<T>& E, Vec<T> x, const T* rhs, T* xnew, double omega, double* partials);
 template <typename T>

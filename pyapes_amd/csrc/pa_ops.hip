@@ -244,10 +244,95 @@ template <typename T> struct EulerStage<T, true> { const T* phi0; T c0, c1; };
 // the scalar source; the instantiations without it are the code they were
 template <typename T, bool SRC> struct EulerSrc {};
 template <typename T> struct EulerSrc<T, true> { const T* f; T val; };
-template <typename T, bool STG = false, bool SRC = false>
+// VEL: a velocity, one advection speed per INTERNAL axis (pa_*_vel) -- the advection term is pa_adv_vel below, Eadv is not
+// read; the instantiations without it are the code they were
+template <typename T, bool VEL> struct EulerVel {};
+template <typename T> struct EulerVel<T, true> { const T* f[3]; T val[3]; int kind; };
+
+// adv = (+0) + t_0 + t_1 + t_2 over the active axes: the per-axis term of pa_apply_terms' scheme `kind` (central, QUICK,
+// upwind), operation for operation, with axis a's own speed W.f[a] / W.val[a] in the place of the one speed
+template <typename T>
+__device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd, const EulerVel<T, true>& W, const FieldAcc<T>& acc,
+                                        int64_t i, int64_t j, int64_t k, T xc) {
+  int64_t g[3], N[3];
+  pa_gidx(G, i, j, k, g, N);
+  const int64_t o = i * G.s0 + j * G.s1 + k;
+  T ax = (T)0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (!G.act[a]) continue;
+    const T* uf = W.f[a];
+    const T ucen = uf ? uf[o] : W.val[a];
+    T xp, xm;
+    pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
+    if (W.kind == 2) {   // PA_OP_DIV_CENTRAL: u_a at the axis's own two neighbours (wrap-around, no slabs here)
+      T up = ucen, um = ucen;
+      if (uf) {
+        int64_t ii = i, jj = j, kk = k, i2 = i, j2 = j, k2 = k;
+        if (a == 0) { ii = pa_wrap(i + 1, G.n0); i2 = pa_wrap(i - 1, G.n0); }
+        if (a == 1) { jj = pa_wrap(j + 1, G.n1); j2 = pa_wrap(j - 1, G.n1); }
+        if (a == 2) { kk = pa_wrap(k + 1, G.n2); k2 = pa_wrap(k - 1, G.n2); }
+        up = uf[ii * G.s0 + jj * G.s1 + kk];
+        um = uf[i2 * G.s0 + j2 * G.s1 + k2];
+      }
+      T cP = up, cC = (T)0 * ucen, cM = -um;
+      if (G.bct[2 * a] == 4 && g[a] == 1) cM = (T)0;
+      if (G.bct[2 * a + 1] == 4 && g[a] == N[a] - 2) cP = (T)0;
+      cP = cP / grd.h2[a];
+      cC = cC / grd.h2[a];
+      cM = cM / grd.h2[a];
+      T s = cP * xp;
+      T m = cC * xc;
+      s = s + m;
+      m = cM * xm;
+      s = s + m;
+      ax = ax + s;
+    } else {
+      const T upl = ucen > (T)0 ? ucen : (T)0;
+      const T umi = ucen < (T)0 ? ucen : (T)0;
+      if (W.kind == 5) {   // PA_OP_DIV_QUICK
+        T xpp, xmm;
+        pa_nbrs2<T>(G, acc, a, i, j, k, xpp, xmm);
+        const bool per = G.bct[2 * a] == 4 || G.bct[2 * a + 1] == 4;
+        T cen = xp - xm;
+        cen = (T)0.5 * cen;
+        T tq = xp + xc;
+        tq = (T)0.375 * tq;
+        T sq = (T)0.875 * xm;
+        tq = tq - sq;
+        sq = (T)0.125 * xmm;
+        T bq = tq + sq;
+        if (!per && g[a] <= 1) bq = cen;
+        tq = xm + xc;
+        tq = (T)0.375 * tq;
+        sq = (T)0.875 * xp;
+        tq = sq - tq;
+        sq = (T)0.125 * xpp;
+        T fq = tq - sq;
+        if (!per && g[a] >= N[a] - 2) fq = cen;
+        T s = upl * bq;
+        T m = umi * fq;
+        s = s + m;
+        s = s * grd.ih[a];
+        ax = ax + s;
+      } else {             // PA_OP_DIV_UPWIND
+        T bwd = xc - xm;
+        T fwd = xp - xc;
+        T s = upl * bwd;
+        T m = umi * fwd;
+        s = s + m;
+        s = s * grd.ih[a];
+        ax = ax + s;
+      }
+    }
+  }
+  return ax;
+}
+
+template <typename T, bool STG = false, bool SRC = false, bool VEL = false>
 __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, DevEq<T> Eadv, Vec<T> pv,
                                                      T* __restrict__ out, T nu, T dt, EulerStage<T, STG> S = {},
-                                                     EulerSrc<T, SRC> Q = {}) {
+                                                     EulerSrc<T, SRC> Q = {}, EulerVel<T, VEL> W = {}) {
   FieldAcc<T> acc{pv};
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < G.ncell;
        idx += (int64_t)gridDim.x * blockDim.x) {
@@ -257,7 +342,9 @@ __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, De
     T v = pc;
     if (pa_in_S(G, i, j, k)) {
       T lap = pa_apply_terms<T>(G, Elap, acc, i, j, k, pc);
-      T adv = pa_apply_terms<T>(G, Eadv, acc, i, j, k, pc);
+      T adv;
+      if constexpr (VEL) adv = pa_adv_vel<T>(G, Elap.grd, W, acc, i, j, k, pc);
+      else adv = pa_apply_terms<T>(G, Eadv, acc, i, j, k, pc);
       T a = nu * lap;
       a = a - adv;
       if constexpr (SRC) {
@@ -526,6 +613,86 @@ static int euler_bcl_t(pa_ctx* c, const T* in, T* out, int kind, double u, const
   return 1;
 }
 
+// The Euler step (phi0 null) or the fused stage with a velocity (pa_*_vel), vel indexed by INTERNAL axis: k_sf's VEL
+// instantiations where pa_tile3d_euler_vel takes the launch, else the generic k_euler<..., VEL>; then the ordered BC fill.
+// A periodic face: the step, k_rk_combine in place, the fill -- as euler_t and for its reason.
+template <typename T>
+static int euler_vel_t(pa_ctx* c, const T* in, T* out, int kind, const pa_velocity* vel, double nu, double dt,
+                       const T* phi0, double c0, double c1, const pa_source* src) {
+  if (phi0) {
+    bool periodic = false;
+    for (int f = 0; f < 6; ++f) periodic = periodic || (c->G.act[f >> 1] && c->bc[f].type == PA_BC_PERIODIC);
+    if (periodic) {
+      if (int rc = euler_vel_t<T>(c, in, out, kind, vel, nu, dt, nullptr, 0.0, 0.0, src)) return rc;
+      if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
+      hipLaunchKernelGGL(k_rk_combine<T>, dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, out, phi0, (T)c0,
+                         (T)c1, c->G.ncell);
+      if (c->profile) pa_profile_stop(c, 0);
+      PA_HIP(c, hipGetLastError());
+      return pa_bc_apply_auto<T>(c, out, false);
+    }
+  }
+  pa_term tl;
+  memset(&tl, 0, sizeof(tl));
+  tl.kind = PA_OP_LAPLACIAN; tl.sign = 1.0;
+  DevEq<T> El;
+  pa_build_eq<T>(c, 1, &tl, El);
+  Vec<T> pv = pa_vec_self<T>(c, in);
+  if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
+  const int fr = pa_tile3d_euler_vel<T>(c, pv, out, kind, vel, nu, dt, phi0, c0, c1, src);
+  if (fr < 0) {
+    if (c->profile) pa_profile_stop(c, 0);
+    return fr;
+  }
+  if (fr == 0) {
+    static int dbg = -1;
+    if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 64 : 0;
+    if (dbg > 0) { --dbg; fprintf(stderr, "[pyapes_hip] k_euler%s%s (velocity): generic kernel, %lld cells\n", phi0 ? " (RK stage)" : "", src ? " (source)" : "", (long long)c->G.ncell); }
+    EulerVel<T, true> W;
+    for (int a = 0; a < 3; ++a) { W.f[a] = (const T*)vel->field[a]; W.val[a] = (T)vel->value[a]; }
+    W.kind = kind;
+    const dim3 grid(pa_grid_blocks(c->G.ncell)), block(PA_BLOCK);   // (below, the second El stands in for Eadv: unread with VEL)
+    const EulerStage<T, true> S{phi0, (T)c0, (T)c1};
+    if (src) {
+      const EulerSrc<T, true> Q{(const T*)src->field, (T)src->value};
+      if (phi0) hipLaunchKernelGGL((k_euler<T, true, true, true>), grid, block, 0, c->stream, c->G, El, El, pv, out, (T)nu, (T)dt, S, Q, W);
+      else hipLaunchKernelGGL((k_euler<T, false, true, true>), grid, block, 0, c->stream, c->G, El, El, pv, out, (T)nu, (T)dt, EulerStage<T, false>{}, Q, W);
+    } else {
+      if (phi0) hipLaunchKernelGGL((k_euler<T, true, false, true>), grid, block, 0, c->stream, c->G, El, El, pv, out, (T)nu, (T)dt, S, EulerSrc<T, false>{}, W);
+      else hipLaunchKernelGGL((k_euler<T, false, false, true>), grid, block, 0, c->stream, c->G, El, El, pv, out, (T)nu, (T)dt, EulerStage<T, false>{}, EulerSrc<T, false>{}, W);
+    }
+  }
+  if (c->profile) pa_profile_stop(c, 0);
+  PA_HIP(c, hipGetLastError());
+  return pa_bc_apply_auto<T>(c, out, false);
+}
+
+// pa_rk_march_vel: the buffer rotation of rk_march_t (order 1: the ping-pong of two buffers, b2 is not touched), a BC fill
+// behind every step and stage
+template <typename T>
+static int rk_march_vel_t(pa_ctx* c, T* b0, T* b1, T* b2, int order, int kind, const pa_velocity* vel, double nu, double dt,
+                          int64_t nsteps, int* final, const pa_source* src) {
+  const double st2[1][2] = {{0.5, 0.5}};
+  const double st3[2][2] = {{3.0 / 4.0, 1.0 / 4.0}, {1.0 / 3.0, 2.0 / 3.0}};
+  const double (*st)[2] = order == 2 ? st2 : st3;
+  T* buf[3] = {b0, b1, b2};
+  int base = 0, wa = 1, wb = 2;
+  for (int64_t s = 0; s < nsteps; ++s) {
+    int rc = euler_vel_t<T>(c, buf[base], buf[wa], kind, vel, nu, dt, nullptr, 0.0, 0.0, src);
+    if (rc) return rc;
+    int cur = wa, free_ = wb;
+    for (int q = 0; q < order - 1; ++q) {
+      rc = euler_vel_t<T>(c, buf[cur], buf[free_], kind, vel, nu, dt, buf[base], st[q][0], st[q][1], src);
+      if (rc) return rc;
+      std::swap(cur, free_);
+    }
+    const int old = base;
+    base = cur; wa = old; wb = free_;
+  }
+  *final = base;
+  return PA_OK;
+}
+
 // ---- vector steps of the host-stepped solver loops (pyapes_amd/solver/host_stepped.py) ------------------------------
 // out = y + a x, the product rounded before the sum (torch: y + a * x; "y - a x" is the same bits with -a)
 template <typename T>
@@ -770,6 +937,85 @@ static int check_source(pa_ctx* c, const pa_source** src, const char* who, std::
       return PA_E_ARG;
     }
   return PA_OK;
+}
+
+// The velocity of a pa_*_vel call: the refusals of the header, made before anything is enqueued, and the velocity by INTERNAL
+// axis in *vi (a d-dimensional mesh occupies the last d internal axes; the others carry a zero speed that is never read).
+static int check_velocity(pa_ctx* c, const pa_velocity* vel, pa_velocity* vi, int kind, const pa_source* src, const char* who,
+                          std::initializer_list<const void*> bufs) {
+  if (!vel || !vel->has) { pa_set_err(c, "%s: a velocity is needed (vel == NULL or has == 0)", who); return PA_E_ARG; }
+  if (kind == PA_OP_DIV_UPWIND_COMPAT) { pa_set_err(c, "%s: the literal upwind form takes no velocity", who); return PA_E_ARG; }
+  if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "%s: a velocity is single GPU only (no slabs)", who); return PA_E_STATE; }
+  if (c->coord != PA_COORD_XYZ) { pa_set_err(c, "%s: a velocity is for xyz meshes (no axisymmetric rows)", who); return PA_E_ARG; }
+  memset(vi, 0, sizeof(*vi));
+  vi->has = 1;
+  const size_t bytes = (size_t)c->G.ncell * (c->dtype == PA_F64 ? 8 : 4);
+  const char* sf = src ? (const char*)src->field : nullptr;
+  for (int a = 0; a < c->ndim; ++a) {
+    const int ia = a + 3 - c->ndim;
+    vi->value[ia] = vel->value[a];
+    vi->field[ia] = vel->field[a];
+    const char* f = (const char*)vel->field[a];
+    if (!f) continue;
+    bool hit = sf && f < sf + bytes && sf < f + bytes;
+    for (const void* b : bufs) hit = hit || (b && f < (const char*)b + bytes && (const char*)b < f + bytes);
+    if (hit) { pa_set_err(c, "%s: a velocity field must not be one of the call's buffers or the source field", who); return PA_E_ARG; }
+  }
+  return PA_OK;
+}
+
+int pa_euler_step_vel(pa_ctx* c, const void* in, void* out, int kind, const pa_velocity* vel, double nu, double dt,
+                      const pa_source* src) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  int rc = check_div_kind(c, kind, "pa_euler_step_vel");
+  if (rc) return rc;
+  if (!in || !out || in == out) { pa_set_err(c, "pa_euler_step_vel: in-place step is not allowed"); return PA_E_ARG; }
+  if ((rc = check_source(c, &src, "pa_euler_step_vel", {in, out}))) return rc;
+  pa_velocity vi;
+  if ((rc = check_velocity(c, vel, &vi, kind, src, "pa_euler_step_vel", {in, out}))) return rc;
+  PA_HIP(c, hipSetDevice(c->device));
+  return c->dtype == PA_F64 ? euler_vel_t<double>(c, (const double*)in, (double*)out, kind, &vi, nu, dt, nullptr, 0.0, 0.0, src)
+                            : euler_vel_t<float>(c, (const float*)in, (float*)out, kind, &vi, nu, dt, nullptr, 0.0, 0.0, src);
+}
+
+int pa_rk_stage_vel(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind,
+                    const pa_velocity* vel, double nu, double dt, const pa_source* src) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  int rc = check_div_kind(c, kind, "pa_rk_stage_vel");
+  if (rc) return rc;
+  if (!phi || !phi0 || !out || out == phi || out == phi0) {
+    pa_set_err(c, "pa_rk_stage_vel: out must be a buffer of its own (not phi, not phi0)");
+    return PA_E_ARG;
+  }
+  if ((rc = check_source(c, &src, "pa_rk_stage_vel", {phi, phi0, out}))) return rc;
+  pa_velocity vi;
+  if ((rc = check_velocity(c, vel, &vi, kind, src, "pa_rk_stage_vel", {phi, phi0, out}))) return rc;
+  PA_HIP(c, hipSetDevice(c->device));
+  return c->dtype == PA_F64
+             ? euler_vel_t<double>(c, (const double*)phi, (double*)out, kind, &vi, nu, dt, (const double*)phi0, c0, c1, src)
+             : euler_vel_t<float>(c, (const float*)phi, (float*)out, kind, &vi, nu, dt, (const float*)phi0, c0, c1, src);
+}
+
+int pa_rk_march_vel(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, const pa_velocity* vel, double nu,
+                    double dt, int64_t nsteps, int* final, const pa_source* src) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  if (order < 1 || order > 3) { pa_set_err(c, "pa_rk_march_vel: order %d (1, 2 or 3)", order); return PA_E_ARG; }
+  int rc = check_div_kind(c, kind, "pa_rk_march_vel");
+  if (rc) return rc;
+  if (!phi || !w1 || !final || phi == w1 || nsteps < 0 || (order > 1 && (!w2 || phi == w2 || w1 == w2))) {
+    pa_set_err(c, "pa_rk_march_vel: distinct buffers (two for order 1, else three), a place for the result index and "
+                  "nsteps >= 0 are needed");
+    return PA_E_ARG;
+  }
+  if (order == 1) w2 = nullptr;
+  if ((rc = check_source(c, &src, "pa_rk_march_vel", {phi, w1, w2}))) return rc;
+  pa_velocity vi;
+  if ((rc = check_velocity(c, vel, &vi, kind, src, "pa_rk_march_vel", {phi, w1, w2}))) return rc;
+  PaRange range_("pyapes march in a velocity field");
+  PA_HIP(c, hipSetDevice(c->device));
+  return c->dtype == PA_F64
+             ? rk_march_vel_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, &vi, nu, dt, nsteps, final, src)
+             : rk_march_vel_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, &vi, nu, dt, nsteps, final, src);
 }
 
 int pa_euler_step_src(pa_ctx* c, const void* in, void* out, int kind, double u, const void* u_field, double nu, double dt,

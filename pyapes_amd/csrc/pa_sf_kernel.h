@@ -110,11 +110,22 @@ template <> struct SfBits<double> {
 // nu lap - adv and the product with dt.  A.src == nullptr is a scalar source: the splat of A.src_val (wave-uniform select;
 // the load then reads the field's own rows and is dropped, so that no branch sits between a load and its use).  RJ * VEC
 // more live registers for one plane.  The SRC = false instantiations are the code they were.
+// VEL: a velocity, one advection speed per axis (pa_*_vel), of the upwind Euler step: t_a = u_a+ (x - x[-1]_a) + u_a- (x[+1]_a - x)
+// with axis a's own component, both halves always formed (the dead-half trick US is per launch: eight sign combinations).
+// 1: three scalar speeds A.vel_v -- u_a+ / u_a- do not change from plane to plane and are formed in front of the plane loop; in
+// the SOURCE they stand inside the plane's lambda (the compiler hoists the six selects): declared at function scope they enter
+// the lambdas' capture lists, and that alone moved the SGPR spill counts of 16 BC-on-load instantiations without a velocity
+// (e.g. 105 -> 102), as the source term's flag once did.  2: three speed fields A.vel_f, read at
+// the cell only (upwind takes the speed at the node: no stencil reach, no halo) -- three 16-byte lane accesses per row and
+// plane, issued at the top of the plane beside phi0's and the source's, in front of the loads of plane q + 2, and used in that
+// plane; 3 * RJ * VEC more live registers for one plane.  Instantiated at two rows per wave (pa_sf_vel.hip).  The VEL = 0
+// instantiations are the code they were.
 #ifndef PA_SF_USIGN
 #define PA_SF_USIGN 1
 #endif
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false, int VEL = 0>
 __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
+  static_assert(VEL == 0 || ((VEL == 1 || VEL == 2) && PHASE == 3 && KIND == 4 && !HASU && !SELF && !BCL && US == 0), "VEL: the upwind Euler step, no other speed");
   static_assert(!SELF || (PHASE == 3 && !HASU && US == 0), "SELF: the Euler step, no other speed");
   static_assert(!BCL || PHASE == 3, "BC on load: the Euler step");
   static_assert(!STG || PHASE == 3, "STG: the Euler step");
@@ -319,6 +330,24 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 #pragma unroll
       for (int jj = 0; jj < RJ; ++jj) Sv[jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(ps + off[jj]);
     }
+    V uplA[VEL == 1 ? 3 : 1], umiA[VEL == 1 ? 3 : 1];   // VEL 1: u_a+ / u_a- of the three scalar speeds (loop-invariant: hoisted)
+    if constexpr (VEL == 1) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const T u = A.vel_v[a];
+        uplA[a] = (V)(u > (T)0 ? u : (T)0);
+        umiA[a] = (V)(u < (T)0 ? u : (T)0);
+      }
+    }
+    V Wv[VEL == 2 ? 3 : 1][VEL == 2 ? RJ : 1];   // VEL 2: the three speed fields of THIS plane, beside phi0's and the source's
+    if constexpr (VEL == 2) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        gcptr pw = (gcptr)((uintptr_t)A.vel_f[a] + (size_t)(unsigned)ii * pstride);
+#pragma unroll
+        for (int jj = 0; jj < RJ; ++jj) Wv[a][jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(pw + off[jj]);
+      }
+    }
     // loads for later planes first: they fly during this plane's arithmetic
     load_own(std::integral_constant<int, SL>{}, ii + 2 <= i1 ? ii + 2 : i1);          // plane q + 2 (<= the one behind the chunk)
     load_halo(std::integral_constant<int, HN>{}, ii + 2 < i1 ? ii + 2 : i1 - 1);
@@ -492,7 +521,23 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
               V t;
-              if constexpr (US == 1) {          // u >= 0: u- = +0, its half is a signed zero
+              if constexpr (VEL != 0) {         // axis a's own speed, both halves
+                V upa, uma;
+                if constexpr (VEL == 1) { upa = uplA[a]; uma = umiA[a]; }
+                else {
+                  const V ua = Wv[a][jj];
+#pragma unroll
+                  for (int v = 0; v < VEC; ++v) {
+                    upa[v] = ua[v] > (T)0 ? ua[v] : (T)0;
+                    uma[v] = ua[v] < (T)0 ? ua[v] : (T)0;
+                  }
+                }
+                V bwd = xc - xm3[a];
+                V fwd = xp3[a] - xc;
+                t = upa * bwd;
+                V m2 = uma * fwd;
+                t = t + m2;
+              } else if constexpr (US == 1) {   // u >= 0: u- = +0, its half is a signed zero
                 V bwd = xc - xm3[a];
                 t = upl * bwd;
               } else if constexpr (US == 2) {   // u < 0: u+ = +0
@@ -595,18 +640,18 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false, int VEL = 0>
 static int sf_blocks_per_cu() {
   static int cached = 0;
   if (!cached) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>, 256, 0) != hipSuccess || n <= 0) n = 4;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>, 256, 0) != hipSuccess || n <= 0) n = 4;
     cached = n;
   }
   return cached;
 }
 
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false>
+template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false, int VEL = 0>
 static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr int VEC = VecOf<T>::N;
   constexpr int TJ = 4 * RJ, TK = 64 * VEC;
@@ -614,7 +659,7 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
   A.tiles_k = (int)((G.n2 + TK - 1) / TK);
   const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>();
+  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>();
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
@@ -626,11 +671,11 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
   if (dbg > 0) {
     --dbg;
-    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", SRC ? " (source)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
-            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>());
+    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
+            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", SRC ? " (source)" : "", VEL ? " (velocity)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
+            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>());
   }
-  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC>), dim3(nblk), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>), dim3(nblk), dim3(256), 0, c->stream, A);
   return nblk;
 }
 
@@ -725,6 +770,11 @@ template <typename T>
 int pa_sf_euler_src(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage, bool self);
 template <typename T>
 int pa_sf_euler_src_bcl(pa_ctx* c, Cg3dArgs<T>& A, int rj, bool stage, bool self);
+
+// The upwind Euler step / stage with a velocity (VEL 1: three scalar speeds A.vel_v, VEL 2: three speed fields A.vel_f), two
+// rows per wave, with and without STG and SRC.  A translation unit of its own: pa_sf_vel.hip.
+template <typename T>
+int pa_sf_euler_vel(pa_ctx* c, Cg3dArgs<T>& A, bool stage, bool fields, bool source);
 
 // can k_sf take this launch?  Full 16-byte vectors only (mode 1 of cg3d_mode), scalar coefficient.
 template <typename T, int PHASE>

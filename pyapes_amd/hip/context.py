@@ -259,6 +259,59 @@ class HipContext:
         ps.value, ps.field = float(source), None
         return ps, None
 
+    def _velocity(self, vel: Sequence[float | Tensor], what: str) -> tuple[Any, list[Tensor]]:
+        """``pa_velocity`` of a call -- one entry per mesh axis, a number or a tensor of the mesh's shape -- and the tensors
+        it points into"""
+        if len(vel) != self.mesh.dim:
+            raise ValueError(f"pyapes_amd: {what}: a velocity has one entry per mesh axis ({len(vel)} for {self.mesh.dim})")
+        pv = L.PaVelocity()
+        pv.has = 1
+        keep = []
+        for a, comp in enumerate(vel):
+            if isinstance(comp, Tensor):
+                t = self._field(comp, "velocity component")
+                keep.append(t)
+                pv.value[a], pv.field[a] = 0.0, t.data_ptr()
+            else:
+                pv.value[a], pv.field[a] = float(comp), None
+        return pv, keep
+
+    def euler_step_vel(self, phi: Tensor, out: Tensor, kind: int, vel: Sequence[float | Tensor], nu: float, dt: float,
+                       source: float | Tensor | None = None) -> None:
+        """``euler_step`` in a velocity field: one advection speed per mesh axis (``pa_euler_step_vel``)"""
+        phi = self._field(phi, "euler_step_vel")
+        out = self._field(out, "euler_step_vel")
+        pv, _kv = self._velocity(vel, "euler_step_vel")
+        ps, _keep = self._source(source, "euler_step_vel")
+        self._rc(self.lib.pa_euler_step_vel(self.h, self._ptr(phi), self._ptr(out), kind, C.byref(pv), float(nu), float(dt),
+                                            None if ps is None else C.byref(ps)))
+
+    def rk_stage_vel(self, phi: Tensor, phi0: Tensor, out: Tensor, c0: float, c1: float, kind: int,
+                     vel: Sequence[float | Tensor], nu: float, dt: float, source: float | Tensor | None = None) -> None:
+        """``rk_stage`` in a velocity field (``pa_rk_stage_vel``)"""
+        phi = self._field(phi, "rk_stage_vel")
+        phi0 = self._field(phi0, "rk_stage_vel")
+        out = self._field(out, "rk_stage_vel")
+        pv, _kv = self._velocity(vel, "rk_stage_vel")
+        ps, _keep = self._source(source, "rk_stage_vel")
+        self._rc(self.lib.pa_rk_stage_vel(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1), kind,
+                                          C.byref(pv), float(nu), float(dt), None if ps is None else C.byref(ps)))
+
+    def rk_march_vel(self, phi: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int, vel: Sequence[float | Tensor],
+                     nu: float, dt: float, nsteps: int, source: float | Tensor | None = None) -> Tensor:
+        """``rk_march`` in a velocity field, frozen for the whole call (``pa_rk_march_vel``).  Order 1 is the Euler march and
+        needs no ``w2``.  Returns the tensor that holds the final state."""
+        bufs = [self._field(t, "rk_march_vel") for t in (phi, w1)]
+        if w2 is not None:
+            bufs.append(self._field(w2, "rk_march_vel"))
+        pv, _kv = self._velocity(vel, "rk_march_vel")
+        ps, _keep = self._source(source, "rk_march_vel")
+        final = C.c_int(0)
+        self._rc(self.lib.pa_rk_march_vel(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2] if len(bufs) > 2 else None),
+                                          int(order), kind, C.byref(pv), float(nu), float(dt), int(nsteps), C.byref(final),
+                                          None if ps is None else C.byref(ps)))
+        return bufs[final.value]
+
     def euler_march(self, phi: Tensor, tmp: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
                     nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``nsteps`` explicit Euler steps enqueued back to back, ping-ponging phi <-> tmp; returns the

@@ -48,6 +48,11 @@ class PaSource(C.Structure):
     _fields_ = [("has", C.c_int32), ("value", C.c_double), ("field", C.c_void_p)]
 
 
+class PaVelocity(C.Structure):
+    """``pa_velocity``: one advection speed per mesh axis (``field[a]`` NULL: the scalar ``value[a]``)"""
+    _fields_ = [("has", C.c_int32), ("value", C.c_double * 3), ("field", C.c_void_p * 3)]
+
+
 class PaSlab(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "sums", "r_send_lo", "r_send_hi", "r_recv_lo", "r_recv_hi", "x_ghost_lo", "x_ghost_hi",
@@ -116,6 +121,11 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
                                   C.POINTER(C.c_int), C.POINTER(PaSource)]),
     "pa_rk_march_self_src": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int64, C.POINTER(C.c_int),
                                        C.POINTER(PaSource)]),
+    "pa_euler_step_vel": (C.c_int, [_VP, _VP, _VP, C.c_int, C.POINTER(PaVelocity), C.c_double, C.c_double, C.POINTER(PaSource)]),
+    "pa_rk_stage_vel": (C.c_int, [_VP, _VP, _VP, _VP, C.c_double, C.c_double, C.c_int, C.POINTER(PaVelocity), C.c_double, C.c_double,
+                                  C.POINTER(PaSource)]),
+    "pa_rk_march_vel": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.POINTER(PaVelocity), C.c_double, C.c_double, C.c_int64,
+                                  C.POINTER(C.c_int), C.POINTER(PaSource)]),
     "pa_cg_begin": (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_int64]),
     "pa_cg_phase_a": (C.c_int, [_VP]),
     "pa_cg_phase_b": (C.c_int, [_VP]),
@@ -179,11 +189,11 @@ def load_library(path: str | None = None) -> C.CDLL:
             f"pyapes_amd: {p} not found. Build it with pyapes_amd/csrc/build.sh "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(p)
-    # an A/B library named by PYAPES_HIP_LIB (bench_ops.py *_baseline sections) may predate the source term: it runs
-    # everything but a call with a source, which then fails on the missing symbol
+    # an A/B library named by PYAPES_HIP_LIB (bench_ops.py *_baseline sections) may predate the source term or the velocity:
+    # it runs everything but a call with one of them, which then fails on the missing symbol
     older = p != LIB_PATH
     for name, (res, args) in SIGNATURES.items():
-        if older and name.endswith("_src") and not hasattr(lib, name):
+        if older and name.endswith(("_src", "_vel")) and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
         fn.restype = res

@@ -18,6 +18,19 @@ set  a = nu*lap; a = a - adv; a = a + s; a = dt*a; v = phi + a,  every operation
 kernel; a Runge-Kutta stage is ``B(c0 phi0 + c1 E_S(phi_s))`` with the source in every stage.  ``S`` is a float / int, a Tensor
 shaped like ``phi()`` or like one component, or a scalar Field on the same mesh.  It is FROZEN for the whole call: a forcing
 that depends on time is supplied anew per ``rk_step``.  ``None`` is the call without the argument, bit for bit.
+
+Velocity: ``u`` with one advection speed per mesh axis, (u_0, .., u_{d-1}), on all four entry points -- uniform flow along one
+axis, shear, rotation.  A float, a ``(1, *n)`` Tensor or a scalar Field stays ONE speed used on every axis (transport along the
+diagonal); a velocity is
+  * a tuple / list of ``mesh.dim`` entries, each a number or a Tensor of one component's shape (``phi()[0].shape``), of the
+    mesh dtype and on the mesh device -- if any entry is a Tensor the numeric entries are materialised on the host side as
+    tensors filled with the number (all-numeric velocities stay scalars down to the kernel),
+  * a Tensor of shape ``(mesh.dim, *n)`` on a mesh with more than one axis, or
+  * a vector Field with ``dim == mesh.dim > 1`` on the same mesh.
+Per axis the scheme's own term is formed with that axis's component (DESIGN.md section 4 "Velocity"): upwind and QUICK in the
+advective form u . grad(phi) with the speed at the node, central in the conservative form with u_a at the axis's two
+neighbours.  The velocity is FROZEN for the whole call, like a speed tensor; ``source=`` composes with it.  Not with a velocity:
+slab and axisymmetric meshes, ``compat: True``, a component on ``phi``'s own storage (no self-advection by component).
 """
 from __future__ import annotations
 
@@ -95,6 +108,62 @@ def _source_of(phi: Field, source: Any, what: str) -> float | Tensor | None:
     return source.contiguous()
 
 
+def _velocity_of(phi: Field, u: Any, config: dict | None, what: str) -> list[float | Tensor] | None:
+    """``u`` as a velocity -- one entry per mesh axis, all numbers or all contiguous tensors of one component's shape -- or None
+    when ``u`` is one speed for every axis (a float, a ``(1, *n)`` Tensor, a scalar Field: the existing path, untouched).  All
+    checks of a velocity are made here, before a device is touched."""
+    mesh = phi.mesh
+    nd = mesh.dim
+    if phi.dim != 1 and not isinstance(u, (tuple, list)):
+        return None   # a vector target with a Tensor / Field: refused where it is today ("... is for scalar fields")
+    if isinstance(u, Field):
+        if not (u.dim == nd and nd > 1):
+            return None
+        if u.mesh is not mesh:
+            raise ValueError(f"pyapes_amd: {what}: the velocity Field lives on another mesh")
+        t = u()
+        entries: list[Any] = [t[a] for a in range(nd)]
+    elif isinstance(u, Tensor):
+        if not (nd > 1 and u.dim() == nd + 1 and u.shape[0] == nd):
+            return None
+        entries = [u[a] for a in range(nd)]
+    elif isinstance(u, (tuple, list)):
+        entries = list(u)
+        if len(entries) != nd:
+            raise ValueError(f"pyapes_amd: {what}: a velocity has one entry per mesh axis ({len(entries)} given, the mesh has {nd})")
+    else:
+        return None
+    if phi.dim != 1:
+        raise NotImplementedError(f"pyapes_amd: {what}: a velocity advects a scalar field (got {phi.dim} components)")
+    if getattr(mesh, "slab", None) is not None:
+        raise NotImplementedError(f"pyapes_amd: {what}: a velocity on a slab mesh (single GPU only)")
+    if mesh.coord_sys == "rz":
+        raise NotImplementedError(f"pyapes_amd: {what}: a velocity on an axisymmetric (rz) mesh")
+    if bool(((config or {}).get("div") or {}).get("compat", False)):
+        raise NotImplementedError(f"pyapes_amd: {what}: a velocity with compat: True (the reference's literal upwind form takes one speed)")
+    p = phi()
+    comp_shape = tuple(p.shape[1:])
+    out: list[float | Tensor] = []
+    for a, e in enumerate(entries):
+        if isinstance(e, bool) or not isinstance(e, (float, int, Tensor)):
+            raise TypeError(f"pyapes_amd: {what}: velocity entry {a} is a number or a Tensor (got {type(e).__name__})")
+        if isinstance(e, Tensor):
+            if tuple(e.shape) != comp_shape:
+                raise ValueError(f"pyapes_amd: {what}: velocity entry {a} has shape {tuple(e.shape)}, expected {comp_shape}")
+            if e.dtype != p.dtype:
+                raise ValueError(f"pyapes_amd: {what}: velocity entry {a} has dtype {e.dtype}, the mesh {p.dtype}")
+            if e.device != p.device:
+                raise ValueError(f"pyapes_amd: {what}: velocity entry {a} on {e.device}, the field on {p.device}")
+            if e.untyped_storage().data_ptr() == p.untyped_storage().data_ptr():
+                raise ValueError(f"pyapes_amd: {what}: velocity entry {a} shares phi's storage (no self-advection by component)")
+            out.append(e)
+        else:
+            out.append(float(e))
+    if any(isinstance(e, Tensor) for e in out):   # mixed: the numbers become filled tensors
+        out = [e.contiguous() if isinstance(e, Tensor) else torch.full(comp_shape, e, dtype=p.dtype, device=p.device) for e in out]
+    return out
+
+
 def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind: int) -> Field:
     """``Mesh(..., slab=(rank, world))``: the same call on every rank of the process group (pyapes_amd/slab.py SlabEuler)."""
     import torch.distributed as dist
@@ -115,10 +184,12 @@ def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind:
     return phi
 
 
-def euler_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float,
+def euler_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float,
                config: dict | None = None, *, source: float | Tensor | Field | None = None) -> Field:
     """Advance ``phi`` in place by one explicit Euler step; returns ``phi``.  ``source``: the term S of ``+ S`` (module
-    docstring), frozen for the call."""
+    docstring), frozen for the call.  ``u``: one speed for every axis, or a velocity -- one speed per mesh axis (module
+    docstring "Velocity"), frozen for the call."""
+    vel = _velocity_of(phi, u, config, "euler_step")
     src = _source_of(phi, source, "euler_step")
     if getattr(phi.mesh, "slab", None) is not None:
         cfg = (config or {}).get("div", {"limiter": "upwind"})
@@ -134,18 +205,23 @@ def euler_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float,
     ctx = context_for(phi.mesh)
     ctx.bind_bcs(phi(), phi.bcs, 0)
     out = torch.empty_like(phi())
-    ctx.euler_step(phi()[0], out[0], kind, _adv_of(u, phi), nu, dt, source=src)
+    if vel is not None:
+        ctx.euler_step_vel(phi()[0], out[0], kind, vel, nu, dt, source=src)
+    else:
+        ctx.euler_step(phi()[0], out[0], kind, _adv_of(u, phi), nu, dt, source=src)
     phi.set_var_tensor(out)
     return phi
 
 
-def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps: int,
+def euler_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float, nsteps: int,
                 config: dict | None = None, *, source: float | Tensor | Field | None = None) -> Field:
     """``nsteps`` explicit Euler steps with no host work in between (the whole march is enqueued by one
     C-ABI call: fused step kernel + ordered BC fill per step, ping-pong buffers).  ``source``: the term S of ``+ S``
-    (module docstring), frozen for the whole call -- the same S in every step."""
+    (module docstring), frozen for the whole call -- the same S in every step.  ``u`` may be a velocity, one speed per mesh
+    axis (module docstring "Velocity"): it is FROZEN for the whole call, like a speed tensor."""
     if phi.dim != 1:
         raise NotImplementedError("pyapes_amd: euler_march is for scalar fields")
+    vel = _velocity_of(phi, u, config, "euler_march")
     src = _source_of(phi, source, "euler_march")
     cfg = (config or {}).get("div", {"limiter": "upwind"})
     kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
@@ -164,7 +240,9 @@ def euler_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nst
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
     tmp = torch.empty_like(phi())
-    if self_adv:   # the speed ping-pongs with the field: no single pointer names it
+    if vel is not None:
+        final = ctx.rk_march_vel(phi()[0], tmp[0], None, 1, kind, vel, nu, dt, nsteps, source=src)
+    elif self_adv:   # the speed ping-pongs with the field: no single pointer names it
         final = ctx.rk_march_self(phi()[0], tmp[0], None, 1, kind, nu, dt, nsteps, source=src)
     else:
         final = ctx.euler_march(phi()[0], tmp[0], kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
@@ -189,11 +267,12 @@ def _rk_args(phi: Field, config: dict | None, order: int, what: str) -> int:
     return kind
 
 
-def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config: dict | None = None,
+def rk_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float, config: dict | None = None,
             order: int = 3, *, source: float | Tensor | Field | None = None) -> Field:
     """Advance ``phi`` by one SSP Runge-Kutta step of ``order`` (1: the Euler step); returns ``phi``.  ``source``: the term S
     of ``+ S`` (module docstring), the same in every stage of the step; a forcing that depends on time is handed in anew
-    with each call."""
+    with each call.  ``u`` may be a velocity (module docstring "Velocity"), frozen for the step."""
+    vel = _velocity_of(phi, u, config, "rk_step")
     kind = _rk_args(phi, config, order, "rk_step")
     src = _source_of(phi, source, "rk_step")
     if order == 1:
@@ -205,7 +284,9 @@ def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config:
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
     w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
-    if self_adv:
+    if vel is not None:
+        final = ctx.rk_march_vel(phi()[0], w1[0], w2[0], order, kind, vel, nu, dt, 1, source=src)
+    elif self_adv:
         final = ctx.rk_march_self(phi()[0], w1[0], w2[0], order, kind, nu, dt, 1, source=src)
     else:
         final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, 1, source=src)
@@ -215,14 +296,16 @@ def rk_step(phi: Field, u: float | Tensor | Field, nu: float, dt: float, config:
     return phi
 
 
-def rk_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps: int,
+def rk_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float, nsteps: int,
              config: dict | None = None, order: int = 3, *, source: float | Tensor | Field | None = None) -> Field:
     """``nsteps`` SSP Runge-Kutta steps of ``order`` with no host work in between (one C-ABI call enqueues the whole
     march: the Euler kernel, then one fused stage kernel per further stage, over three buffers).  Arguments as
     ``euler_march``; ``phi`` holds the final state on return and its time advances by ``nsteps * dt``.  ``u`` being
     ``phi`` itself (``advects_itself``) marches ``div(phi, phi)``: every stage is advected by its own input.  ``source``:
     the term S of ``+ S`` (module docstring), in every stage of every step and FROZEN for the whole call -- a forcing that
-    depends on time is re-supplied per ``rk_step``."""
+    depends on time is re-supplied per ``rk_step``.  ``u`` may be a velocity, one speed per mesh axis (module docstring
+    "Velocity"): FROZEN for the whole call, the same in every stage of every step."""
+    vel = _velocity_of(phi, u, config, "rk_march")
     kind = _rk_args(phi, config, order, "rk_march")
     src = _source_of(phi, source, "rk_march")
     self_adv = advects_itself(phi, u)
@@ -232,7 +315,9 @@ def rk_march(phi: Field, u: float | Tensor | Field, nu: float, dt: float, nsteps
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
     w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
-    if self_adv:
+    if vel is not None:
+        final = ctx.rk_march_vel(phi()[0], w1[0], None if order == 1 else w2[0], order, kind, vel, nu, dt, nsteps, source=src)
+    elif self_adv:
         final = ctx.rk_march_self(phi()[0], w1[0], None if order == 1 else w2[0], order, kind, nu, dt, nsteps, source=src)
     else:
         final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
