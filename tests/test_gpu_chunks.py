@@ -101,13 +101,22 @@ class Case:
     def speed(self, form):
         return {"pos": 1.3, "neg": -0.8, "zero": 0.0, "field": self.ufield, "self": self.phis}[form]
 
-    def launch(self, scheme, form, stage):
-        u = self.speed(form)
+    def launch(self, scheme, form, stage, source=None, velocity=None):
+        """one Euler step (stage None) or fused stage; source: None, a number or a tensor of one component's shape; velocity:
+        None, or one entry per axis in place of the speed `form` names (tests/test_gpu_chunks_terms.py)"""
         out = torch.full_like(self.phis, float("nan"))
+        if velocity is not None:
+            if stage is None:
+                self.ctx.euler_step_vel(self.phis[0], out[0], _kind(scheme), velocity, self.nu, self.dt, source=source)
+            else:
+                self.ctx.rk_stage_vel(self.phis[0], self.phi0[0], out[0], stage[0], stage[1], _kind(scheme), velocity, self.nu, self.dt,
+                                      source=source)
+            return out
+        u = self.speed(form)
         if stage is None:
-            self.ctx.euler_step(self.phis[0], out[0], _kind(scheme), u, self.nu, self.dt)
+            self.ctx.euler_step(self.phis[0], out[0], _kind(scheme), u, self.nu, self.dt, source=source)
         else:
-            self.ctx.rk_stage(self.phis[0], self.phi0[0], out[0], stage[0], stage[1], _kind(scheme), u, self.nu, self.dt)
+            self.ctx.rk_stage(self.phis[0], self.phi0[0], out[0], stage[0], stage[1], _kind(scheme), u, self.nu, self.dt, source=source)
         return out
 
     def cpu(self, scheme, form, stage):

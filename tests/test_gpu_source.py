@@ -9,7 +9,9 @@ order 3.  Meshes: the smallest on which k_sf / k_sfq can still go wrong -- whole
 fp32 nodes per row), n1 = 13 (a partial row block) and n1 = 14 (what BC on load accepts at two and four rows per wave), n0 =
 7 and 9 with the chunk cap at 1, 2 and 3 (every remainder of the chunk length mod 4, one chunk with both faces, uneven
 chunks) -- one of n1 = 4 (one row per wave), one with a periodic axis 0 (the unfused stage; k_sfq declines it), and the generic
-kernel's: odd rows in 3-D, 2-D, 1-D.  The fixed-point test catches a source added in the wrong place, with the wrong sign or
+kernel's: odd rows in 3-D, 2-D, 1-D.  (Smallest for the source term itself; the row-count, row-length and periodic-axis edges of the
+kernels -- n1 from 4 to 36, rows of 2 * VEC to 264 nodes, a periodic axis 1 or 2, all-Neumann faces, long chunks under the rule
+itself -- are swept for the SRC instantiations in tests/test_gpu_chunks_terms.py.)  The fixed-point test catches a source added in the wrong place, with the wrong sign or
 read at the wrong cell: S = -(nu lap - adv)(phi*) makes phi* a fixed point bit for bit.
 """
 import ctypes as C

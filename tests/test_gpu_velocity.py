@@ -7,7 +7,9 @@ BITS: on both kernels, for the three Div limiters, scalar and field velocities o
 swapped axis cannot pass), Dirichlet and mixed faces, no source / a source field / a scalar source, the Euler step and both
 fused stages of order 3.  Meshes as tests/test_gpu_source.py: whole 16-byte rows and two k tiles (132 fp64 / 260 fp32 nodes per
 row), n1 = 13 / 14, n0 = 7 / 9 with the chunk cap at 1, 2, 3; the generic kernel's odd rows in 3-D, 2-D, 1-D; a periodic axis
-0.  The exact shift needs no reference at all: with dx = dt = 1 and u = +-e_a one upwind step moves small integers by one node.
+0.  (The row-count, row-length and periodic-axis edges of the two-row VEL kernels -- n1 = 5 .. 36 with 8 / 9 / 16 / 17 among them,
+rows of 2 * VEC to 264 nodes, a periodic axis 1 or 2, all-Neumann faces, long chunks -- are swept in
+tests/test_gpu_chunks_terms.py.)  The exact shift needs no reference at all: with dx = dt = 1 and u = +-e_a one upwind step moves small integers by one node.
 """
 import ctypes as C
 import os

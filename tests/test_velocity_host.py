@@ -55,6 +55,50 @@ def test_equal_components_are_the_single_speed(n, dtype, limiter):
                        S.march(phi, one, 0.05, 1e-3, 2, mesh, bcs, limiter, 3, src))
 
 
+# the eight BC sets and the mesh shapes of tests/test_gpu_chunks.py / test_gpu_chunks_terms.py, which use BOTH references
+_D, _N, _S, _P = "dirichlet", "neumann", "symmetry", "periodic"
+CHUNK_BCS = {
+    "NEUSYM": ([0.0, 0.0, None, None, None, None], [_N, _N, _S, _S, _S, _S]),
+    "ALLNEU": ([0.3, -0.2, 0.1, 0.0, -0.4, 0.25], [_N] * 6),
+    "MIXED": ([0.5, 0.1, None, 1.0, -0.3, None], [_D, _N, _S, _D, _N, _S]),
+    "ALLDIR": ([0.0, 1.0, 0.25, -0.5, 2.0, 0.0], [_D] * 6),
+    "YPER": ([0.5, 0.1, None, None, -0.3, None], [_D, _N, _P, _P, _N, _S]),
+    "DIRPER": ([0.0, 1.0, None, None, None, None], [_D, _D, _P, _P, _P, _P]),
+    "XPER": ([None, None, 0.25, -0.5, 2.0, 0.0], [_P, _P, _D, _D, _D, _D]),
+    "ALLPER": ([None] * 6, [_P] * 6),
+}
+
+
+@pytest.mark.parametrize("limiter", ["upwind", "quick", "none"])
+@pytest.mark.parametrize("dtype", ["double", "single"])
+def test_the_two_references_agree_on_the_chunk_test_meshes(dtype, limiter):
+    """with a source field, a stage of velocity_ref with three equal components is the stage of source_ref, bit for bit and
+    finite: on the eight BC sets and the row counts / row lengths of the chunk tests (eight-node rows, one- and two-tile rows),
+    so that both references are defined on every input those tests hand them"""
+    tdt = torch.float64 if dtype == "double" else torch.float32
+    ran = 0
+    for n in ([5, 19, 36], [9, 5, 32], [6, 6, 32], [7, 8, 8], [13, 9, 132 if dtype == "double" else 260]):
+        for name, (vals, types) in CHUNK_BCS.items():
+            if limiter == "none" and any(t in (_N, _S) for t in types):
+                continue                                    # central Div is refused on neumann / symmetry faces
+            mesh = O.OMesh([0.0] * 3, [1.0] * 3, n, dtype)
+            bcs = O.make_bcs(mesh, O.mixed_cfg(list(vals), list(types), O.FACES[:6]))
+            g = torch.Generator().manual_seed(17)
+            phi, phi0 = (torch.rand((1, *n), generator=g, dtype=torch.float64).to(tdt) for _ in range(2))
+            O.bc_fill(phi, bcs)
+            O.bc_fill(phi0, bcs)
+            U = torch.randn((1, *n), generator=g, dtype=torch.float64).to(tdt)
+            src = (3.0 * torch.randn((1, *n), generator=g, dtype=torch.float64)).to(tdt)
+            dx = 1.0 / (max(n) - 1)
+            nu, dt = 1e-3, 0.2 * min(dx * dx / 6e-3, dx / 1.3)
+            for u_vel, u_one in (([-0.8] * 3, -0.8), ([U[0]] * 3, U)):
+                a = R.rk_stage(phi, phi0, 0.75, 0.25, u_vel, nu, dt, mesh, bcs, limiter, src)
+                b = S.rk_stage(phi, phi0, 0.75, 0.25, u_one, nu, dt, mesh, bcs, limiter, src)
+                assert bool(torch.isfinite(a).all()) and torch.equal(a, b), (n, name)
+                ran += 1
+    assert ran == (40 if limiter == "none" else 80)
+
+
 @pytest.mark.parametrize("n,dtype", [([7, 9, 12], "single"), ([7, 9, 12], "double"), ([17, 12], "double")],
                          ids=["3d_f32", "3d_f64", "2d_f64"])
 def test_upwind_is_the_oracle_on_the_stacked_field(n, dtype):
