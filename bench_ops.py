@@ -4,7 +4,8 @@ contract; bench.py is).  One JSON line per workload: explicit Laplacian apply, t
 adv-diff Euler march (BASELINE config 4), the SSP Runge-Kutta march beside its unfused composition, the self-advected
 march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step composition, the marches with a source term
 (--sections source) beside the three-launch workaround and the generic kernel, the marches in a velocity field (--sections
-velocity) beside the one-speed marches and the generic kernel, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+velocity) beside the one-speed marches and the generic kernel, the momentum march of a vector field (--sections momentum)
+beside three scalar marches in three frozen fields, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -62,7 +63,9 @@ def main():
                          "which a library without the source term can run), velocity (euler_march and rk_march order 3 with a "
                          "velocity of three equal scalars and of three fields, each on k_sf and with fastpath 0, beside the scalar-speed "
                          "and speed-tensor marches; not in the default list; velocity_baseline: the no-velocity rows alone, which a "
-                         "library without the velocity entry points can run), small (the reference's "
+                         "library without the velocity entry points can run), momentum (momentum_march orders 1 and 3: the default, "
+                         "vself 0, fastpath 0; not in the default list; momentum_baseline: the yardstick alone, three scalar rk_march "
+                         "calls in three velocity fields, which a library without pa_momentum_march can run), small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -116,6 +119,8 @@ def main():
         source_rows(q, emit, with_source="source" in sections)
     if sections & {"velocity", "velocity_baseline"}:
         velocity_rows(q, emit, with_velocity="velocity" in sections)
+    if sections & {"momentum", "momentum_baseline"}:
+        momentum_rows(q, emit, with_momentum="momentum" in sections)
     solver_rows(q, emit, sections)
 
 
@@ -401,6 +406,85 @@ def velocity_rows(q, emit, with_velocity=True):
         ctx.set_option("fastpath", 1)
         ctx.set_option("bcl", 1)
         del mesh, start, U, V3
+        torch.cuda.empty_cache()
+
+
+def momentum_rows(q, emit, with_momentum=True):
+    """``momentum_march`` -- a vector field that advects itself, one launch per stage and component (pa_momentum_march) --
+    upwind, config-4 BC types, fp32, orders 1 and 3 (20 steps per call, ms per STEP): the default (k_sf VEL 3), "vself": 0
+    (the aliased VEL 2 instantiations) and "fastpath": 0 (the generic kernel).  The yardstick: three scalar ``rk_march`` calls,
+    one per component, in three FROZEN velocity fields (VEL 2) -- what a user could run before, and all a library without
+    pa_momentum_march can run (momentum_baseline).  Variants are timed in turn, three rounds; "ms" is the median.  Passes per
+    launch: 2 + 2 speed fields (VEL 3; 3 for VEL 2 and the generic kernel, which re-read the target as a speed), + 1 for phi0
+    in a stage."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.march import rk_march
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    types = ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"]
+    bcs = mixed_bcs([0.0, 0.0, None, None, None, None], types)
+    vbcs = mixed_bcs([[0.0, 0.0, 0.0], [0.0, 0.0, 0.0], None, None, None, None], types)
+    cfg = {"div": {"limiter": "upwind"}}
+    nu, steps = 1e-3, 20
+    for n in ([128] if q else [256, 512]):
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", "single")
+        ctx = context_for(mesh)
+        dx = mesh.dx_list[0]
+        dt = 0.2 * min(dx * dx / (6 * nu), dx / 1.0)
+        V3 = torch.stack([0.5 + 0.5 * torch.sin(3.0 * mesh.X) * torch.cos(2.0 * mesh.Y), 0.8 * torch.cos(2.0 * mesh.Z),
+                          -0.6 * torch.sin(mesh.X + mesh.Y)]).contiguous()
+        reps = 3 if n <= 256 else 1
+
+        def momentum(order):
+            from pyapes_amd.solver.march import momentum_march
+
+            def run():
+                U = Field("U", 3, mesh, {"domain": vbcs, "obstacle": None})
+                U.set_var_tensor(V3.clone())
+                U.apply_bcs()
+                ms = timed(lambda: momentum_march(U, nu, dt, steps, cfg, order=order), reps, warm=1) / steps
+                assert bool(torch.isfinite(U()).all())
+                return ms
+            return run
+
+        def three_scalar_marches(order):
+            def run():
+                phis = []
+                for c in range(3):
+                    phi = Field("phi", 1, mesh, {"domain": bcs, "obstacle": None})
+                    phi.set_var_tensor(V3[c:c + 1].clone())
+                    phi.apply_bcs()
+                    phis.append(phi)
+                vel = (V3[0], V3[1], V3[2])
+                ms = timed(lambda: [rk_march(phi, vel, nu, dt, steps, cfg, order=order) for phi in phis], reps, warm=1) / steps
+                assert all(bool(torch.isfinite(phi()).all()) for phi in phis)
+                return ms
+            return run
+
+        for order in (1, 3):
+            launches = 3 * order
+            stage_reads = 3 * (order - 1)
+            variants = [("yardstick: three rk_march in three frozen fields", three_scalar_marches(order), {"fastpath": 1}, 5 * launches + stage_reads)]
+            if with_momentum:
+                variants += [("momentum_march", momentum(order), {"fastpath": 1, "vself": 1}, 4 * launches + stage_reads),
+                             ("momentum_march, vself 0", momentum(order), {"fastpath": 1, "vself": 0}, 5 * launches + stage_reads),
+                             ("momentum_march, fastpath 0", momentum(order), {"fastpath": 0, "vself": 1}, 5 * launches + stage_reads)]
+            rounds = {v[0]: [] for v in variants}
+            for _ in range(3):
+                for vname, run, opts, _ in variants:
+                    for k, v in opts.items():
+                        if k != "vself" or with_momentum:
+                            ctx.set_option(k, v)
+                    rounds[vname].append(run())
+            yard = sorted(rounds[variants[0][0]])[1]
+            for vname, _, opts, passes in variants:
+                ms = sorted(rounds[vname])[1]
+                emit(f"order {order} ({steps} steps per call) {n}^3 f32 upwind, {vname} (config 4 BC types)", n ** 3, ms, passes, 4,
+                     {"ms_rounds": rounds[vname], "over_yardstick": ms / yard, "options": opts})
+        ctx.set_option("fastpath", 1)
+        del mesh, V3
         torch.cuda.empty_cache()
 
 

@@ -106,7 +106,9 @@ int pa_ctx_set_option(pa_ctx* ctx, const char* name, int value);
  * solver), "comm" / "slab_fold" (read back by the slab driver: library-side RCCL loop, folded sequence), "comm_overlap"
  * (-1 auto), "comm_timeout" (s), "roctx" (process-wide), "chunks" N > 0 = at most N axis-0 chunks in k_sf / k_sfq / k_cg3d (a cap behind
  * their rule, which on small meshes gives one plane per chunk; same bits in the single-field kernels, another grouping of
- * the partial sums in the solver phases; tests/test_gpu_chunks.py), "sf" 2 / 4 = k_sf with that many rows per wave.
+ * the partial sums in the solver phases; tests/test_gpu_chunks.py), "sf" 2 / 4 = k_sf with that many rows per wave,
+ * "vself" 0 = pa_momentum_march's upwind step on the VEL 2 instantiations of k_sf with the own component's pointer aliased into
+ * the input instead of VEL 3 (same bits; A/B runs).
  * pa_ctx_get_option reads a value back. */
 int pa_ctx_get_option(const pa_ctx* ctx, const char* name, int* value);
 /* Accounts of the online placement search of this ctx, out[10]: state (-1 off, 0 not begun / arrays too small,
@@ -318,6 +320,34 @@ int pa_rk_stage_vel(pa_ctx* ctx, const void* phi, const void* phi0, void* out, d
                     const pa_velocity* vel, double nu, double dt, const pa_source* src);
 int pa_rk_march_vel(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, const pa_velocity* vel, double nu,
                     double dt, int64_t nsteps, int* final, const pa_source* src);
+
+/* ---- momentum: the SSP Runge-Kutta march of a VECTOR field that advects itself,
+ *     dU_c/dt = nu lap(U_c) - (U . grad) U_c + S_c          c = 0 .. ncomp-1,   ncomp == the mesh dimension (2 or 3).
+ * E(V)_c is the velocity step above applied to the scalar V_c with the velocity (V_0, .., V_{d-1}) -- all components of the STAGE
+ * INPUT V -- followed by the ordered BC fill with component c's face values; a stage is B_c( c0*U0_c + c1*E(V)_c ) and every
+ * stage is advected by its own input, as pa_rk_march_self does for a scalar.  All components of a stage are computed from the
+ * same input vector (input and output are distinct buffers).  `frozen` != NULL: every component is transported by that FROZEN
+ * velocity instead (Oseen form) -- ncomp scalar pa_rk_march_vel marches in one call, the same bits.
+ * U, w1, w2: contiguous (ncomp, *n) buffers; order 1 uses U and w1 only; *final = 0, 1, 2 names the one with the result.
+ * src: NULL or ncomp entries (has == 0: none for that component), frozen for the call.  The BC list bound by pa_bc_set gives
+ * the types, the order and dxf; bcv[c] replaces `value` and `face_vals` of every face for component c's launches and fills
+ * (indexed like pa_bc_set's `face`; entries of faces without a BC are not read).  On return -- also on error -- the bound
+ * list is what it was before the call.
+ *     PA_E_ARG    ncomp != the mesh dimension, a 1-D mesh; buffers that alias or overlap; a frozen velocity field, a source
+ *                 field or a BC face array that overlaps a buffer; PA_OP_DIV_UPWIND_COMPAT; an axisymmetric mesh
+ *     PA_E_STATE  slab mode
+ * and the context stays usable.  Kernels: per stage and component one launch (the step is bound by instruction issue and
+ * registers: three stencils in one kernel would halve the waves in flight).  Upwind on whole 16-byte rows, 3-D, n1 > 4, no
+ * periodic axis 0: k_sf<..., VEL 3>, which takes the speed of the target's own axis from the centre operand the row holds --
+ * two speed fields read at the cell instead of three; option "vself" 0 runs the VEL 2 instantiations with the own component's
+ * pointer aliased into the input (same bits).  Everything else -- QUICK, central, 2-D, odd rows -- the generic kernel. */
+typedef struct {
+  double value[6];       /* per face: the scalar face value, used when vals[face] == NULL */
+  const void* vals[6];   /* per face: the face array or NULL */
+} pa_bc_values;
+int pa_momentum_march(pa_ctx* ctx, void* U, void* w1, void* w2, int ncomp, int order, int div_kind,
+                      const pa_velocity* frozen, double nu, double dt, int64_t nsteps, int* final, const pa_source* src,
+                      const pa_bc_values* bcv);
 
 /* ---- vector steps for a host-stepped solver loop (pyapes_amd/solver/host_stepped.py: BC callables that read the iterate
  * make the reference's loop come back to Python for every face of every fill, bcs.py:200-253; the loop's AXPYs and dot

@@ -105,6 +105,8 @@ struct Cg3dArgs {
   // (VEL 1) or three fields read at the cell (VEL 2); behind everything else for the same reason
   const T* vel_f[3];
   T vel_v[3];
+  // VEL 3 (pa_sf_vself.hip): the internal axis whose speed field IS the field `d` -- its speed is the centre operand
+  int vel_own;
 };
 
 __device__ __forceinline__ int pa_xcd_remap(int b, int nb) {

@@ -334,6 +334,7 @@ int pa_ctx_set_option(pa_ctx* c, const char* name, int value) {
   if (!strcmp(name, "fastpath")) c->fastpath = value != 0;      // tiled kernels (else the generic ones)
   else if (!strcmp(name, "sf")) c->sf = (value == 2 || value == 4) ? value : (value != 0);   // k_sf (else k_cg3d's single-field phases; 2 / 4: that many rows per wave, tests)
   else if (!strcmp(name, "chunks")) c->chunks = value < 0 ? 0 : value;   // cap of the axis-0 chunk count of k_sf / k_sfq / k_cg3d (0: their rule alone; tests)
+  else if (!strcmp(name, "vself")) c->vself = value != 0;   // pa_momentum_march: VEL 3 (0: the aliased VEL 2 instantiations, same bits; A/B runs)
   else if (!strcmp(name, "sfq")) c->sfq = value < 0 ? 0 : value;   // k_sfq for QUICK (0: the generic Euler kernel; 2 / 4: that many rows per wave, A/B runs)
   else if (!strcmp(name, "fold")) c->fold = value != 0;         // scalar steps in the next kernel's prologue
   else if (!strcmp(name, "resident")) c->resident = value != 0; // small meshes: one cooperative launch per solve
@@ -370,7 +371,7 @@ int pa_ctx_set_option(pa_ctx* c, const char* name, int value) {
 int pa_ctx_get_option(const pa_ctx* c, const char* name, int* value) {
   if (!c || !name || !value) return PA_E_ARG;
   const struct { const char* n; int v; } tab[] = {
-      {"fastpath", c->fastpath}, {"sf", c->sf}, {"sfq", c->sfq}, {"chunks", c->chunks}, {"fold", c->fold}, {"resident", c->resident}, {"bcl", c->bcl}, {"pitch", c->pitch},
+      {"fastpath", c->fastpath}, {"sf", c->sf}, {"sfq", c->sfq}, {"vself", c->vself}, {"chunks", c->chunks}, {"fold", c->fold}, {"resident", c->resident}, {"bcl", c->bcl}, {"pitch", c->pitch},
       {"place", c->place}, {"resident_coop", c->resident_coop}, {"bc_path", c->bc_path}, {"bicg_pfold", c->bicg_pfold}, {"bicg_srv", c->bicg_srv}, {"jac_alt", c->jac_alt},
       {"rhs_full", c->rhs_full}, {"comm", c->opt_comm}, {"slab_fold", c->opt_slab_fold}, {"comm_overlap", c->comm_overlap},
       {"comm_timeout", c->comm_timeout}, {"place_blocks", c->ps.blocks}};

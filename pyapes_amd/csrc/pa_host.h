@@ -191,6 +191,7 @@ struct pa_ctx {
   int fastpath = 1;
   int sfq = 1;                   // option "sfq": k_sfq for the QUICK Euler step / stage (0: the generic k_euler; 2 / 4: rows per wave forced); pa_sfq_kernel.h
   int sf = 1;                    // option "sf": k_sf for the Div-carrying single-field operations (0: k_cg3d's phases; 2 / 4: rows per wave forced, pa_sf_kernel.h sf_rows_per_wave)
+  int vself = 1;                 // option "vself": pa_momentum_march's upwind step on k_sf's VEL 3 instantiations (0: VEL 2 with the own component's pointer aliased into the input; same bits)
   int chunks = 0;                // option "chunks": N > 0 caps the axis-0 chunk count of k_sf / k_sfq / k_cg3d behind their rule (0: the rule alone)
   int resident = 1;              // small meshes: the whole CG / Jacobi solve in one cooperative launch (pa_resident.hip)
   // 1: hipLaunchCooperativeKernel (the runtime guarantees co-residency).  0: a plain launch of the same grid, which
@@ -310,10 +311,11 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
                     const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0,    // phi0: the stage c0 phi0 + c1 E(phi) of pa_rk_stage
                     const pa_source* src = nullptr);   // src: the source term (pa_*_src) or null; k_sf's SRC instantiations or 0
 // the upwind Euler step / stage with a velocity (pa_*_vel; vel indexed by INTERNAL axis) on k_sf's VEL instantiations
-// (pa_sf_vel.hip): blocks launched, 0 when k_sf does not take the launch (the generic k_euler then runs)
+// (pa_sf_vel.hip): blocks launched, 0 when k_sf does not take the launch (the generic k_euler then runs).  own >= 0
+// (pa_momentum_march): vel->field[own] IS phi.p -- the VEL 3 instantiations (pa_sf_vself.hip) unless option "vself" is 0
 template <typename T>
 int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_velocity* vel, double nu, double dt, const T* phi0,
-                        double c0, double c1, const pa_source* src);
+                        double c0, double c1, const pa_source* src, int own = -1);
 template <typename T>
 int pa_tile3d_jacobi(pa_ctx* c, const DevEq<T>& E, Vec<T> x, const T* rhs, T* xnew, double omega, double* partials);
 template <typename T>

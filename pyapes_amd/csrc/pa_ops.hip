@@ -616,14 +616,18 @@ static int euler_bcl_t(pa_ctx* c, const T* in, T* out, int kind, double u, const
 // The Euler step (phi0 null) or the fused stage with a velocity (pa_*_vel), vel indexed by INTERNAL axis: k_sf's VEL
 // instantiations where pa_tile3d_euler_vel takes the launch, else the generic k_euler<..., VEL>; then the ordered BC fill.
 // A periodic face: the step, k_rk_combine in place, the fill -- as euler_t and for its reason.
+// own >= 0 (momentum_march_t): vel->field[own] is `in` itself -- the target is a component of the velocity.  Nothing on the way
+// needs the speed fields to be distinct from the field read through the stencil: cg3d_mode ORs the pointers for their alignment,
+// sf_applies does not look at them, and the kernels read every operand through plain (non-restrict) global loads; `out` alone is
+// written, and it is a buffer of its own.
 template <typename T>
 static int euler_vel_t(pa_ctx* c, const T* in, T* out, int kind, const pa_velocity* vel, double nu, double dt,
-                       const T* phi0, double c0, double c1, const pa_source* src) {
+                       const T* phi0, double c0, double c1, const pa_source* src, int own = -1) {
   if (phi0) {
     bool periodic = false;
     for (int f = 0; f < 6; ++f) periodic = periodic || (c->G.act[f >> 1] && c->bc[f].type == PA_BC_PERIODIC);
     if (periodic) {
-      if (int rc = euler_vel_t<T>(c, in, out, kind, vel, nu, dt, nullptr, 0.0, 0.0, src)) return rc;
+      if (int rc = euler_vel_t<T>(c, in, out, kind, vel, nu, dt, nullptr, 0.0, 0.0, src, own)) return rc;
       if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
       hipLaunchKernelGGL(k_rk_combine<T>, dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, out, phi0, (T)c0,
                          (T)c1, c->G.ncell);
@@ -639,7 +643,7 @@ static int euler_vel_t(pa_ctx* c, const T* in, T* out, int kind, const pa_veloci
   pa_build_eq<T>(c, 1, &tl, El);
   Vec<T> pv = pa_vec_self<T>(c, in);
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
-  const int fr = pa_tile3d_euler_vel<T>(c, pv, out, kind, vel, nu, dt, phi0, c0, c1, src);
+  const int fr = pa_tile3d_euler_vel<T>(c, pv, out, kind, vel, nu, dt, phi0, c0, c1, src, own);
   if (fr < 0) {
     if (c->profile) pa_profile_stop(c, 0);
     return fr;
@@ -691,6 +695,54 @@ static int rk_march_vel_t(pa_ctx* c, T* b0, T* b1, T* b2, int order, int kind, c
   }
   *final = base;
   return PA_OK;
+}
+
+// pa_momentum_march: rk_march_vel_t's rotation over (ncomp, ncell) buffers.  A stage computes every component from the SAME
+// input vector: component q of `in` goes to component q of `out` with component q's BC values in the bound list (types, order
+// and dxf stay), advected by the frozen velocity `fz` or, fz null, by the input vector itself -- internal axis ia carries
+// component ia - (3 - ndim).  The bound list's values are restored on every way out.
+template <typename T>
+static int momentum_march_t(pa_ctx* c, T* b0, T* b1, T* b2, int ncomp, int order, int kind, const pa_velocity* fz, double nu,
+                            double dt, int64_t nsteps, int* final, const pa_source* src, const pa_bc_values* bcv) {
+  const double st2[1][2] = {{0.5, 0.5}};
+  const double st3[2][2] = {{3.0 / 4.0, 1.0 / 4.0}, {1.0 / 3.0, 2.0 / 3.0}};
+  const double (*st)[2] = order == 2 ? st2 : st3;
+  const int64_t nc = c->G.ncell;
+  const int sh = 3 - c->ndim;
+  HostBC saved[6];
+  for (int f = 0; f < 6; ++f) saved[f] = c->bc[f];
+  auto stage = [&](const T* in, T* out, const T* phi0, double c0, double c1) -> int {
+    pa_velocity vi;
+    if (fz) vi = *fz;
+    else {
+      memset(&vi, 0, sizeof(vi));
+      vi.has = 1;
+      for (int a = 0; a < ncomp; ++a) vi.field[a + sh] = in + a * nc;
+    }
+    for (int q = 0; q < ncomp; ++q) {
+      for (int f = 0; f < 2 * c->ndim; ++f) { c->bc[f + 2 * sh].value = bcv[q].value[f]; c->bc[f + 2 * sh].vals = bcv[q].vals[f]; }
+      const pa_source* sq = (src && src[q].has) ? &src[q] : nullptr;
+      if (int rc = euler_vel_t<T>(c, in + q * nc, out + q * nc, kind, &vi, nu, dt, phi0 ? phi0 + q * nc : nullptr, c0, c1, sq,
+                                  fz ? -1 : q + sh))
+        return rc;
+    }
+    return PA_OK;
+  };
+  T* buf[3] = {b0, b1, b2};
+  int base = 0, wa = 1, wb = 2, rc = PA_OK;
+  for (int64_t s = 0; s < nsteps && !rc; ++s) {
+    rc = stage(buf[base], buf[wa], nullptr, 0.0, 0.0);
+    int cur = wa, free_ = wb;
+    for (int q = 0; q < order - 1 && !rc; ++q) {
+      rc = stage(buf[cur], buf[free_], buf[base], st[q][0], st[q][1]);
+      std::swap(cur, free_);
+    }
+    const int old = base;
+    base = cur; wa = old; wb = free_;
+  }
+  for (int f = 0; f < 6; ++f) c->bc[f] = saved[f];
+  if (!rc) *final = base;
+  return rc;
 }
 
 // ---- vector steps of the host-stepped solver loops (pyapes_amd/solver/host_stepped.py) ------------------------------
@@ -1016,6 +1068,67 @@ int pa_rk_march_vel(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kin
   return c->dtype == PA_F64
              ? rk_march_vel_t<double>(c, (double*)phi, (double*)w1, (double*)w2, order, kind, &vi, nu, dt, nsteps, final, src)
              : rk_march_vel_t<float>(c, (float*)phi, (float*)w1, (float*)w2, order, kind, &vi, nu, dt, nsteps, final, src);
+}
+
+int pa_momentum_march(pa_ctx* c, void* U, void* w1, void* w2, int ncomp, int order, int kind, const pa_velocity* frozen, double nu,
+                      double dt, int64_t nsteps, int* final, const pa_source* src, const pa_bc_values* bcv) {
+  if (!c || !c->grid_set) return PA_E_STATE;
+  const char* who = "pa_momentum_march";
+  if (order < 1 || order > 3) { pa_set_err(c, "%s: order %d (1, 2 or 3)", who, order); return PA_E_ARG; }
+  if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "%s: single GPU only (no slabs)", who); return PA_E_STATE; }
+  if (c->coord != PA_COORD_XYZ) { pa_set_err(c, "%s: for xyz meshes (no axisymmetric rows)", who); return PA_E_ARG; }
+  if (c->ndim < 2 || ncomp != c->ndim) {
+    pa_set_err(c, "%s: one component per mesh axis on a 2-D or 3-D mesh (%d components, %d axes)", who, ncomp, c->ndim);
+    return PA_E_ARG;
+  }
+  if (kind == PA_OP_DIV_UPWIND_COMPAT) { pa_set_err(c, "%s: the literal upwind form takes no velocity", who); return PA_E_ARG; }
+  int rc = check_div_kind(c, kind, who);
+  if (rc) return rc;
+  if (order == 1) w2 = nullptr;
+  if (!U || !w1 || !final || !bcv || nsteps < 0 || (order > 1 && !w2)) {
+    pa_set_err(c, "%s: buffers (two for order 1, else three), a place for the result index, BC values and nsteps >= 0 are needed", who);
+    return PA_E_ARG;
+  }
+  const size_t cbytes = (size_t)c->G.ncell * (c->dtype == PA_F64 ? 8 : 4), vbytes = cbytes * (size_t)ncomp;
+  const void* bufs[3] = {U, w1, w2};
+  auto hits = [&](const void* p, size_t bytes) {   // [p, p + bytes) against the three vector buffers
+    for (const void* b : bufs)
+      if (b && p && (const char*)p < (const char*)b + vbytes && (const char*)b < (const char*)p + bytes) return true;
+    return false;
+  };
+  for (int i = 0; i < 3; ++i)
+    for (int j = i + 1; j < 3; ++j)
+      if (bufs[i] && bufs[j] && (const char*)bufs[i] < (const char*)bufs[j] + vbytes && (const char*)bufs[j] < (const char*)bufs[i] + vbytes) {
+        pa_set_err(c, "%s: the buffers must not overlap", who);
+        return PA_E_ARG;
+      }
+  pa_velocity vi;
+  if (frozen) {
+    if (!frozen->has) { pa_set_err(c, "%s: a frozen velocity with has == 0", who); return PA_E_ARG; }
+    memset(&vi, 0, sizeof(vi));
+    vi.has = 1;
+    for (int a = 0; a < c->ndim; ++a) {
+      vi.value[a + 3 - c->ndim] = frozen->value[a];
+      vi.field[a + 3 - c->ndim] = frozen->field[a];
+      if (hits(frozen->field[a], cbytes)) { pa_set_err(c, "%s: a frozen velocity field must not overlap a buffer of the call", who); return PA_E_ARG; }
+    }
+  }
+  if (src)
+    for (int q = 0; q < ncomp; ++q)
+      if (src[q].has && hits(src[q].field, cbytes)) { pa_set_err(c, "%s: a source field must not overlap a buffer of the call", who); return PA_E_ARG; }
+  {
+    const int64_t n[3] = {c->G.n0, c->G.n1, c->G.n2};
+    for (int q = 0; q < ncomp; ++q)
+      for (int f = 0; f < 2 * c->ndim; ++f) {
+        const size_t fbytes = cbytes / (size_t)n[(f >> 1) + 3 - c->ndim];
+        if (hits(bcv[q].vals[f], fbytes)) { pa_set_err(c, "%s: a BC face array must not overlap a buffer of the call", who); return PA_E_ARG; }
+      }
+  }
+  PaRange range_("pyapes momentum march");
+  PA_HIP(c, hipSetDevice(c->device));
+  return c->dtype == PA_F64
+             ? momentum_march_t<double>(c, (double*)U, (double*)w1, (double*)w2, ncomp, order, kind, frozen ? &vi : nullptr, nu, dt, nsteps, final, src, bcv)
+             : momentum_march_t<float>(c, (float*)U, (float*)w1, (float*)w2, ncomp, order, kind, frozen ? &vi : nullptr, nu, dt, nsteps, final, src, bcv);
 }
 
 int pa_euler_step_src(pa_ctx* c, const void* in, void* out, int kind, double u, const void* u_field, double nu, double dt,

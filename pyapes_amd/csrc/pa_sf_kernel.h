@@ -118,14 +118,19 @@ template <> struct SfBits<double> {
 // (e.g. 105 -> 102), as the source term's flag once did.  2: three speed fields A.vel_f, read at
 // the cell only (upwind takes the speed at the node: no stencil reach, no halo) -- three 16-byte lane accesses per row and
 // plane, issued at the top of the plane beside phi0's and the source's, in front of the loads of plane q + 2, and used in that
-// plane; 3 * RJ * VEC more live registers for one plane.  Instantiated at two rows per wave (pa_sf_vel.hip).  The VEL = 0
-// instantiations are the code they were.
+// plane; 3 * RJ * VEC more live registers for one plane.  Instantiated at two rows per wave (pa_sf_vel.hip).  3: VEL 2 for a
+// target that is itself one of the three speed fields (pa_momentum_march: component c of a vector field advected by the vector):
+// the speed of internal axis A.vel_own (wave-uniform, 0..2) is the centre operand xc the row holds, as SELF takes uc = xc -- two
+// 16-byte lane accesses per row and plane instead of three and RJ * VEC fewer live registers; the two foreign fields and the
+// per-axis operand are picked by uniform selects on A.vel_own (no branch between a load and its use), read inside the plane's
+// lambda through A (nothing new in the capture lists).  Same bits as VEL 2 with vel_f[vel_own] == the field.  Two rows per wave
+// (pa_sf_vself.hip).  The VEL = 0 instantiations are the code they were.
 #ifndef PA_SF_USIGN
 #define PA_SF_USIGN 1
 #endif
 template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false, int VEL = 0>
 __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
-  static_assert(VEL == 0 || ((VEL == 1 || VEL == 2) && PHASE == 3 && KIND == 4 && !HASU && !SELF && !BCL && US == 0), "VEL: the upwind Euler step, no other speed");
+  static_assert(VEL == 0 || ((VEL == 1 || VEL == 2 || VEL == 3) && PHASE == 3 && KIND == 4 && !HASU && !SELF && !BCL && US == 0), "VEL: the upwind Euler step, no other speed");
   static_assert(!SELF || (PHASE == 3 && !HASU && US == 0), "SELF: the Euler step, no other speed");
   static_assert(!BCL || PHASE == 3, "BC on load: the Euler step");
   static_assert(!STG || PHASE == 3, "STG: the Euler step");
@@ -339,13 +344,23 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
         umiA[a] = (V)(u < (T)0 ? u : (T)0);
       }
     }
-    V Wv[VEL == 2 ? 3 : 1][VEL == 2 ? RJ : 1];   // VEL 2: the three speed fields of THIS plane, beside phi0's and the source's
+    V Wv[VEL == 2 ? 3 : (VEL == 3 ? 2 : 1)][VEL >= 2 ? RJ : 1];   // VEL 2: the three speed fields of THIS plane, beside phi0's and the source's
     if constexpr (VEL == 2) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         gcptr pw = (gcptr)((uintptr_t)A.vel_f[a] + (size_t)(unsigned)ii * pstride);
 #pragma unroll
         for (int jj = 0; jj < RJ; ++jj) Wv[a][jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(pw + off[jj]);
+      }
+    }
+    if constexpr (VEL == 3) {   // the two speed fields that are NOT the target: slot 0 the lower axis, slot 1 the upper (uniform selects)
+      const uintptr_t f0 = (uintptr_t)A.vel_f[0], f1 = (uintptr_t)A.vel_f[1], f2 = (uintptr_t)A.vel_f[2];
+      const uintptr_t w2[2] = {A.vel_own == 0 ? f1 : f0, A.vel_own == 2 ? f1 : f2};
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        gcptr pw = (gcptr)(w2[s] + (size_t)(unsigned)ii * pstride);
+#pragma unroll
+        for (int jj = 0; jj < RJ; ++jj) Wv[s][jj] = *reinterpret_cast<const V __attribute__((address_space(1)))*>(pw + off[jj]);
       }
     }
     // loads for later planes first: they fly during this plane's arithmetic
@@ -525,7 +540,16 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
                 V upa, uma;
                 if constexpr (VEL == 1) { upa = uplA[a]; uma = umiA[a]; }
                 else {
-                  const V ua = Wv[a][jj];
+                  V ua;
+                  if constexpr (VEL == 3) {   // the target's own axis: the centre operand, as SELF; else the slot of axis a
+                    const V wl = Wv[0][jj], wh = Wv[VEL == 3 ? 1 : 0][jj];
+                    const bool lower = a == 0 || (a == 1 && A.vel_own == 0);   // (a is a constant of the unrolled loop)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) {
+                      const T w = lower ? wl[v] : wh[v];
+                      ua[v] = A.vel_own == a ? xc[v] : w;
+                    }
+                  } else ua = Wv[a][jj];
 #pragma unroll
                   for (int v = 0; v < VEC; ++v) {
                     upa[v] = ua[v] > (T)0 ? ua[v] : (T)0;
@@ -672,7 +696,7 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg > 0) {
     --dbg;
     fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", SRC ? " (source)" : "", VEL ? " (velocity)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
+            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", SRC ? " (source)" : "", VEL == 3 ? (A.vel_own == 0 ? " (velocity, own 0)" : (A.vel_own == 1 ? " (velocity, own 1)" : " (velocity, own 2)")) : (VEL ? " (velocity)" : ""), A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
             sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>());
   }
   hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>), dim3(nblk), dim3(256), 0, c->stream, A);
@@ -775,6 +799,9 @@ int pa_sf_euler_src_bcl(pa_ctx* c, Cg3dArgs<T>& A, int rj, bool stage, bool self
 // rows per wave, with and without STG and SRC.  A translation unit of its own: pa_sf_vel.hip.
 template <typename T>
 int pa_sf_euler_vel(pa_ctx* c, Cg3dArgs<T>& A, bool stage, bool fields, bool source);
+// VEL 3: the target is the speed field of internal axis A.vel_own (pa_momentum_march).  Its own unit: pa_sf_vself.hip.
+template <typename T>
+int pa_sf_euler_vself(pa_ctx* c, Cg3dArgs<T>& A, bool stage, bool source);
 
 // can k_sf take this launch?  Full 16-byte vectors only (mode 1 of cg3d_mode), scalar coefficient.
 template <typename T, int PHASE>

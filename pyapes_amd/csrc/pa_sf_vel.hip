@@ -2,7 +2,8 @@
 // stage in a velocity field, one advection speed per mesh axis (pa_*_vel).  Three scalar speeds (VEL 1) or three speed fields
 // read at the cell (VEL 2), two rows per wave, with and without a source term.  Everything else with a velocity -- central,
 // QUICK, 1-D / 2-D meshes, odd rows, unaligned operands, a periodic axis 0, a mix of scalar and field components, n1 <= 4 --
-// runs the generic k_euler (pa_ops.hip): pa_tile3d_euler_vel returns 0 for it.
+// runs the generic k_euler (pa_ops.hip): pa_tile3d_euler_vel returns 0 for it.  A target that is itself one of the three speed
+// fields (pa_momentum_march, own >= 0) takes the VEL 3 instantiations of pa_sf_vself.hip under the same conditions.
 #include "pa_sf_kernel.h"
 
 template <typename T, int VEL, bool STG>
@@ -20,7 +21,7 @@ int pa_sf_euler_vel(pa_ctx* c, Cg3dArgs<T>& A, bool stage, bool fields, bool sou
 // vel: indexed by INTERNAL axis (euler_vel_t, pa_ops.hip).  Blocks launched, 0 when k_sf does not take the launch, < 0: error.
 template <typename T>
 int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_velocity* vel, double nu, double dt, const T* phi0,
-                        double c0, double c1, const pa_source* src) {
+                        double c0, double c1, const pa_source* src, int own) {
   if (kind != PA_OP_DIV_UPWIND || c->ndim != 3) return 0;
   const int nf = (vel->field[0] ? 1 : 0) + (vel->field[1] ? 1 : 0) + (vel->field[2] ? 1 : 0);
   if (nf != 0 && nf != 3) return 0;                  // a mix of scalar and field components
@@ -49,12 +50,15 @@ int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_veloci
     A.out_all = faces == 2 * c->ndim ? 1 : 0;
   }
   if (!sf_applies<T, 3>(c, A, mode)) return 0;
-  const int n = pa_sf_euler_vel<T>(c, A, phi0 != nullptr, nf == 3, src != nullptr);
+  A.vel_own = own;
+  const bool vself = own >= 0 && own < 3 && nf == 3 && c->vself && vel->field[own] == (const void*)phi.p;
+  const int n = vself ? pa_sf_euler_vself<T>(c, A, phi0 != nullptr, src != nullptr)
+                      : pa_sf_euler_vel<T>(c, A, phi0 != nullptr, nf == 3, src != nullptr);
   if (n > 0 && hipGetLastError() != hipSuccess) { pa_set_err(c, "k_sf Euler launch (velocity) failed"); return PA_E_HIP; }
   return n;
 }
 
 template int pa_sf_euler_vel<float>(pa_ctx*, Cg3dArgs<float>&, bool, bool, bool);
 template int pa_sf_euler_vel<double>(pa_ctx*, Cg3dArgs<double>&, bool, bool, bool);
-template int pa_tile3d_euler_vel<float>(pa_ctx*, Vec<float>, float*, int, const pa_velocity*, double, double, const float*, double, double, const pa_source*);
-template int pa_tile3d_euler_vel<double>(pa_ctx*, Vec<double>, double*, int, const pa_velocity*, double, double, const double*, double, double, const pa_source*);
+template int pa_tile3d_euler_vel<float>(pa_ctx*, Vec<float>, float*, int, const pa_velocity*, double, double, const float*, double, double, const pa_source*, int);
+template int pa_tile3d_euler_vel<double>(pa_ctx*, Vec<double>, double*, int, const pa_velocity*, double, double, const double*, double, double, const pa_source*, int);

@@ -312,6 +312,56 @@ class HipContext:
                                           None if ps is None else C.byref(ps)))
         return bufs[final.value]
 
+    def bc_values(self, var: Tensor, bcs: Sequence[Any], comp: int) -> tuple[Any, list[Tensor]]:
+        """``pa_bc_values`` of component ``comp`` -- every face's scalar and face array, resolved once -- and the arrays it
+        points into"""
+        bv = L.PaBcValues()
+        keep = []
+        for bc in bcs:
+            scalar, arr = bc.resolve(var, comp)
+            f = self.mesh.face_index(bc.bc_face)
+            bv.value[f] = float(scalar)
+            if arr is not None:
+                keep.append(arr)
+                bv.vals[f] = arr.data_ptr()
+        return bv, keep
+
+    def momentum_march(self, U: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int,
+                       vel: Sequence[float | Tensor] | None, nu: float, dt: float, nsteps: int,
+                       sources: Sequence[float | Tensor | None] | None, bcs: Sequence[Any]) -> Tensor:
+        """``pa_momentum_march``: the SSP Runge-Kutta march of the vector ``U`` ((dim, *nx), contiguous) advected by itself
+        (``vel`` None) or by a frozen velocity; ``sources``: None or one entry per component.  The BC list must be bound
+        (``bind_bcs(U, bcs, 0)``); the values of every component are resolved here, once.  Returns the tensor that holds
+        the final state."""
+        self.use_current_stream()
+        nd = self.mesh.dim
+        bufs = [U, w1] + ([] if w2 is None else [w2])
+        for t in bufs:
+            require_gpu(t, "momentum_march")
+            if t.dtype != self.dtype or not t.is_contiguous() or t.numel() != nd * self.mesh.N:
+                raise ValueError("pyapes_amd: momentum_march: contiguous (dim, *nx) buffers of the mesh dtype are needed")
+        pv, _kv = (None, None) if vel is None else self._velocity(vel, "momentum_march")
+        ps, _ks = None, []
+        if sources is not None:
+            ps = (L.PaSource * nd)()
+            for q, s in enumerate(sources):
+                one, kept = self._source(s, "momentum_march")
+                if one is not None:
+                    ps[q].has, ps[q].value, ps[q].field = 1, one.value, one.field
+                    _ks.append(kept)
+        bv = (L.PaBcValues * nd)()
+        _kb = []
+        for q in range(nd):
+            one, kept = self.bc_values(U, bcs, q)
+            bv[q] = one
+            _kb.append(kept)
+        self._keep["momentum"] = (_kv, _ks, _kb)   # what the enqueued launches still read
+        final = C.c_int(0)
+        self._rc(self.lib.pa_momentum_march(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2] if len(bufs) > 2 else None),
+                                            nd, int(order), kind, None if pv is None else C.byref(pv), float(nu), float(dt),
+                                            int(nsteps), C.byref(final), ps, bv))
+        return bufs[final.value]
+
     def euler_march(self, phi: Tensor, tmp: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
                     nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``nsteps`` explicit Euler steps enqueued back to back, ping-ponging phi <-> tmp; returns the

@@ -31,6 +31,15 @@ Per axis the scheme's own term is formed with that axis's component (DESIGN.md s
 advective form u . grad(phi) with the speed at the node, central in the conservative form with u_a at the axis's two
 neighbours.  The velocity is FROZEN for the whole call, like a speed tensor; ``source=`` composes with it.  Not with a velocity:
 slab and axisymmetric meshes, ``compat: True``, a component on ``phi``'s own storage (no self-advection by component).
+
+Momentum: ``momentum_step`` / ``momentum_march`` march a VECTOR field ``U`` with ``U.dim == mesh.dim >= 2`` that advects itself,
+    dU_c/dt = nu lap(U_c) - (U . grad) U_c + S_c,
+the momentum predictor of a projection step (DESIGN.md section 4 "Momentum").  Component c of a stage is the velocity step
+above applied to the scalar V_c with the velocity (V_0, .., V_{d-1}), all components of the stage's INPUT V, then the BC fill
+with component c's face values; every Runge-Kutta stage is advected by its own input and no component sees another
+component's output of the same stage.  ``u=`` a velocity transports every component by that frozen velocity instead (the
+linearised, Oseen form: ``mesh.dim`` scalar marches in one call); ``source=`` has one entry per component.  The four scalar
+entry points keep refusing vector targets.
 """
 from __future__ import annotations
 
@@ -327,3 +336,110 @@ def rk_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt
     if hasattr(phi, "_t"):
         phi.update_time(dt * nsteps)
     return phi
+
+
+class _Component:
+    """one component of a vector Field, as the scalar target ``_velocity_of`` / ``_source_of`` check against (a view of the
+    vector's storage: an entry that shares it is caught)"""
+
+    def __init__(self, U: Field):
+        self.mesh, self.dim, self._t = U.mesh, 1, U()[0:1]
+
+    def __call__(self) -> Tensor:
+        return self._t
+
+
+def _shares_storage(t: Any, p: Tensor) -> bool:
+    t = t() if isinstance(t, Field) else t
+    return isinstance(t, Tensor) and t.device == p.device and t.untyped_storage().data_ptr() == p.untyped_storage().data_ptr()
+
+
+def _momentum_args(U: Field, config: dict | None, order: int, u: Any, source: Any,
+                   what: str) -> tuple[int, list[float | Tensor] | None, list[float | Tensor | None] | None]:
+    """every check of ``momentum_step`` / ``momentum_march``, made before a device is touched; returns the Div kind, the frozen
+    velocity (None: ``U`` transports itself) and the per-component sources (None: no source)"""
+    if order not in SSP_STAGES:
+        raise ValueError(f"pyapes_amd: {what}: order {order!r} (1, 2 or 3)")
+    mesh = U.mesh
+    nd = mesh.dim
+    if nd < 2:
+        raise NotImplementedError(f"pyapes_amd: {what}: a 1-D mesh (a scalar that advects itself: rk_march(phi, phi, ...))")
+    if U.dim != nd:
+        raise NotImplementedError(f"pyapes_amd: {what}: a vector field with one component per mesh axis ({U.dim} for {nd})")
+    if getattr(mesh, "slab", None) is not None:
+        raise NotImplementedError(f"pyapes_amd: {what} on a slab mesh (single GPU only)")
+    if mesh.coord_sys == "rz":
+        raise NotImplementedError(f"pyapes_amd: {what} on an axisymmetric (rz) mesh")
+    cfg = (config or {}).get("div", {"limiter": "upwind"})
+    if bool(cfg.get("compat", False)):
+        raise NotImplementedError(f"pyapes_amd: {what} with compat: True (the reference's literal upwind form takes one speed)")
+    kind = div_kind(cfg.get("limiter", "upwind").lower(), False)
+    quick_mesh_check(kind, mesh, what)
+    comp = _Component(U)
+    vel = None
+    if u is not None:
+        entries = list(u) if isinstance(u, (tuple, list)) else [u]
+        if u is U or any(_shares_storage(e, U()) for e in entries):
+            raise NotImplementedError(f"pyapes_amd: {what}: u= on U's own storage (u=None is the field that transports itself; "
+                                      "a frozen velocity is a clone)")
+        vel = _velocity_of(comp, u, config, what)
+        if vel is None:
+            raise TypeError(f"pyapes_amd: {what}: u= is a velocity, one entry per mesh axis (a tuple / list, a "
+                            f"({nd}, *n) Tensor or a vector Field), or None")
+    srcs = None
+    if source is not None:
+        p = U()
+        if isinstance(source, Field):
+            if source.mesh is not mesh:
+                raise ValueError(f"pyapes_amd: {what}: the source Field lives on another mesh")
+            if source.dim != nd:
+                raise ValueError(f"pyapes_amd: {what}: the source Field has {source.dim} components, U {nd}")
+            source = source()
+        if isinstance(source, Tensor):
+            if tuple(source.shape) != tuple(p.shape):
+                raise ValueError(f"pyapes_amd: {what}: source shape {tuple(source.shape)}, expected {tuple(p.shape)}")
+            source = [source[c] for c in range(nd)]
+        if not isinstance(source, (tuple, list)):
+            raise TypeError(f"pyapes_amd: {what}: source is None, a list / tuple of {nd} entries, a ({nd}, *n) Tensor or a "
+                            f"vector Field (got {type(source).__name__})")
+        if len(source) != nd:
+            raise ValueError(f"pyapes_amd: {what}: the source has one entry per component ({len(source)} given, U has {nd})")
+        srcs = [_source_of(comp, e, what) for e in source]
+    return kind, vel, srcs
+
+
+def _momentum(U: Field, nu: float, dt: float, nsteps: int, config: dict | None, order: int, u: Any, source: Any,
+              what: str) -> Field:
+    kind, vel, srcs = _momentum_args(U, config, order, u, source, what)
+    require_gpu(U(), what)
+    ctx = context_for(U.mesh)
+    if not U().is_contiguous():
+        U.set_var_tensor(U().contiguous())
+    ctx.bind_bcs(U(), U.bcs, 0)
+    w1 = torch.empty_like(U())
+    w2 = None if order == 1 else torch.empty_like(U())
+    final = ctx.momentum_march(U(), w1, w2, order, kind, vel, nu, dt, nsteps, srcs, U.bcs)
+    if final.data_ptr() != U().data_ptr():
+        U.set_var_tensor(final)
+    return U
+
+
+def momentum_step(U: Field, nu: float, dt: float, config: dict | None = None, order: int = 3, *,
+                  u: Tensor | Field | tuple | list | None = None, source: Tensor | Field | tuple | list | None = None) -> Field:
+    """Advance the vector field ``U`` by one SSP Runge-Kutta step of ``order`` of the momentum equation (module docstring
+    "Momentum"); returns ``U``, whose time is not advanced (as ``rk_step``).  ``u`` None: ``U`` transports itself, every stage by
+    its own input; a velocity: every component is transported by it, frozen.  ``source``: None, one entry per component (each
+    what a scalar march takes), a ``(dim, *n)`` Tensor or a vector Field on the same mesh -- frozen, in every stage.  BC values
+    (callables included) are resolved once per call."""
+    return _momentum(U, nu, dt, 1, config, order, u, source, "momentum_step")
+
+
+def momentum_march(U: Field, nu: float, dt: float, nsteps: int, config: dict | None = None, order: int = 3, *,
+                   u: Tensor | Field | tuple | list | None = None, source: Tensor | Field | tuple | list | None = None) -> Field:
+    """``nsteps`` steps of ``momentum_step`` with no host work in between (one C-ABI call, ``pa_momentum_march``: per stage
+    and component one step kernel and its BC fill, over three vector buffers); ``U`` holds the final state and its time
+    advances by ``nsteps * dt``.  ``u``, ``source`` and the BC values are FROZEN for the whole call."""
+    U = _momentum(U, nu, dt, nsteps, config, order, u, source, "momentum_march")
+    if hasattr(U, "_t"):
+        U.update_time(dt * nsteps)
+    return U
