@@ -1,7 +1,7 @@
 // pa_core.hip -- host infrastructure of libpyapes_hip: context, scratch, grid / coordinate system / BC list /
 // equation state behind the C ABI declared in include/pyapes_hip.h.  gfx950 only.
 // The kernels live beside the host code that launches them: pa_bc.hip (BC fill), pa_ops.hip (generic
-// operators, explicit entry points), pa_cg.hip / pa_bicgstab.hip / pa_jacobi.hip (the CG / BiCGSTAB / Jacobi drivers
+// operators, explicit entry points), pa_march.hip (Euler step, Runge-Kutta stages, the marches), pa_cg.hip / pa_bicgstab.hip / pa_jacobi.hip (the CG / BiCGSTAB / Jacobi drivers
 // and their generic kernels) with pa_solver.hip (what they share), pa_cg3d*.hip (the tiled marching kernel), pa_rfp.hip,
 // pa_comm.hip.
 #include "pa_host.h"

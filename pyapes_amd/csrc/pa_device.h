@@ -150,7 +150,7 @@ __device__ __forceinline__ void pa_nbrs(const DevGeom& G, const Acc& a, int ax, 
 }
 
 // the neighbours at distance 2 (QUICK), wrap-around indices on every axis.  Axis 0 has no ghost planes at that distance:
-// the callers keep this off slabs (pa_ops.hip check_quick), so the rank's own planes are the whole axis.
+// the callers keep this off slabs (pa_ops.hip pa_check_div_kind), so the rank's own planes are the whole axis.
 template <typename T, class Acc>
 __device__ __forceinline__ void pa_nbrs2(const DevGeom& G, const Acc& a, int ax, int64_t i, int64_t j,
                                          int64_t k, T& xpp, T& xmm) {

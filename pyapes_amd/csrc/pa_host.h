@@ -234,6 +234,8 @@ int pa_scratch(pa_ctx* c, void** slot, size_t* cap, size_t bytes);
 void pa_refresh_geom(pa_ctx* c);
 int pa_bc_apply_any(pa_ctx* c, void* x);
 int pa_check_eq_applicable(pa_ctx* c);   // pa_ops.hip: Grad inside a solver equation is 1-D only
+// pa_ops.hip: the Div kind of an explicit call (pa_div, the steps and marches of pa_march.hip); `who` names the entry point in the messages
+int pa_check_div_kind(pa_ctx* c, int kind, const char* who = "pa_div");
 // pa_solver.hip: PA_OK (device selected) when the stepwise solve `kind` is live, else PA_E_STATE, error text naming `what`
 int pa_require_solve(pa_ctx* c, PaSolve kind, const char* what);
 int pa_cg_slab_mid(pa_ctx* c);                // pa_cg.hip: the step between the phases of a folded slab iteration
@@ -278,6 +280,21 @@ template <typename T>
 void pa_build_eq(const pa_ctx* c, int nterms, const pa_term* terms, DevEq<T>& E);
 template <typename T>
 Vec<T> pa_vec_self(const pa_ctx* c, const T* p);
+// the Laplacian alone as an equation: the rows of the Euler step's diffusion term, and what the tiled layer's geometry / mode
+// checks of the step and the gradient are made with
+template <typename T>
+static inline void pa_build_lap(const pa_ctx* c, DevEq<T>& E) {
+  pa_term t = {};
+  t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
+  pa_build_eq<T>(c, 1, &t, E);
+}
+// every face of the mesh has a BC: the fill behind a step kernel rewrites every node outside the interior set, so the kernel may
+// write its value at EVERY node (Cg3dArgs::out_all)
+static inline int pa_bc_on_every_face(const pa_ctx* c) {
+  int faces = 0;
+  for (int f = 0; f < 6; ++f) faces += (c->G.act[f >> 1] && c->bc[f].type != PA_BC_NONE) ? 1 : 0;
+  return faces == 2 * c->ndim ? 1 : 0;
+}
 
 // 3-D fast path (pa_cg3d.hip): return number of partial-sum rows written (> 0) when the
 // kernel ran, 0 when the configuration is not covered (caller falls back to the generic

@@ -12,10 +12,7 @@ template <typename T>
 int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt, int bcl,
                     const T* phi0, double c0, double c1, const pa_source* src) {
   DevEq<T> E;
-  pa_term t;
-  memset(&t, 0, sizeof(t));
-  t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
-  pa_build_eq<T>(c, 1, &t, E);
+  pa_build_lap<T>(c, E);
   const int mode = cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0, src ? src->field : nullptr});   // (a stage's phi0 and a source field count for the alignment)
   if (!mode) return 0;
   if (src && kind == PA_OP_DIV_UPWIND_COMPAT) return 0;   // no SRC instantiation of the literal form: generic kernel
@@ -29,11 +26,7 @@ int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const voi
   A.d = phi; A.out = out; A.aux = (const T*)u_field; A.u = (T)u; A.p0 = (T)nu; A.p1 = (T)dt; A.kind = kind;
   A.stg_phi0 = phi0; A.stg_c0 = (T)c0; A.stg_c1 = (T)c1;   // phi0 != null: the Runge-Kutta stage (STG instantiations)
   if (src) { A.src = (const T*)src->field; A.src_val = (T)src->value; }   // the SRC instantiations of k_sf
-  {  // the BC fill that follows the step kernel (euler_t) rewrites every face plane that has a BC
-    int faces = 0;
-    for (int f = 0; f < 6; ++f) faces += (c->G.act[f >> 1] && c->bc[f].type != PA_BC_NONE) ? 1 : 0;
-    A.out_all = faces == 2 * c->ndim ? 1 : 0;
-  }
+  A.out_all = pa_bc_on_every_face(c);   // the BC fill that follows the step kernel (step_t) rewrites every face plane that has a BC
   const bool sf = sf_applies<T, 3>(c, A, mode);
   if (src && !sf) return 0;   // k_cg3d's Euler phase takes no source: the generic kernel does
   // central self off k_sf: k_cg3d reads the speed at the cell only.  On a slab the generic kernel takes u's axis-0
@@ -111,10 +104,7 @@ int pa_tile3d_aop(pa_ctx* c, const DevEq<T>& E, Vec<T> x, T* y, int interior_onl
 template <typename T>
 int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd) {
   DevEq<T> E;
-  pa_term t;
-  memset(&t, 0, sizeof(t));
-  t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
-  pa_build_eq<T>(c, 1, &t, E);
+  pa_build_lap<T>(c, E);
   const int mode = cg3d_mode<T>(c, E, {x.p, y, x.glo, x.ghi});
   if (!mode || nd != c->ndim) return 0;
   Cg3dArgs<T> A;

@@ -2,7 +2,7 @@
 // stage in a velocity field, one advection speed per mesh axis (pa_*_vel).  Three scalar speeds (VEL 1) or three speed fields
 // read at the cell (VEL 2), two rows per wave, with and without a source term.  Everything else with a velocity -- central,
 // QUICK, 1-D / 2-D meshes, odd rows, unaligned operands, a periodic axis 0, a mix of scalar and field components, n1 <= 4 --
-// runs the generic k_euler (pa_ops.hip): pa_tile3d_euler_vel returns 0 for it.  A target that is itself one of the three speed
+// runs the generic k_euler (pa_march.hip): pa_tile3d_euler_vel returns 0 for it.  A target that is itself one of the three speed
 // fields (pa_momentum_march, own >= 0) takes the VEL 3 instantiations of pa_sf_vself.hip under the same conditions.
 #include "pa_sf_kernel.h"
 
@@ -18,7 +18,7 @@ int pa_sf_euler_vel(pa_ctx* c, Cg3dArgs<T>& A, bool stage, bool fields, bool sou
   return stage ? launch_sf_vel<T, 1, true>(c, A, source) : launch_sf_vel<T, 1, false>(c, A, source);
 }
 
-// vel: indexed by INTERNAL axis (euler_vel_t, pa_ops.hip).  Blocks launched, 0 when k_sf does not take the launch, < 0: error.
+// vel: indexed by INTERNAL axis (step_t, pa_march.hip).  Blocks launched, 0 when k_sf does not take the launch, < 0: error.
 template <typename T>
 int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_velocity* vel, double nu, double dt, const T* phi0,
                         double c0, double c1, const pa_source* src, int own) {
@@ -28,10 +28,7 @@ int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_veloci
   if (c->G.n1 <= 4) return 0;                        // two rows per wave only
   if (c->bc[0].type == PA_BC_PERIODIC || c->bc[1].type == PA_BC_PERIODIC) return 0;   // a periodic axis 0
   DevEq<T> E;
-  pa_term t;
-  memset(&t, 0, sizeof(t));
-  t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
-  pa_build_eq<T>(c, 1, &t, E);
+  pa_build_lap<T>(c, E);
   // (the three speed fields, a stage's phi0 and a source field count for the alignment)
   const int mode = cg3d_mode<T>(c, E, {phi.p, out, phi.glo, phi.ghi, phi0, src ? src->field : nullptr, vel->field[0], vel->field[1],
                                        vel->field[2]});
@@ -44,11 +41,7 @@ int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_veloci
   A.stg_phi0 = phi0; A.stg_c0 = (T)c0; A.stg_c1 = (T)c1;
   if (src) { A.src = (const T*)src->field; A.src_val = (T)src->value; }
   for (int a = 0; a < 3; ++a) { A.vel_f[a] = (const T*)vel->field[a]; A.vel_v[a] = (T)vel->value[a]; }
-  {  // the BC fill that follows the step kernel rewrites every face plane that has a BC (pa_tile3d_euler)
-    int faces = 0;
-    for (int f = 0; f < 6; ++f) faces += (c->G.act[f >> 1] && c->bc[f].type != PA_BC_NONE) ? 1 : 0;
-    A.out_all = faces == 2 * c->ndim ? 1 : 0;
-  }
+  A.out_all = pa_bc_on_every_face(c);   // the BC fill that follows the step kernel rewrites every face plane that has a BC (pa_tile3d_euler)
   if (!sf_applies<T, 3>(c, A, mode)) return 0;
   A.vel_own = own;
   const bool vself = own >= 0 && own < 3 && nf == 3 && c->vself && vel->field[own] == (const void*)phi.p;

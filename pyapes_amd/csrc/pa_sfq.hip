@@ -1,6 +1,6 @@
 // pa_sfq.hip -- the explicit Euler step / fused Runge-Kutta stage with the QUICK advection term on k_sfq
 // (pa_sfq_kernel.h).  A translation unit of its own: k_sf and its instantiations (pa_sf.hip, pa_sf_self.hip) are untouched.
-// euler_t (pa_ops.hip) asks here first for PA_OP_DIV_QUICK; 0 = not for k_sfq, the generic k_euler runs.
+// step_t (pa_march.hip) asks here first for PA_OP_DIV_QUICK; 0 = not for k_sfq, the generic k_euler runs.
 #include "pa_sfq_kernel.h"
 
 // Rows per wave.  Four rows read (4 + 4) / 4 = 2 rows per row computed, two rows (2 + 4) / 2 = 3 -- the halo rows are the
@@ -30,10 +30,7 @@ int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, d
   if (G.n0 < 5 || G.n1 < 5 || G.n2 < 5) return 0;
   if (G.bct[0] == PA_BC_PERIODIC || G.bct[1] == PA_BC_PERIODIC) return 0;   // the planes beyond the ends are not wrapped
   DevEq<T> E;
-  pa_term t;
-  memset(&t, 0, sizeof(t));
-  t.kind = PA_OP_LAPLACIAN; t.sign = 1.0;
-  pa_build_eq<T>(c, 1, &t, E);
+  pa_build_lap<T>(c, E);
   // whole 16-byte vectors, aligned operands (mode 1), option "fastpath"
   if (cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0, src ? src->field : nullptr}) != 1) return 0;
   Cg3dArgs<T> A;

@@ -180,21 +180,12 @@ class HipContext:
     def div(self, kind: int, u: float | Tensor, x: Tensor, out: Tensor | None = None) -> Tensor:
         x = self._field(x, "div")
         y = torch.empty_like(x) if out is None else self._field(out, "div out")
-        uf = None
-        us = 0.0
-        if isinstance(u, Tensor):
-            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
-        else:
-            us = float(u)
+        us, uf = self._speed(u)
         self._rc(self.lib.pa_div(self.h, kind, us, self._ptr(uf), self._ptr(x), self._ptr(y)))
         return y
 
     def div_edge(self, u: float | Tensor, x: Tensor, y: Tensor) -> None:
-        uf, us = None, 0.0
-        if isinstance(u, Tensor):
-            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
-        else:
-            us = float(u)
+        us, uf = self._speed(u)
         self._rc(self.lib.pa_div_edge(self.h, us, self._ptr(uf), self._ptr(self._field(x, "div edge")),
                                       self._ptr(self._field(y, "div edge out"))))
 
@@ -245,6 +236,27 @@ class HipContext:
         out = torch.empty_like(a)
         self._rc(self.lib.pa_limiter(self.h, int(which), self._ptr(a), self._ptr(b), self._ptr(out), a.numel()))
         return out
+
+    def _speed(self, u: float | Tensor) -> tuple[float, Tensor | None]:
+        """one advection speed as the C ABI takes it, ``(u, u_field)``: the number and no field, or 0.0 and the tensor"""
+        if isinstance(u, Tensor):
+            return 0.0, self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
+        return float(u), None
+
+    def _call_src(self, name: str, source: float | Tensor | None, what: str, *args: Any) -> None:
+        """``lib.<name>(h, *args)`` without a source, ``lib.<name>_src(h, *args, source)`` with one.  Two symbols, not one
+        with a NULL source: an A/B library named by ``PYAPES_HIP_LIB`` may predate the ``_src`` entry points (lib.py)."""
+        ps, _keep = self._source(source, what)
+        if ps is None:
+            self._rc(getattr(self.lib, name)(self.h, *args))
+        else:
+            self._rc(getattr(self.lib, name + "_src")(self.h, *args, C.byref(ps)))
+
+    def _rotate(self, bufs: Sequence[Tensor], call: Any) -> Tensor:
+        """a march over two or three buffers: ``call((phi, w1, w2 or NULL), final)``; returns the buffer that holds the result"""
+        final = C.c_int(0)
+        call([self._ptr(t) for t in bufs] + [self._ptr(None)] * (3 - len(bufs)), C.byref(final))
+        return bufs[final.value]
 
     def _source(self, source: float | Tensor | None, what: str) -> tuple[Any, Tensor | None]:
         """``pa_source`` of a call (None: no source, the sibling entry point runs) and the tensor it points into"""
@@ -301,16 +313,12 @@ class HipContext:
                      nu: float, dt: float, nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``rk_march`` in a velocity field, frozen for the whole call (``pa_rk_march_vel``).  Order 1 is the Euler march and
         needs no ``w2``.  Returns the tensor that holds the final state."""
-        bufs = [self._field(t, "rk_march_vel") for t in (phi, w1)]
-        if w2 is not None:
-            bufs.append(self._field(w2, "rk_march_vel"))
+        bufs = [self._field(t, "rk_march_vel") for t in (phi, w1, w2) if t is not None]
         pv, _kv = self._velocity(vel, "rk_march_vel")
         ps, _keep = self._source(source, "rk_march_vel")
-        final = C.c_int(0)
-        self._rc(self.lib.pa_rk_march_vel(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2] if len(bufs) > 2 else None),
-                                          int(order), kind, C.byref(pv), float(nu), float(dt), int(nsteps), C.byref(final),
-                                          None if ps is None else C.byref(ps)))
-        return bufs[final.value]
+        return self._rotate(bufs, lambda ptrs, final: self._rc(self.lib.pa_rk_march_vel(
+            self.h, *ptrs, int(order), kind, C.byref(pv), float(nu), float(dt), int(nsteps), final,
+            None if ps is None else C.byref(ps))))
 
     def bc_values(self, var: Tensor, bcs: Sequence[Any], comp: int) -> tuple[Any, list[Tensor]]:
         """``pa_bc_values`` of component ``comp`` -- every face's scalar and face array, resolved once -- and the arrays it
@@ -356,11 +364,9 @@ class HipContext:
             bv[q] = one
             _kb.append(kept)
         self._keep["momentum"] = (_kv, _ks, _kb)   # what the enqueued launches still read
-        final = C.c_int(0)
-        self._rc(self.lib.pa_momentum_march(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2] if len(bufs) > 2 else None),
-                                            nd, int(order), kind, None if pv is None else C.byref(pv), float(nu), float(dt),
-                                            int(nsteps), C.byref(final), ps, bv))
-        return bufs[final.value]
+        return self._rotate(bufs, lambda ptrs, final: self._rc(self.lib.pa_momentum_march(
+            self.h, *ptrs, nd, int(order), kind, None if pv is None else C.byref(pv), float(nu), float(dt), int(nsteps), final,
+            ps, bv)))
 
     def euler_march(self, phi: Tensor, tmp: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
                     nsteps: int, source: float | Tensor | None = None) -> Tensor:
@@ -369,36 +375,18 @@ class HipContext:
         for the whole call."""
         phi = self._field(phi, "euler_march")
         tmp = self._field(tmp, "euler_march")
-        uf, us = None, 0.0
-        if isinstance(u, Tensor):
-            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
-        else:
-            us = float(u)
-        ps, _keep = self._source(source, "euler_march")
-        if ps is None:
-            self._rc(self.lib.pa_euler_march(self.h, self._ptr(phi), self._ptr(tmp), kind, us, self._ptr(uf),
-                                             float(nu), float(dt), int(nsteps)))
-        else:
-            self._rc(self.lib.pa_euler_march_src(self.h, self._ptr(phi), self._ptr(tmp), kind, us, self._ptr(uf),
-                                                 float(nu), float(dt), int(nsteps), C.byref(ps)))
+        us, uf = self._speed(u)
+        self._call_src("pa_euler_march", source, "euler_march", self._ptr(phi), self._ptr(tmp), kind, us, self._ptr(uf),
+                       float(nu), float(dt), int(nsteps))
         return phi if nsteps % 2 == 0 else tmp
 
     def euler_step(self, phi: Tensor, out: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
                    source: float | Tensor | None = None) -> None:
         phi = self._field(phi, "euler_step")
         out = self._field(out, "euler_step")
-        uf, us = None, 0.0
-        if isinstance(u, Tensor):
-            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
-        else:
-            us = float(u)
-        ps, _keep = self._source(source, "euler_step")
-        if ps is None:
-            self._rc(self.lib.pa_euler_step(self.h, self._ptr(phi), self._ptr(out), kind, us, self._ptr(uf),
-                                            float(nu), float(dt)))
-        else:
-            self._rc(self.lib.pa_euler_step_src(self.h, self._ptr(phi), self._ptr(out), kind, us, self._ptr(uf),
-                                                float(nu), float(dt), C.byref(ps)))
+        us, uf = self._speed(u)
+        self._call_src("pa_euler_step", source, "euler_step", self._ptr(phi), self._ptr(out), kind, us, self._ptr(uf),
+                       float(nu), float(dt))
 
     def rk_stage(self, phi: Tensor, phi0: Tensor, out: Tensor, c0: float, c1: float, kind: int, u: float | Tensor,
                  nu: float, dt: float, source: float | Tensor | None = None) -> None:
@@ -407,56 +395,26 @@ class HipContext:
         phi = self._field(phi, "rk_stage")
         phi0 = self._field(phi0, "rk_stage")
         out = self._field(out, "rk_stage")
-        uf, us = None, 0.0
-        if isinstance(u, Tensor):
-            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
-        else:
-            us = float(u)
-        ps, _keep = self._source(source, "rk_stage")
-        if ps is None:
-            self._rc(self.lib.pa_rk_stage(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1),
-                                          kind, us, self._ptr(uf), float(nu), float(dt)))
-        else:
-            self._rc(self.lib.pa_rk_stage_src(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1),
-                                              kind, us, self._ptr(uf), float(nu), float(dt), C.byref(ps)))
+        us, uf = self._speed(u)
+        self._call_src("pa_rk_stage", source, "rk_stage", self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1),
+                       kind, us, self._ptr(uf), float(nu), float(dt))
 
     def rk_march(self, phi: Tensor, w1: Tensor, w2: Tensor, order: int, kind: int, u: float | Tensor, nu: float,
                  dt: float, nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``nsteps`` SSP Runge-Kutta steps of ``order`` enqueued back to back over the three buffers; returns the
         tensor that holds the final state.  ``source``: frozen for the whole call, in every stage."""
         bufs = [self._field(t, "rk_march") for t in (phi, w1, w2)]
-        uf, us = None, 0.0
-        if isinstance(u, Tensor):
-            uf = self._field(u if u.dim() == self.mesh.dim else u[0], "advection tensor")
-        else:
-            us = float(u)
-        final = C.c_int(0)
-        ps, _keep = self._source(source, "rk_march")
-        if ps is None:
-            self._rc(self.lib.pa_rk_march(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2]), int(order),
-                                          kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), C.byref(final)))
-        else:
-            self._rc(self.lib.pa_rk_march_src(self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2]), int(order),
-                                              kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), C.byref(final),
-                                              C.byref(ps)))
-        return bufs[final.value]
+        us, uf = self._speed(u)
+        return self._rotate(bufs, lambda ptrs, final: self._call_src(
+            "pa_rk_march", source, "rk_march", *ptrs, int(order), kind, us, self._ptr(uf), float(nu), float(dt), int(nsteps), final))
 
     def rk_march_self(self, phi: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int, nu: float, dt: float,
                       nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``rk_march`` of a field that advects itself: every launch takes its own input buffer as the speed.  Order 1
         needs no ``w2``.  Returns the tensor that holds the final state."""
-        bufs = [self._field(t, "rk_march_self") for t in (phi, w1)]
-        if w2 is not None:
-            bufs.append(self._field(w2, "rk_march_self"))
-        final = C.c_int(0)
-        ps, _keep = self._source(source, "rk_march_self")
-        args = (self.h, self._ptr(bufs[0]), self._ptr(bufs[1]), self._ptr(bufs[2] if len(bufs) > 2 else None), int(order),
-                kind, float(nu), float(dt), int(nsteps), C.byref(final))
-        if ps is None:
-            self._rc(self.lib.pa_rk_march_self(*args))
-        else:
-            self._rc(self.lib.pa_rk_march_self_src(*args, C.byref(ps)))
-        return bufs[final.value]
+        bufs = [self._field(t, "rk_march_self") for t in (phi, w1, w2) if t is not None]
+        return self._rotate(bufs, lambda ptrs, final: self._call_src(
+            "pa_rk_march_self", source, "rk_march_self", *ptrs, int(order), kind, float(nu), float(dt), int(nsteps), final))
 
     # -- solvers --------------------------------------------------------------------------
     def keep_old(self, x_old: Tensor | None) -> None:

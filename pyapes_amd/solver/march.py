@@ -173,6 +173,34 @@ def _velocity_of(phi: Field, u: Any, config: dict | None, what: str) -> list[flo
     return out
 
 
+def _kind_of(config: dict | None, mesh: Any, what: str) -> int:
+    """the Div kind ``config`` asks for (default: upwind), checked against the mesh where the scheme needs it (QUICK)"""
+    cfg = (config or {}).get("div", {"limiter": "upwind"})
+    kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
+    quick_mesh_check(kind, mesh, what)
+    return kind
+
+
+def _run(ctx: Any, phi: Field, bufs: list[Tensor], order: int, kind: int, u: Any, vel: list[float | Tensor] | None,
+         self_adv: bool, nu: float, dt: float, nsteps: int, src: float | Tensor | None) -> None:
+    """``nsteps`` steps of ``order`` of ``phi`` over the work buffers ``bufs`` (``(1, *n)`` each; one: the Euler march), through
+    the Context method that takes ``u`` -- a velocity, the field itself, else one speed.  ``phi`` adopts the buffer that holds
+    the result."""
+    w1 = bufs[0][0]
+    w2 = None if len(bufs) == 1 or order == 1 else bufs[1][0]   # order 1: the ping-pong of two buffers
+    if vel is not None:
+        final = ctx.rk_march_vel(phi()[0], w1, w2, order, kind, vel, nu, dt, nsteps, source=src)
+    elif self_adv:   # the speed moves with the field: no single pointer names it
+        final = ctx.rk_march_self(phi()[0], w1, w2, order, kind, nu, dt, nsteps, source=src)
+    elif len(bufs) == 1:
+        final = ctx.euler_march(phi()[0], w1, kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
+    else:
+        final = ctx.rk_march(phi()[0], w1, bufs[1][0], order, kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
+    for w in bufs:
+        if final.data_ptr() == w[0].data_ptr():
+            phi.set_var_tensor(w)
+
+
 def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind: int) -> Field:
     """``Mesh(..., slab=(rank, world))``: the same call on every rank of the process group (pyapes_amd/slab.py SlabEuler)."""
     import torch.distributed as dist
@@ -200,14 +228,9 @@ def euler_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, 
     docstring "Velocity"), frozen for the call."""
     vel = _velocity_of(phi, u, config, "euler_step")
     src = _source_of(phi, source, "euler_step")
+    kind = _kind_of(config, phi.mesh, "euler_step")
     if getattr(phi.mesh, "slab", None) is not None:
-        cfg = (config or {}).get("div", {"limiter": "upwind"})
-        kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
-        quick_mesh_check(kind, phi.mesh, "euler_step")
         return _march_on_slabs(phi, u, nu, dt, 1, kind)
-    cfg = (config or {}).get("div", {"limiter": "upwind"})
-    kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
-    quick_mesh_check(kind, phi.mesh, "euler_step")
     require_gpu(phi(), "euler_step")
     if phi.dim != 1:
         raise NotImplementedError("pyapes_amd: euler_step is for scalar fields")
@@ -232,9 +255,7 @@ def euler_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float,
         raise NotImplementedError("pyapes_amd: euler_march is for scalar fields")
     vel = _velocity_of(phi, u, config, "euler_march")
     src = _source_of(phi, source, "euler_march")
-    cfg = (config or {}).get("div", {"limiter": "upwind"})
-    kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
-    quick_mesh_check(kind, phi.mesh, "euler_march")
+    kind = _kind_of(config, phi.mesh, "euler_march")
     self_adv = advects_itself(phi, u)
     if self_adv:
         _no_self_on_slabs(phi, "euler_march")
@@ -248,15 +269,7 @@ def euler_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float,
     ctx.bind_bcs(phi(), phi.bcs, 0)
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
-    tmp = torch.empty_like(phi())
-    if vel is not None:
-        final = ctx.rk_march_vel(phi()[0], tmp[0], None, 1, kind, vel, nu, dt, nsteps, source=src)
-    elif self_adv:   # the speed ping-pongs with the field: no single pointer names it
-        final = ctx.rk_march_self(phi()[0], tmp[0], None, 1, kind, nu, dt, nsteps, source=src)
-    else:
-        final = ctx.euler_march(phi()[0], tmp[0], kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
-    if final.data_ptr() == tmp[0].data_ptr():
-        phi.set_var_tensor(tmp)
+    _run(ctx, phi, [torch.empty_like(phi())], 1, kind, u, vel, self_adv, nu, dt, nsteps, src)
     if hasattr(phi, "_t"):
         phi.update_time(dt * nsteps)
     return phi
@@ -270,10 +283,7 @@ def _rk_args(phi: Field, config: dict | None, order: int, what: str) -> int:
         raise NotImplementedError(f"pyapes_amd: {what} is for scalar fields")
     if getattr(phi.mesh, "slab", None) is not None:
         raise NotImplementedError(f"pyapes_amd: {what} on a slab mesh (the stages march on one GPU; euler_march does slabs)")
-    cfg = (config or {}).get("div", {"limiter": "upwind"})
-    kind = div_kind(cfg.get("limiter", "upwind").lower(), bool(cfg.get("compat", False)))
-    quick_mesh_check(kind, phi.mesh, what)
-    return kind
+    return _kind_of(config, phi.mesh, what)
 
 
 def rk_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float, config: dict | None = None,
@@ -292,16 +302,7 @@ def rk_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt:
     ctx.bind_bcs(phi(), phi.bcs, 0)
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
-    w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
-    if vel is not None:
-        final = ctx.rk_march_vel(phi()[0], w1[0], w2[0], order, kind, vel, nu, dt, 1, source=src)
-    elif self_adv:
-        final = ctx.rk_march_self(phi()[0], w1[0], w2[0], order, kind, nu, dt, 1, source=src)
-    else:
-        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, 1, source=src)
-    for w in (w1, w2):
-        if final.data_ptr() == w[0].data_ptr():
-            phi.set_var_tensor(w)
+    _run(ctx, phi, [torch.empty_like(phi()), torch.empty_like(phi())], order, kind, u, vel, self_adv, nu, dt, 1, src)
     return phi
 
 
@@ -323,16 +324,7 @@ def rk_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt
     ctx.bind_bcs(phi(), phi.bcs, 0)
     if not phi().is_contiguous():
         phi.set_var_tensor(phi().contiguous())
-    w1, w2 = torch.empty_like(phi()), torch.empty_like(phi())
-    if vel is not None:
-        final = ctx.rk_march_vel(phi()[0], w1[0], None if order == 1 else w2[0], order, kind, vel, nu, dt, nsteps, source=src)
-    elif self_adv:
-        final = ctx.rk_march_self(phi()[0], w1[0], None if order == 1 else w2[0], order, kind, nu, dt, nsteps, source=src)
-    else:
-        final = ctx.rk_march(phi()[0], w1[0], w2[0], order, kind, _adv_of(u, phi), nu, dt, nsteps, source=src)
-    for w in (w1, w2):
-        if final.data_ptr() == w[0].data_ptr():
-            phi.set_var_tensor(w)
+    _run(ctx, phi, [torch.empty_like(phi()), torch.empty_like(phi())], order, kind, u, vel, self_adv, nu, dt, nsteps, src)
     if hasattr(phi, "_t"):
         phi.update_time(dt * nsteps)
     return phi
@@ -373,8 +365,7 @@ def _momentum_args(U: Field, config: dict | None, order: int, u: Any, source: An
     cfg = (config or {}).get("div", {"limiter": "upwind"})
     if bool(cfg.get("compat", False)):
         raise NotImplementedError(f"pyapes_amd: {what} with compat: True (the reference's literal upwind form takes one speed)")
-    kind = div_kind(cfg.get("limiter", "upwind").lower(), False)
-    quick_mesh_check(kind, mesh, what)
+    kind = _kind_of(config, mesh, what)
     comp = _Component(U)
     vel = None
     if u is not None:

@@ -6,7 +6,7 @@ The yardstick is the composition of public pieces that exist without the feature
 and a fused stage must give those BITS -- on every kernel path, for every Div scheme, for both signs of a scalar speed, a
 speed tensor, the BC mixes of test_gpu_bcl.py and a periodic axis, the (c0, c1) of every fused stage, and a phi0 that is
 not 16-byte aligned (which must fall to the next path).  (With a periodic face the stage cannot be ONE kernel -- the
-periodic fill reads a face value before it rewrites it, csrc/pa_ops.hip euler_t -- and runs as step + combine kernel.)  The march must be its stages, the kernel switches must not change
+periodic fill reads a face value before it rewrites it, csrc/pa_march.hip step_t -- and runs as step + combine kernel.)  The march must be its stages, the kernel switches must not change
 bits, and the facts tests/test_rk_host.py establishes on the CPU (order in time, stability of central advection) must hold
 through rk_march on the GPU with the same bounds.
 """
