@@ -9,25 +9,24 @@ the rows per wave of k_sf (as "sfq" 2 / 4 does for k_sfq), so that small meshes 
 Every check has two yardsticks, neither of which is the code under test:
   * the generic kernels (option "fastpath" 0: one thread per node, no chunks), bit for bit (helpers.bit_equal) -- every
     tiled launch is compared with them;
-  * the CPU references, each with the criterion the suite already uses for that scheme: QUICK tests/quick_ref.py bit for bit
+  * the CPU references, each with the criterion the suite already uses for that scheme: QUICK tests/march_ref.py bit for bit
     (test_gpu_quick.py), central pyapes_oracle.euler_step bit for bit (test_gpu_parity_golden.py), intended upwind
     pyapes_oracle.euler_step to rel_err 1e-13 (fp64) / 1e-6 (fp32) (test_gpu_fuzz.py); a stage is c0 * phi0 + c1 * E in the
     mesh dtype followed by the oracle's bc_fill.  (The literal "compat" upwind has no CPU statement in the oracle's Euler
     step: the generic kernels alone.)  The generic result is held against the CPU reference once per case; a tiled
     launch that equals the generic bits then meets the same criterion with the same figures.
 """
-import os
 import random
 import re
-import subprocess
 import sys
 import warnings
 
 import pytest
 import torch
 
+import march_gpu as G
+import march_ref as Q
 import pyapes_oracle as O
-import quick_ref as Q
 import test_gpu_fuzz as F
 import test_gpu_quick as TQ
 import test_gpu_rk as R
@@ -85,7 +84,7 @@ class Case:
         self.tag = ("x".join(map(str, n)), dtype, BCNAME.get(id(bcs), bcs[1]))
 
     def rebind(self):
-        f = R._field(self.mesh, self.bc, self.phis)
+        f = G.fresh_field(self.mesh, self.bc, self.phis)
         self.ctx.bind_bcs(f(), f.bcs, 0)
 
     def options(self, **kw):
@@ -125,7 +124,7 @@ class Case:
         u = self.speed(form)
         uc = x if form == "self" else (u.cpu().clone() if isinstance(u, torch.Tensor) else u)
         if scheme == "quick":
-            e = Q.euler_step_quick(x, uc, self.nu, self.dt, self.om, self.ob)
+            e = Q.euler_step(x, uc, self.nu, self.dt, self.om, self.ob, "quick")
         elif scheme in LIMITER:
             e = O.euler_step(x, uc, self.nu, self.dt, self.om, self.ob, LIMITER[scheme])
         else:
@@ -203,17 +202,6 @@ def sweep_steps(dtype, scheme, form, meshes, rows_list, sf=None):
 
 
 # ---- (a) the switches do what they say ---------------------------------------------------------------------------------------
-def _child(code):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pre = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, PYAPES_HIP_DEBUG="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(root, "oracle"), os.environ.get("PYTHONPATH", "")]))
-    env.pop("PYAPES_HIP_OPTIONS", None)
-    r = subprocess.run([sys.executable, "-c", pre + code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
 def _mark(tag):
     torch.cuda.synchronize()
     sys.stderr.write("CASE %s\n" % tag)
@@ -221,14 +209,7 @@ def _mark(tag):
 
 
 def _by_case(log):
-    seen, cur = {}, None
-    for ln in log.splitlines():
-        if ln.startswith("CASE "):
-            cur = ln[5:].strip()
-            seen[cur] = []
-        elif cur is not None and "[pyapes_hip]" in ln:
-            seen[cur].append(ln)
-    return seen
+    return G.case_log(log, lambda ln: "[pyapes_hip]" in ln)
 
 
 def _field_of(line, word):
@@ -267,7 +248,7 @@ def switch_child():
 
 
 def test_switches_do_what_they_say():
-    log = _child("import torch\nimport test_gpu_chunks as T\nT.switch_child()\n")
+    log = G.child("import torch\nimport test_gpu_chunks as T\nT.switch_child()\n", drop_options=True)
     seen = _by_case(log)
     for kern, word in (("sf", "k_sf "), ("sfq", "k_sfq "), ("cg3d", "k_cg3d ")):
         rule = [ln for ln in seen["%s cap 0" % kern] if word in ln]
@@ -348,7 +329,7 @@ def test_k_cg3d_step_and_stage(scheme, form, dtype):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_div_term_alone(dtype):
-    """FDC.div on k_sf phase 2: the generic kernels bit for bit; QUICK (generic on every path) == tests/quick_ref.py"""
+    """FDC.div on k_sf phase 2: the generic kernels bit for bit; QUICK (generic on every path) == tests/march_ref.py"""
     bad = []
     for n, bcs in step_meshes(dtype, "upwind", "k_sf"):
         c = Case(n, dtype, bcs)
@@ -358,17 +339,17 @@ def test_div_term_alone(dtype):
                 u = c.speed(form)
                 cfg = {"div": dict(CONFIG[scheme]["div"], edge=False)}
                 c.generic()
-                gen = FDC(cfg).div(u, R._field(c.mesh, c.bc, c.phis)).clone()
+                gen = FDC(cfg).div(u, G.fresh_field(c.mesh, c.bc, c.phis)).clone()
                 assert bool(torch.isfinite(gen).all())
                 for rows in (2, 4):
                     for cap in CAPS:
                         c.tiled(cap, rows)
-                        out = FDC(cfg).div(u, R._field(c.mesh, c.bc, c.phis))
+                        out = FDC(cfg).div(u, G.fresh_field(c.mesh, c.bc, c.phis))
                         if not bit_equal(out, gen):
                             bad.append((c.tag, scheme, form, rows, cap, where(out, gen)))
         if n[1] >= 5:
             c.tiled(2)
-            out = FDC(QUICK).div(c.ufield, R._field(c.mesh, c.bc, c.phis))
+            out = FDC(QUICK).div(c.ufield, G.fresh_field(c.mesh, c.bc, c.phis))
             if not bit_equal(out, Q.div_quick(c.ufield.cpu(), c.phis.cpu(), c.om, c.ob)):
                 bad.append((c.tag, "quick div"))
     assert not bad, told(bad, 6)
@@ -385,7 +366,7 @@ def test_k_cg3d_laplacian_aop_gradient(dtype):
         def ops():
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
-                var = R._field(c.mesh, c.bc, c.phis)
+                var = G.fresh_field(c.mesh, c.bc, c.phis)
                 solver = Solver({"fdm": {"method": "cg", "tol": 1e-6, "max_it": 1, "report": False}})
                 solver.set_eq(-FDM().laplacian(0.7, var) == torch.zeros_like(var()))
                 return {"lap": FDC({"laplacian": {"edge": False}}).laplacian(var).clone(), "aop": solver.Aop(var).clone(),
@@ -458,7 +439,7 @@ def march_meshes(dtype):
 
 
 def _march(c, scheme, self_adv, order, u=None):
-    f = R._field(c.mesh, c.bc, c.phis)
+    f = G.fresh_field(c.mesh, c.bc, c.phis)
     if order == 0:
         return euler_march(f, f if self_adv else u, c.nu, c.dt, 3, CONFIG[scheme])().clone()
     return rk_march(f, f if self_adv else u, c.nu, c.dt, 3, CONFIG[scheme], order=order)().clone()
@@ -469,10 +450,10 @@ def _cpu_march(c, scheme, self_adv, order, u=None):
     uc = u.cpu().clone() if isinstance(u, torch.Tensor) else u
     order = order or 1
     if scheme == "quick":
-        return Q.march_quick(x, uc, c.nu, c.dt, 3, c.om, c.ob, order, self_adv)
+        return Q.march(x, uc, c.nu, c.dt, 3, c.om, c.ob, "quick", order, self_adv=self_adv)
     if self_adv:
         return HS.oracle_self_march(x, c.nu, c.dt, 3, c.om, c.ob, LIMITER[scheme], order)
-    return Q.march_limiter(x, uc, c.nu, c.dt, 3, c.om, c.ob, LIMITER[scheme], order)
+    return Q.march(x, uc, c.nu, c.dt, 3, c.om, c.ob, LIMITER[scheme], order, step=O.euler_step)
 
 
 def sweep_marches(dtype, scheme, self_adv, orders, bcsets, speeds=("pos",), bcl=(1,)):
@@ -634,7 +615,7 @@ def rule_child():
 
 
 def test_the_rule_itself_reaches_long_chunks():
-    log = _child("import torch\nimport test_gpu_chunks as T\nT.rule_child()\n")
+    log = G.child("import torch\nimport test_gpu_chunks as T\nT.rule_child()\n", drop_options=True)
     seen = _by_case(log)
     print([ln for ln in log.splitlines() if "[pyapes_hip] k_" in ln or ln.startswith("RESULT")])
     march = [ln for ln in seen["march"] if "k_sf " in ln]

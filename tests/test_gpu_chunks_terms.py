@@ -11,8 +11,8 @@ take, 2 * VEC nodes, where one lane's vector ends the row.
 
 Two yardsticks, neither of them the code under test, and no tolerance anywhere:
   * every tiled launch equals the generic kernels (option "fastpath" 0, "chunks" 0) in every bit;
-  * the generic result, once per case, equals the CPU reference in every bit: tests/source_ref.py for one speed,
-    tests/velocity_ref.py for a velocity (tests/test_velocity_host.py holds the two against each other on these meshes).
+  * the generic result, once per case, equals the CPU reference in every bit: tests/march_ref.py with one speed and
+    with a velocity (tests/test_velocity_host.py holds the two forms against each other on these meshes).
 Inputs: the case's two BC-filled fields and speed field, a source field 3 * randn and a velocity of three DISTINCT randn
 components (a swapped axis cannot pass) from the case's seeded generator; the scalar velocity (0.9, -0.8, 0.4), the scalar
 source 1.75.
@@ -23,17 +23,17 @@ import sys
 import pytest
 import torch
 
-import source_ref as SR
+import march_gpu as G
+import march_ref as M
 import test_gpu_rk as R
-import velocity_ref as VR
 from helpers import bit_equal
 from pyapes_amd.solver.march import euler_march, rk_march
-from test_gpu_chunks import (CAPS, CONFIG, DTYPES, MARCH_BCS, STAGES, Case, _by_case, _child, _field_of, _mark, _n2, march_meshes,
-                             step_meshes, told, where)
+from test_gpu_chunks import (CAPS, CONFIG, DTYPES, MARCH_BCS, STAGES, Case, _by_case, _field_of, _mark, _n2, march_meshes, step_meshes,
+                             told, where)
 
 pytestmark = pytest.mark.gpu
 
-LIMITER = {"upwind": "upwind", "central": "none", "quick": "quick"}      # the limiter names of the two references
+LIMITER = {"upwind": "upwind", "central": "none", "quick": "quick"}      # the limiter names of tests/march_ref.py
 SCALAR_VELOCITY = (0.9, -0.8, 0.4)
 SCALAR_SOURCE = 1.75
 SOURCES = ["field", "scalar"]
@@ -80,7 +80,7 @@ class TermCase(Case):
     def cpu_term(self, scheme, form, stage, source):
         s = self.source(source)[0]
         v = self.velocity(form)[0]
-        M, u = (VR, v) if v is not None else (SR, self.speed_ref(form))
+        u = v if v is not None else self.speed_ref(form)
         if stage is None:
             return M.euler_step(self.x, u, self.nu, self.dt, self.om, self.ob, LIMITER[scheme], s)
         return M.rk_stage(self.x, self.x0, stage[0], stage[1], u, self.nu, self.dt, self.om, self.ob, LIMITER[scheme], s)
@@ -159,9 +159,9 @@ def test_a_mix_of_scalar_and_field_components_under_a_cap(dtype):
         s_ref, s_dev = c.source(source)
         for st in STAGES:
             if st is None:
-                ref = VR.euler_step(c.x, v_ref, c.nu, c.dt, c.om, c.ob, "upwind", s_ref)
+                ref = M.euler_step(c.x, v_ref, c.nu, c.dt, c.om, c.ob, "upwind", s_ref)
             else:
-                ref = VR.rk_stage(c.x, c.x0, st[0], st[1], v_ref, c.nu, c.dt, c.om, c.ob, "upwind", s_ref)
+                ref = M.rk_stage(c.x, c.x0, st[0], st[1], v_ref, c.nu, c.dt, c.om, c.ob, "upwind", s_ref)
             c.generic()
             assert bit_equal(c.launch("upwind", "pos", st, s_dev, v_dev), ref), (source, st)
             for cap in (2, 0):
@@ -175,7 +175,7 @@ def test_a_mix_of_scalar_and_field_components_under_a_cap(dtype):
 
 # ---- (c) marches --------------------------------------------------------------------------------------------------------------
 def _march(c, scheme, form, order, source):
-    f = R._field(c.mesh, c.bc, c.phis)
+    f = G.fresh_field(c.mesh, c.bc, c.phis)
     v = c.velocity(form)[1]
     u = tuple(v) if v is not None else (f if form == "self" else c.speed(form))
     s = c.src if source == "field" else c.source(source)[1]
@@ -188,8 +188,8 @@ def _cpu_march(c, scheme, form, order, source):
     s = c.source(source)[0]
     v = c.velocity(form)[0]
     if v is not None:
-        return VR.march(c.x, v, c.nu, c.dt, 3, c.om, c.ob, LIMITER[scheme], order or 1, s)
-    return SR.march(c.x, c.speed_ref(form), c.nu, c.dt, 3, c.om, c.ob, LIMITER[scheme], order or 1, s, self_adv=form == "self")
+        return M.march(c.x, v, c.nu, c.dt, 3, c.om, c.ob, LIMITER[scheme], order or 1, s)
+    return M.march(c.x, c.speed_ref(form), c.nu, c.dt, 3, c.om, c.ob, LIMITER[scheme], order or 1, s, self_adv=form == "self")
 
 
 def sweep_term_marches(dtype, scheme, forms, orders, bcsets, source, bcl=(1,), extra=(), meshes=None, rows_list=(0, 4)):
@@ -393,7 +393,7 @@ def sweep_child():
 def test_term_sweep_cases_run_on_the_tiled_kernels():
     """the first 24 cases in one child process with the launch log on: one k_sf / k_sfq line each, with the source and the
     velocity it was given, the cap's chunks of two planes or more, and no generic or k_cg3d launch beside it"""
-    log = _child("import torch\nimport test_gpu_chunks_terms as T\nT.sweep_child()\n")
+    log = G.child("import torch\nimport test_gpu_chunks_terms as T\nT.sweep_child()\n", drop_options=True)
     seen = _by_case(log)
     checked = 0
     for k, p in enumerate(term_cases()[:24]):
@@ -442,7 +442,7 @@ def rule_child():
 
 
 def test_the_rule_itself_with_a_source_and_a_velocity():
-    log = _child("import torch\nimport test_gpu_chunks_terms as T\nT.rule_child()\n")
+    log = G.child("import torch\nimport test_gpu_chunks_terms as T\nT.rule_child()\n", drop_options=True)
     seen = _by_case(log)
     print([ln for ln in log.splitlines() if "[pyapes_hip] k_" in ln or ln.startswith("RESULT")])
     march = [ln for ln in seen["march"] if "k_sf " in ln]

@@ -2,7 +2,7 @@
 ``pa_momentum_march`` at the C ABI, the VEL 3 instantiations of k_sf (upwind, the target's own speed taken from the centre
 operand), the aliased VEL 2 instantiations (option ``vself`` 0) and the generic k_euler (everything else).
 
-The yardstick is tests/momentum_ref.py, the stage restated on the CPU from tests/velocity_ref.py, and the device must give its
+The yardstick is the momentum functions of tests/march_ref.py, the stage restated on the CPU, and the device must give its
 BITS: three DISTINCT random components, face values that DIFFER per component with one component holding a Dirichlet face ARRAY
 where the others hold scalars (a swapped component, axis or BC bank cannot pass), no source / a source field per component / a
 scalar per component.  Meshes as tests/test_gpu_velocity.py: whole 16-byte rows and two k tiles (132 fp64 / 260 fp32 nodes per
@@ -10,48 +10,32 @@ row), n1 = 13 / 14, n0 = 7 / 9 with the chunk cap at 1, 2, 3; the generic kernel
 The exact shift needs no reference.  The frozen form must be d scalar ``rk_march`` calls, the march the stages composed by hand.
 """
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
-import momentum_ref as MR
+import march_gpu as G
+import march_ref as R
 import pyapes_oracle as O
-import velocity_ref as R
 from helpers import bit_equal
+from march_gpu import BCS, LIMITER_BCS, VECTOR
+from march_ref import momentum as MR
 from pyapes_amd.geometry import Box, Cylinder
 from pyapes_amd.hip import lib as L
 from pyapes_amd.hip.context import context_for
 from pyapes_amd.hip.lib import PaError
 from pyapes_amd.mesh import Mesh
 from pyapes_amd.solver.fdc import div_kind
-from pyapes_amd.solver.march import SSP_STAGES, momentum_march, momentum_step, rk_march
+from pyapes_amd.solver.march import momentum_march, momentum_step, rk_march
 from pyapes_amd.variables import Field
 from pyapes_amd.variables.bcs import mixed_bcs
 
 pytestmark = pytest.mark.gpu
 
-ALLDIR = ([0.0, 1.0, 0.25, -0.5, 2.0, 0.0], ["dirichlet"] * 6)
-MIXED = ([0.5, 0.1, None, 1.0, -0.3, None], ["dirichlet", "neumann", "symmetry", "dirichlet", "neumann", "symmetry"])
-XPER = ([None, None, 0.25, -0.5, 2.0, 0.0], ["periodic", "periodic", "dirichlet", "dirichlet", "dirichlet", "dirichlet"])
-BCS = {"dir": ALLDIR, "mix": MIXED, "xper": XPER}
 ARRAY_FACE, ARRAY_COMP = 3, 1          # face "yu" is dirichlet in every set: component 1 holds an array there
-LIMITER_BCS = {"upwind": ("dir", "mix"), "quick": ("dir", "mix"), "none": ("dir",)}   # central Div refuses neumann / symmetry
 SCALAR_SOURCES = (1.75, -0.5, 0.25)
 
-VECTOR = [([7, 13, 132], "double"), ([9, 14, 132], "double"), ([7, 13, 260], "single"), ([9, 14, 260], "single")]
-_ids = lambda v: "x".join(map(str, v)) if isinstance(v, list) else v
-
-
-def _config(limiter):
-    return {"div": {"limiter": limiter}}
-
-
-def _box(nd):
-    return Box[0:1] if nd == 1 else (Box[0:1, 0:1] if nd == 2 else Box[0:1, 0:1, 0:1])
-
+_ids = G.mesh_id
 
 _SETUPS = {}
 
@@ -64,7 +48,7 @@ def _setup(n, dtype, bcname):
         nd = len(n)
         vals, types = BCS[bcname]
         vals, types = vals[:2 * nd], types[:2 * nd]
-        mesh = Mesh(_box(nd), None, list(n), "cuda", dtype)
+        mesh = Mesh(G.box(nd), None, list(n), "cuda", dtype)
         tdt = mesh.dtype.float
         om = O.OMesh([0.0] * nd, [1.0] * nd, list(n), dtype)
         g = torch.Generator().manual_seed(5)
@@ -91,14 +75,6 @@ def _setup(n, dtype, bcname):
     return _SETUPS[key]
 
 
-def _field(mesh, bc, U_c, time=False):
-    f = Field("U", U_c.shape[0], mesh, bc)
-    f.set_var_tensor(U_c.cuda())
-    if time:
-        f.set_time(0.0, 1.5)
-    return f
-
-
 def _sources(src_c):
     nd = src_c.shape[0]
     sd = src_c.cuda()
@@ -107,7 +83,7 @@ def _sources(src_c):
 
 
 def run_case(n, dtype, limiter, option_sets, bcnames=None):
-    """one Euler step (momentum_step, order 1) and a one-step order-3 march, every source variant, against momentum_ref"""
+    """one Euler step (momentum_step, order 1) and a one-step order-3 march, every source variant, against march_ref.momentum"""
     bad = []
     for bcname in bcnames or LIMITER_BCS[limiter]:
         mesh, bc, om, obcs, _, U_c, src_c, _, nu, dt = _setup(n, dtype, bcname)
@@ -118,8 +94,8 @@ def run_case(n, dtype, limiter, option_sets, bcnames=None):
             for opts in option_sets:
                 for k, v in opts.items():
                     ctx.set_option(k, v)
-                got1 = momentum_step(_field(mesh, bc, U_c), nu, dt, _config(limiter), order=1, source=s_dev)()
-                got3 = momentum_march(_field(mesh, bc, U_c), nu, dt, 1, _config(limiter), order=3, source=s_dev)()
+                got1 = momentum_step(G.fresh_field(mesh, bc, U_c), nu, dt, G.config(limiter), order=1, source=s_dev)()
+                got3 = momentum_march(G.fresh_field(mesh, bc, U_c), nu, dt, 1, G.config(limiter), order=3, source=s_dev)()
                 for what, got, want in (("step", got1, want1), ("march3", got3, want3)):
                     if not bit_equal(got, want):
                         bad.append((bcname, sname, what, opts, float((got.cpu() - want).abs().max())))
@@ -179,8 +155,8 @@ def test_exact_shift(fastpath, dtype):
                     ints = torch.randint(-8, 9, (n[axis],), generator=g)
                     ints[ints == 0] = 3                                 # a speed of its own on the other axes: not zero
                     U[c] = ints.to(U.dtype).reshape(shape).expand(*n)
-            f = _field(mesh, bc, U)
-            got = momentum_step(f, 0.0, 1.0, _config("upwind"), order=1)().cpu()
+            f = G.fresh_field(mesh, bc, U)
+            got = momentum_step(f, 0.0, 1.0, G.config("upwind"), order=1)().cpu()
             sl = tuple(inner if q == axis else slice(None) for q in range(3))
             for c in range(3):
                 want = U[c] if c == axis else torch.roll(U[c], 1 if sign > 0 else -1, axis)
@@ -198,10 +174,10 @@ def test_frozen_mode_is_one_scalar_march_per_component(order, limiter):
     n, dtype, bcname, nsteps = [9, 14, 132], "double", "mix", 3
     mesh, bc, om, obcs, per_comp, U_c, src_c, vel_c, nu, dt = _setup(n, dtype, bcname)
     types = BCS[bcname][1]
-    cfg = _config(limiter)
+    cfg = G.config(limiter)
     vd = vel_c.cuda()
     for sname, s_ref, s_dev in _sources(src_c)[:2]:
-        f = _field(mesh, bc, U_c, time=True)
+        f = G.fresh_field(mesh, bc, U_c, time=True)
         g = momentum_march(f, nu, dt, nsteps, cfg, order=order, u=vd, source=s_dev)
         assert g is f and abs(float(f.t) - (1.5 + nsteps * dt)) <= 1e-12
         for c in range(3):
@@ -213,7 +189,7 @@ def test_frozen_mode_is_one_scalar_march_per_component(order, limiter):
         assert bit_equal(f(), want)
     # the tuple of numbers and the vector Field are the same call
     want = MR.march(U_c, nu, dt, 1, om, obcs, limiter, order, None, u=[0.9, -0.8, 0.4])
-    assert bit_equal(momentum_step(_field(mesh, bc, U_c), nu, dt, cfg, order=order, u=(0.9, -0.8, 0.4))(), want)
+    assert bit_equal(momentum_step(G.fresh_field(mesh, bc, U_c), nu, dt, cfg, order=order, u=(0.9, -0.8, 0.4))(), want)
 
 
 # ---- the march is its pieces ----------------------------------------------------------------------------------------
@@ -223,7 +199,7 @@ def _march_by_stages(mesh, f, U, kind, nu, dt, order, nsteps, sources):
     ctx = context_for(mesh)
     nd = U.shape[0]
 
-    def stage(V, V0, c0c1):
+    def stage(V, V0, c0, c1):
         frozen = V.clone()
         vel = [frozen[a] for a in range(nd)]
         out = torch.empty_like(V)
@@ -233,41 +209,26 @@ def _march_by_stages(mesh, f, U, kind, nu, dt, order, nsteps, sources):
             if V0 is None:
                 ctx.euler_step_vel(V[c], out[c], kind, vel, nu, dt, source=s)
             else:
-                ctx.rk_stage_vel(V[c], V0[c], out[c], c0c1[0], c0c1[1], kind, vel, nu, dt, source=s)
+                ctx.rk_stage_vel(V[c], V0[c], out[c], c0, c1, kind, vel, nu, dt, source=s)
         return out
 
-    for _ in range(nsteps):
-        U0 = U
-        U = stage(U0, None, None)
-        for c0c1 in SSP_STAGES[order]:
-            U = stage(U, U0, c0c1)
-    return U
+    return G.march_by_stages(lambda U0: stage(U0, None, None, None), stage, U, order, nsteps)
 
 
 @pytest.mark.parametrize("order", [2, 3])
 @pytest.mark.parametrize("n,dtype,limiter", [([9, 14, 260], "single", "upwind"), ([6, 7, 9], "double", "quick")], ids=["vector", "generic"])
 def test_march_is_its_pieces(n, dtype, limiter, order):
     mesh, bc, om, obcs, _, U_c, src_c, _, nu, dt = _setup(n, dtype, "mix")
-    kind, cfg, nsteps = div_kind(limiter, False), _config(limiter), 2
+    kind, cfg, nsteps = div_kind(limiter, False), G.config(limiter), 2
     for sname, s_ref, s_dev in _sources(src_c)[:2]:
-        f = _field(mesh, bc, U_c)
+        f = G.fresh_field(mesh, bc, U_c)
         momentum_march(f, nu, dt, nsteps, cfg, order=order, source=s_dev)
-        pieces = _march_by_stages(mesh, _field(mesh, bc, U_c), U_c.cuda(), kind, nu, dt, order, nsteps, s_dev)
+        pieces = _march_by_stages(mesh, G.fresh_field(mesh, bc, U_c), U_c.cuda(), kind, nu, dt, order, nsteps, s_dev)
         assert bit_equal(f(), pieces), (sname, float((f() - pieces).abs().max()))
         assert bit_equal(f(), MR.march(U_c, nu, dt, nsteps, om, obcs, limiter, order, s_ref))
 
 
 # ---- routing --------------------------------------------------------------------------------------------------------
-def _child(code):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pre = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, PYAPES_HIP_DEBUG="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(root, "oracle"), os.environ.get("PYTHONPATH", "")]))
-    r = subprocess.run([sys.executable, "-c", pre + code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
 # name, mesh, dtype, BCs, limiter, source, options -> kernel, and whether the log names the own axis.  The launch log is limited
 # per k_sf instantiation (8 lines): every k_sf route uses instantiations of its own (dtype x VEL x source)
 ROUTES = [
@@ -286,11 +247,11 @@ def route_case(name):
     """one order-2 step of the named route -- an Euler step and a stage per component -- on a fresh mesh"""
     _, n, dtype, bcname, limiter, source, options, _, _ = next(r for r in ROUTES if r[0] == name)
     _, bc, _, _, _, U_c, src_c, _, nu, dt = _setup(n, dtype, bcname)
-    mesh = Mesh(_box(len(n)), None, list(n), "cuda", dtype)
+    mesh = Mesh(G.box(len(n)), None, list(n), "cuda", dtype)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
     s_dev = {s[0]: s[2] for s in _sources(src_c)}[source]
-    return momentum_step(_field(mesh, bc, U_c), nu, dt, _config(limiter), order=2, source=s_dev)()
+    return momentum_step(G.fresh_field(mesh, bc, U_c), nu, dt, G.config(limiter), order=2, source=s_dev)()
 
 
 def test_every_case_runs_on_the_kernel_it_is_meant_for():
@@ -300,18 +261,11 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
             "    torch.cuda.synchronize(); sys.stderr.write('CASE %s\\n' % r[0]); sys.stderr.flush()\n"
             "    T.route_case(r[0])\n"
             "    torch.cuda.synchronize(); sys.stderr.flush()\n")
-    log = _child(code)
-    seen, cur = {}, None
-    for ln in log.splitlines():
-        if ln.startswith("CASE "):
-            cur = ln[5:].strip()
-            seen[cur] = []
-        elif cur is not None and ("k_sf" in ln or "k_euler" in ln or "k_cg3d" in ln):
-            seen[cur].append(ln)
+    seen = G.case_log(G.child(code), lambda ln: "k_sf" in ln or "k_euler" in ln or "k_cg3d" in ln)
     for name, n, dtype, bcname, limiter, source, options, kernel, own in ROUTES:
         nd = len(n)
         lines = seen.get(name)
-        assert lines is not None and len(lines) == 2 * nd, (name, lines, log[-2000:])
+        assert lines is not None and len(lines) == 2 * nd, (name, lines, sorted(seen))
         for q, ln in enumerate(lines):
             comp, stage = q % nd, q >= nd
             assert kernel + " " in ln and "k_cg3d" not in ln and "k_sfq" not in ln, (name, ln)
@@ -326,17 +280,13 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
 
 
 # ---- errors ---------------------------------------------------------------------------------------------------------
-def _ptr(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
-
-
 def test_c_abi_errors_leave_the_context_usable():
     n, dtype = [9, 14, 132], "double"
     _, bc, om, obcs, per_comp, U_c, src_c, vel_c, nu, dt = _setup(n, dtype, "mix")
     types = BCS["mix"][1]
-    mesh = Mesh(_box(3), None, list(n), "cuda", dtype)   # a context of its own
+    mesh = Mesh(G.box(3), None, list(n), "cuda", dtype)   # a context of its own
     ctx = context_for(mesh)
-    f = _field(mesh, bc, U_c)
+    f = G.fresh_field(mesh, bc, U_c)
     ctx.bind_bcs(f(), f.bcs, 0)
     lib, h = ctx.lib, ctx.h
     kind = div_kind("upwind", False)
@@ -375,9 +325,9 @@ def test_c_abi_errors_leave_the_context_usable():
         bv[c] = ctx.bc_values(f(), f.bcs, c)[0]
     final = C.c_int(-1)
     for ncomp in (2, 1, 4):
-        assert lib.pa_momentum_march(h, _ptr(U), _ptr(w1), _ptr(w2), ncomp, 3, kind, None, nu, dt, 2, C.byref(final), None, bv) == L.PA_E_ARG
-    assert lib.pa_momentum_march(h, _ptr(U), _ptr(w1), _ptr(w2), 3, 4, kind, None, nu, dt, 2, C.byref(final), None, bv) == L.PA_E_ARG
-    assert lib.pa_momentum_march(h, _ptr(U), _ptr(w1), _ptr(w2), 3, 3, kind, None, nu, dt, 2, C.byref(final), None, None) == L.PA_E_ARG
+        assert lib.pa_momentum_march(h, G.ptr(U), G.ptr(w1), G.ptr(w2), ncomp, 3, kind, None, nu, dt, 2, C.byref(final), None, bv) == L.PA_E_ARG
+    assert lib.pa_momentum_march(h, G.ptr(U), G.ptr(w1), G.ptr(w2), 3, 4, kind, None, nu, dt, 2, C.byref(final), None, bv) == L.PA_E_ARG
+    assert lib.pa_momentum_march(h, G.ptr(U), G.ptr(w1), G.ptr(w2), 3, 3, kind, None, nu, dt, 2, C.byref(final), None, None) == L.PA_E_ARG
     assert final.value == -1
     good()
     # aliased or overlapping buffers
@@ -408,7 +358,7 @@ def test_c_abi_errors_leave_the_context_usable():
     assert code_of(lambda: march(U, w1, w2, k=div_kind("upwind", True))) == L.PA_E_ARG
     good()
     # a 1-D mesh, an axisymmetric mesh: PA_E_ARG; a slab: PA_E_STATE
-    line = Mesh(_box(1), None, [33], "cuda", "double")
+    line = Mesh(G.box(1), None, [33], "cuda", "double")
     lf = Field("U", 1, line, {"domain": mixed_bcs([0.0, 1.0], ["dirichlet"] * 2), "obstacle": None})
     l0, l1, l2 = (torch.zeros((1, 33), dtype=torch.float64, device="cuda") for _ in range(3))
     assert code_of(lambda: context_for(line).momentum_march(l0, l1, l2, 3, kind, None, nu, dt, 2, None, lf.bcs)) == L.PA_E_ARG
@@ -429,5 +379,5 @@ def test_c_abi_errors_leave_the_context_usable():
     # and a plain scalar march on the same context still gives its reference bits
     phi = Field("phi", 1, mesh, _scalar_bc(per_comp, types, 2))
     phi.set_var_tensor(U_c[2:3].cuda())
-    rk_march(phi, (vd[0], vd[1], vd[2]), nu, dt, 2, _config("upwind"), order=3)
+    rk_march(phi, (vd[0], vd[1], vd[2]), nu, dt, 2, G.config("upwind"), order=3)
     assert bit_equal(phi(), R.march(U_c[2:3], [vel_c[a] for a in range(3)], nu, dt, 2, om, obcs[2], "upwind", 3))

@@ -1,7 +1,7 @@
 """-m gpu: the QUICK advection scheme, Div limiter "quick" (PA_OP_DIV_QUICK: the generic kernels of csrc/pa_device.h, the
 marching kernel k_sfq of csrc/pa_sfq_kernel.h).
 
-The yardstick of the BITS is tests/quick_ref.py, the torch-CPU restatement of the definition: FDC.div at every node and one
+The yardstick of the BITS is tests/march_ref.py, the torch-CPU restatement of the definition: FDC.div at every node and one
 euler_step must equal it bit for bit, fp32 and fp64, on k_sfq and on the generic kernel.  A fused Runge-Kutta stage must be
 euler_step + three torch ops + apply_bcs, the march must be its stages, no kernel switch may change a bit, and the facts
 tests/test_quick_host.py establishes on the CPU must hold through rk_march on the GPU with the same bounds.
@@ -10,33 +10,30 @@ tests/test_quick_host.py establishes on the CPU must hold through rk_march on th
 four rows of nodes that the other march suites use, [16, 4, 32], therefore appears here among the ERRORS, and [16, 5, 32]
 stands in for it among the k_sfq cases: the smallest row count that runs, halo rows +-2 wrapping inside the tile.)
 """
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+import march_gpu as G
+import march_ref as Q
 import pyapes_oracle as O
-import quick_ref as Q
 import test_gpu_rk as R
 import test_quick_host as H
 import test_self_march_host as HS
 from helpers import bit_equal
+from march_gpu import XPER
 from pyapes_amd.geometry import Box, Cylinder
 from pyapes_amd.hip import lib as L
 from pyapes_amd.hip.context import context_for
 from pyapes_amd.hip.lib import PaError
 from pyapes_amd.mesh import Mesh
 from pyapes_amd.solver.fdc import FDC
-from pyapes_amd.solver.march import SSP_STAGES, euler_march, euler_step, rk_march, rk_step
+from pyapes_amd.solver.march import euler_march, euler_step, rk_march, rk_step
 from pyapes_amd.variables import Field
 from pyapes_amd.variables.bcs import mixed_bcs
 
 pytestmark = pytest.mark.gpu
 
 QUICK = {"div": {"limiter": "quick"}}
-XPER = ([None, None, 0.25, -0.5, 2.0, 0.0], ["periodic", "periodic", "dirichlet", "dirichlet", "dirichlet", "dirichlet"])
 
 # name, n, dtype, bcs, u ("field": a randn speed tensor, "self": the field itself), operands misaligned, context options,
 # the kernel the Euler step must run on
@@ -109,7 +106,7 @@ def test_div_and_euler_step_are_the_restatement_bit_for_bit(name):
     om, ob = _oracle_side(name, mesh)
     x = phis.cpu().clone()
     uc = u.cpu().clone() if isinstance(u, torch.Tensor) else u
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     if phis.data_ptr() % 16 != 0:
         f.set_var_tensor(phis)                       # keep the misaligned storage
     d = FDC(QUICK).div(u if not isinstance(u, torch.Tensor) else u.clone(), f)
@@ -120,26 +117,16 @@ def test_div_and_euler_step_are_the_restatement_bit_for_bit(name):
     ctx.bind_bcs(f(), f.bcs, 0)
     out = torch.full_like(phis, float("nan"))
     ctx.euler_step(phis[0], out[0], L.OP_DIV_QUICK, u, nu, dt)     # (u is phis itself in the self cases)
-    ref = Q.euler_step_quick(x, uc, nu, dt, om, ob)
+    ref = Q.euler_step(x, uc, nu, dt, om, ob, "quick")
     assert bit_equal(out, ref), ("euler_step", float((out.cpu() - ref).abs().max()), int((out.cpu() != ref).sum()))
-    g = euler_step(R._field(mesh, bc, phis), u, nu, dt, QUICK)     # the public entry
+    g = euler_step(G.fresh_field(mesh, bc, phis), u, nu, dt, QUICK)     # the public entry
     assert bit_equal(g(), ref)
-
-
-def _child(code):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pre = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, PYAPES_HIP_DEBUG="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(root, "oracle"), os.environ.get("PYTHONPATH", "")]))
-    r = subprocess.run([sys.executable, "-c", pre + code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
 
 
 def _step_and_stage(name):
     mesh, bc, phis, phi0, u, nu, dt = _setup(name)
     ctx = context_for(mesh)
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     ctx.bind_bcs(f(), f.bcs, 0)
     out = torch.empty_like(phis)
     ctx.euler_step(phis[0], out[0], L.OP_DIV_QUICK, u, nu, dt)
@@ -153,15 +140,8 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
             "    torch.cuda.synchronize(); sys.stderr.write('CASE %s\\n' % name); sys.stderr.flush()\n"
             "    T._step_and_stage(name)\n"
             "    torch.cuda.synchronize(); sys.stderr.flush()\n")
-    log = _child(code)
-    seen, cur = {}, None
-    for ln in log.splitlines():
-        if ln.startswith("CASE "):
-            cur = ln[5:].strip()
-            seen[cur] = []
-        elif cur is not None and "[pyapes_hip]" in ln and ("k_sfq" in ln or "k_euler" in ln or "k_sf " in ln or "k_cg3d" in ln
-                                                           or "k_rk_combine" in ln):
-            seen[cur].append(ln)
+    kernels = ("k_sfq", "k_euler", "k_sf ", "k_cg3d", "k_rk_combine")
+    seen = G.case_log(G.child(code), lambda ln: "[pyapes_hip]" in ln and any(k in ln for k in kernels))
     for name, n, dtype, bcs, u, *_, kernel in CASES:
         lines = seen[name]
         assert not any("k_sf " in ln or "k_cg3d" in ln for ln in lines), (name, lines)   # the other tiled paths decline the kind
@@ -199,7 +179,7 @@ def rows_per_wave_case():
             mesh, bc, phis, phi0, u, nu, dt = _setup(name)
             ctx = context_for(mesh)
             ctx.set_option("sfq", rows)
-            f = R._field(mesh, bc, phis)
+            f = G.fresh_field(mesh, bc, phis)
             ctx.bind_bcs(f(), f.bcs, 0)
             a, b = torch.full_like(phis, float("nan")), torch.full_like(phis, float("nan"))
             ctx.euler_step(phis[0], a[0], L.OP_DIV_QUICK, u, nu, dt)
@@ -211,9 +191,9 @@ def rows_per_wave_case():
 
 
 def test_rows_per_wave():
-    log = _child("import torch\nimport test_gpu_quick as T\n"
-                 "w = T.rows_per_wave_case(); torch.cuda.synchronize()\n"
-                 "assert all(w.values()), w\n")
+    log = G.child("import torch\nimport test_gpu_quick as T\n"
+                  "w = T.rows_per_wave_case(); torch.cuda.synchronize()\n"
+                  "assert all(w.values()), w\n")
     lines = [ln for ln in log.splitlines() if "k_sfq " in ln]
     assert len(lines) == 16, log[-3000:]             # four cases x (two rows, four rows) x (step, stage)
     assert sum(" RJ 2 " in ln for ln in lines) == 8 and sum(" RJ 4 " in ln for ln in lines) == 8, lines
@@ -240,32 +220,32 @@ def test_march_is_its_stages(name, order):
     import test_gpu_self_march as S
     mesh, bc, phis, _, u, nu, dt = _setup(name)
     for nsteps in (1, 2, 3, 5):
-        f = R._field(mesh, bc, phis, time=True)
+        f = G.fresh_field(mesh, bc, phis, time=True)
         assert rk_march(f, u, nu, dt, nsteps, QUICK, order=order) is f
         ref = R._march_by_stages(mesh, bc, QUICK, phis, u, nu, dt, order, nsteps)
         assert bit_equal(f(), ref), (nsteps, float((f() - ref).abs().max()))
         assert abs(float(f.t) - (1.5 + nsteps * dt)) <= 1e-12
         if order == 1:
-            assert bit_equal(euler_march(R._field(mesh, bc, phis), u, nu, dt, nsteps, QUICK)(), ref)
+            assert bit_equal(euler_march(G.fresh_field(mesh, bc, phis), u, nu, dt, nsteps, QUICK)(), ref)
         # the field advects itself: every stage by its own input
-        g = R._field(mesh, bc, phis, time=True)
+        g = G.fresh_field(mesh, bc, phis, time=True)
         assert rk_march(g, g, nu, dt, nsteps, QUICK, order=order) is g
         sref = S._self_march_by_pieces(mesh, bc, QUICK, phis, nu, dt, order, nsteps)
         assert bit_equal(g(), sref), (nsteps, float((g() - sref).abs().max()))
         assert abs(float(g.t) - (1.5 + nsteps * dt)) <= 1e-12
-    f = rk_step(R._field(mesh, bc, phis), u, nu, dt, QUICK, order=order)
+    f = rk_step(G.fresh_field(mesh, bc, phis), u, nu, dt, QUICK, order=order)
     assert bit_equal(f(), R._march_by_stages(mesh, bc, QUICK, phis, u, nu, dt, order, 1))
 
 
 def test_march_equals_the_restatement():
-    """three order-3 steps, frozen speed and self-advected, against the CPU march of tests/quick_ref.py"""
+    """three order-3 steps, frozen speed and self-advected, against the CPU march of tests/march_ref.py"""
     for name in ("sfq_f64_mixed", "sfq_f32_config4"):
         mesh, bc, phis, _, u, nu, dt = _setup(name)
         om, ob = _oracle_side(name, mesh)
-        a = rk_march(R._field(mesh, bc, phis), u, nu, dt, 3, QUICK, order=3)()
-        assert bit_equal(a, Q.march_quick(phis.cpu().clone(), u, nu, dt, 3, om, ob, 3))
-        g = R._field(mesh, bc, phis)
-        assert bit_equal(rk_march(g, g, nu, dt, 3, QUICK, order=3)(), Q.march_quick(phis.cpu().clone(), None, nu, dt, 3, om, ob, 3, True))
+        a = rk_march(G.fresh_field(mesh, bc, phis), u, nu, dt, 3, QUICK, order=3)()
+        assert bit_equal(a, Q.march(phis.cpu().clone(), u, nu, dt, 3, om, ob, "quick", 3))
+        g = G.fresh_field(mesh, bc, phis)
+        assert bit_equal(rk_march(g, g, nu, dt, 3, QUICK, order=3)(), Q.march(phis.cpu().clone(), None, nu, dt, 3, om, ob, "quick", 3, self_adv=True))
 
 
 # ---- 5. switches ----------------------------------------------------------------------------------------------------
@@ -273,7 +253,7 @@ def _march_with(name, options, self_adv=False):
     mesh, bc, phis, _, u, nu, dt = _setup(name)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     rk_march(f, f if self_adv else u, nu, dt, 4, QUICK, order=3)
     return f().clone()
 
@@ -347,7 +327,7 @@ def test_order_in_time_on_the_gpu(order, self_adv):
     nu, T = 0.05, 0.02
 
     def march(n, o):
-        f = R._field(mesh, bc, phi0)
+        f = G.fresh_field(mesh, bc, phi0)
         return rk_march(f, f if self_adv else 1.0, nu, T / n, n, QUICK, order=o)().clone()
 
     ref = march(640, 3)
@@ -377,7 +357,7 @@ def test_burgers_on_the_gpu():
 def test_errors_leave_the_context_usable():
     mesh, bc, phis, phi0, u, nu, dt = _setup("sfq_f64_mixed")
     ctx = context_for(mesh)
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     # an axis of 4 nodes: PA_E_ARG from every entry point that takes the kind
     small = Mesh(Box[0:1, 0:1, 0:1], None, [16, 4, 32], "cuda", "double")
     sbc = {"domain": mixed_bcs(*R.MIXED), "obstacle": None}
@@ -424,7 +404,7 @@ def test_errors_leave_the_context_usable():
     with pytest.raises(PaError):
         ctx.div_general(L.OP_DIV_QUICK, False, [phis[0]] * 3, 1.0, [None] * 3, [None] * 3, torch.empty_like(phis[0]))
     # the context that saw the errors still marches, and gives what a fresh one gives
-    a = rk_march(R._field(mesh, bc, phis), u, nu, dt, 2, QUICK)().clone()
+    a = rk_march(G.fresh_field(mesh, bc, phis), u, nu, dt, 2, QUICK)().clone()
     mesh_b, bc_b, phis_b, _, _, _, _ = _setup("sfq_f64_mixed")
-    b = rk_march(R._field(mesh_b, bc_b, phis_b), u, nu, dt, 2, QUICK)()
+    b = rk_march(G.fresh_field(mesh_b, bc_b, phis_b), u, nu, dt, 2, QUICK)()
     assert bit_equal(phis, phis_b) and bit_equal(a, b)

@@ -10,14 +10,12 @@ periodic fill reads a face value before it rewrites it, csrc/pa_march.hip step_t
 bits, and the facts tests/test_rk_host.py establishes on the CPU (order in time, stability of central advection) must hold
 through rk_march on the GPU with the same bounds.
 """
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
+import march_gpu as G
 from helpers import bit_equal
+from march_gpu import ALLDIR, MIXED
 from pyapes_amd.geometry import Box
 from pyapes_amd.hip.context import context_for
 from pyapes_amd.hip.lib import PaError
@@ -30,8 +28,6 @@ pytestmark = pytest.mark.gpu
 
 NEUSYM = ([0.0, 0.0, None, None, None, None], ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"])
 ALLNEU = ([0.3, -0.2, 0.1, 0.0, -0.4, 0.25], ["neumann"] * 6)
-MIXED = ([0.5, 0.1, None, 1.0, -0.3, None], ["dirichlet", "neumann", "symmetry", "dirichlet", "neumann", "symmetry"])
-ALLDIR = ([0.0, 1.0, 0.25, -0.5, 2.0, 0.0], ["dirichlet"] * 6)
 YPER = ([0.5, 0.1, None, None, -0.3, None], ["dirichlet", "neumann", "periodic", "periodic", "neumann", "symmetry"])
 DIRPER = ([0.0, 1.0, None, None, None, None], ["dirichlet", "dirichlet", "periodic", "periodic", "periodic", "periodic"])
 DIR2D = ([0.0, 1.0, 0.25, -0.5], ["dirichlet"] * 4)
@@ -75,14 +71,10 @@ CASES = [
 CASE = {c[0]: c for c in CASES}
 
 
-def _box(nd):
-    return Box[0:1] if nd == 1 else (Box[0:1, 0:1] if nd == 2 else Box[0:1, 0:1, 0:1])
-
-
 def _setup(name, seed=9):
     """mesh, BC config, (phi_s, phi0) BC-filled fields' tensors, the speed, nu, dt"""
     _, n, dtype, bcs, config, u, misaligned, options, _ = CASE[name]
-    mesh = Mesh(_box(len(n)), None, n, "cuda", dtype)
+    mesh = Mesh(G.box(len(n)), None, n, "cuda", dtype)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
     g = torch.Generator().manual_seed(seed)
@@ -156,16 +148,6 @@ def test_stage_is_the_composition_bit_for_bit(name):
     assert run_stage_case(name) is None
 
 
-def _child(code):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pre = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, PYAPES_HIP_DEBUG="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(root, "oracle"), os.environ.get("PYTHONPATH", "")]))
-    r = subprocess.run([sys.executable, "-c", pre + code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
 def test_every_case_runs_on_the_kernel_it_is_meant_for():
     """the launch log (PYAPES_HIP_DEBUG=1) of one fused stage per case, in ONE child process (the log is limited per kernel
     instantiation, so every case prints a marker line first and only the lines behind it are read)"""
@@ -175,14 +157,7 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
             "    torch.cuda.synchronize(); sys.stderr.write('CASE %s\\n' % c[0]); sys.stderr.flush()\n"
             "    R._fused(mesh, bc, config, phis, phi0, 0.75, 0.25, u, nu, dt)\n"
             "    torch.cuda.synchronize(); sys.stderr.flush()\n")
-    log = _child(code)
-    seen, cur = {}, None
-    for ln in log.splitlines():
-        if ln.startswith("CASE "):
-            cur = ln[5:].strip()
-            seen[cur] = []
-        elif cur is not None and "(RK stage" in ln:
-            seen[cur].append(ln)
+    seen = G.case_log(G.child(code), lambda ln: "(RK stage" in ln)
     kernels_hit = set()
     for name, *_, kernel in CASES:
         lines = seen.get(name, [])
@@ -191,11 +166,11 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
             continue
         assert len(lines) == 1 and kernel + " " in lines[0], (name, kernel, lines)
         kernels_hit.add(kernel)
-    assert kernels_hit == {"k_sf", "k_cg3d", "k_euler", "k_rk_combine"}, log[-3000:]
+    assert kernels_hit == {"k_sf", "k_cg3d", "k_euler", "k_rk_combine"}, seen
     # the cases that exist to show a fall-back must have been seen themselves
     for name in ("cg3d_f32_phi0_misaligned", "cg3d_f64_phi0_misaligned", "cg3d_f32_odd_rows", "cg3d_f64_2d", "euler_f64_1d",
                  "euler_f64_central_field", "sf_f32_config4", "sf_f64_allneu_uneg"):
-        assert seen.get(name), (name, log[-3000:])
+        assert seen.get(name), (name, seen)
 
 
 # ---- march = stages -------------------------------------------------------------------------------------------------
@@ -203,30 +178,23 @@ MARCH_CASES = ["sf_f32_config4", "sf_f64_mixed", "sf_f64_yperiodic", "cg3d_f32_o
                "sf_f32_speed_field", "sf_f64_central"]
 
 
-def _field(mesh, bc, t, time=False):
-    f = Field("phi", 1, mesh, bc)
-    f.set_var_tensor(t.clone())
-    if time:
-        f.set_time(0.0, 1.5)
-    return f
-
-
 def _march_by_stages(mesh, bc, config, phi, u, nu, dt, order, nsteps):
     from pyapes_amd.solver.fdc import div_kind
     cfg = config["div"]
     kind = div_kind(cfg["limiter"], bool(cfg.get("compat", False)))
     ctx = context_for(mesh)
-    for _ in range(nsteps):
-        phi0 = phi.clone()
-        cur = euler_step(_field(mesh, bc, phi0), u, nu, dt, config)().clone()
-        for c0, c1 in SSP_STAGES[order]:
-            f = _field(mesh, bc, cur)
-            ctx.bind_bcs(f(), f.bcs, 0)
-            out = torch.empty_like(cur)
-            ctx.rk_stage(cur[0], phi0[0], out[0], c0, c1, kind, u, nu, dt)
-            cur = out
-        phi = cur
-    return phi
+
+    def step(phi0):
+        return euler_step(G.fresh_field(mesh, bc, phi0), u, nu, dt, config)().clone()
+
+    def stage(cur, phi0, c0, c1):
+        f = G.fresh_field(mesh, bc, cur)
+        ctx.bind_bcs(f(), f.bcs, 0)
+        out = torch.empty_like(cur)
+        ctx.rk_stage(cur[0], phi0[0], out[0], c0, c1, kind, u, nu, dt)
+        return out
+
+    return G.march_by_stages(step, stage, phi, order, nsteps)
 
 
 @pytest.mark.parametrize("name", MARCH_CASES)
@@ -234,20 +202,20 @@ def _march_by_stages(mesh, bc, config, phi, u, nu, dt, order, nsteps):
 def test_march_is_its_stages(name, order):
     mesh, bc, config, phis, _, u, nu, dt = _setup(name)
     for nsteps in (1, 2, 3, 5):
-        f = _field(mesh, bc, phis, time=True)
+        f = G.fresh_field(mesh, bc, phis, time=True)
         g = rk_march(f, u, nu, dt, nsteps, config, order=order)
         assert g is f                                    # the field handed in holds the result ...
         ref = _march_by_stages(mesh, bc, config, phis, u, nu, dt, order, nsteps)
         assert bit_equal(f(), ref), (nsteps, float((f() - ref).abs().max()))   # ... i.e. the right one of the three buffers
         assert f().shape == phis.shape and f().is_contiguous()
         if order == 1:
-            e = euler_march(_field(mesh, bc, phis), u, nu, dt, nsteps, config)
+            e = euler_march(G.fresh_field(mesh, bc, phis), u, nu, dt, nsteps, config)
             assert bit_equal(f(), e())
         assert abs(float(f.t) - (1.5 + nsteps * dt)) <= 1e-12
-        g = rk_march(_field(mesh, bc, phis), u, nu, dt, nsteps, config, order=order)   # no time set: nothing to advance
+        g = rk_march(G.fresh_field(mesh, bc, phis), u, nu, dt, nsteps, config, order=order)   # no time set: nothing to advance
         assert bit_equal(g(), ref)
     # one step through rk_step
-    f = rk_step(_field(mesh, bc, phis), u, nu, dt, config, order=order)
+    f = rk_step(G.fresh_field(mesh, bc, phis), u, nu, dt, config, order=order)
     assert bit_equal(f(), _march_by_stages(mesh, bc, config, phis, u, nu, dt, order, 1))
 
 
@@ -256,7 +224,7 @@ def _march_with(name, options, order, nsteps):
     mesh, bc, config, phis, _, u, nu, dt = _setup(name)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
-    f = _field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     rk_march(f, u, nu, dt, nsteps, config, order=order)
     return f().clone()
 
@@ -277,16 +245,15 @@ def test_bc_on_load_is_taken_for_all_stages_and_declined_with_a_periodic_face():
             "R._march_with('sf_f32_config4', {}, 3, 2); torch.cuda.synchronize()\n"
             "sys.stderr.write('CASE b\\n'); sys.stderr.flush()\n"
             "R._march_with('sf_f64_yperiodic', {}, 3, 2); torch.cuda.synchronize()\n")
-    log = _child(code)
-    a, b = log.split("CASE a\n")[1].split("CASE b\n")
-    la = [ln for ln in a.splitlines() if "k_sf phase 3" in ln]
-    lb = [ln for ln in b.splitlines() if "k_sf phase 3" in ln]
+    seen = G.case_log(G.child(code), lambda ln: "k_sf phase 3" in ln or "k_rk_combine (RK stage" in ln)
+    la = [ln for ln in seen["a"] if "k_sf phase 3" in ln]
+    lb = [ln for ln in seen["b"] if "k_sf phase 3" in ln]
     # two steps of three launches: two Euler launches and four fused stages, every one in the BC-on-load form
-    assert len(la) == 6 and all("(BC on load)" in ln for ln in la), a
-    assert sum("(RK stage)" in ln for ln in la) == 4, a
+    assert len(la) == 6 and all("(BC on load)" in ln for ln in la), la
+    assert sum("(RK stage)" in ln for ln in la) == 4, la
     # a periodic face: no BC on load, and every stage is the step kernel + the combine kernel
-    assert len(lb) == 6 and not any("(BC on load)" in ln or "(RK stage)" in ln for ln in lb), b
-    assert sum("k_rk_combine (RK stage" in ln for ln in b.splitlines()) == 4, b
+    assert len(lb) == 6 and not any("(BC on load)" in ln or "(RK stage)" in ln for ln in lb), lb
+    assert sum("k_rk_combine (RK stage" in ln for ln in seen["b"]) == 4, seen["b"]
 
 
 # ---- the CPU facts of tests/test_rk_host.py, through rk_march -------------------------------------------------------
@@ -308,8 +275,8 @@ def _pulse_case():
 def test_order_in_time_on_the_gpu(order, config):
     mesh, bc, phi0 = _pulse_case()
     u, nu, T = 1.0, 0.05, 0.02
-    ref = rk_march(_field(mesh, bc, phi0), u, nu, T / 640, 640, config, order=3)().clone()
-    err = [float((rk_march(_field(mesh, bc, phi0), u, nu, T / n, n, config, order=order)() - ref).abs().max())
+    ref = rk_march(G.fresh_field(mesh, bc, phi0), u, nu, T / 640, 640, config, order=3)().clone()
+    err = [float((rk_march(G.fresh_field(mesh, bc, phi0), u, nu, T / n, n, config, order=order)() - ref).abs().max())
            for n in (20, 40, 80)]
     ratios = (err[0] / err[1], err[1] / err[2])
     print(f"order {order}: errors {err}, ratios {ratios}")
@@ -325,7 +292,7 @@ def test_central_advection_without_diffusion_on_the_gpu():
     ends = {}
     for cfl, steps in ((1.0, 8), (1.5, 5)):
         for order in (1, 2, 3):
-            ends[cfl, order] = float(rk_march(_field(mesh, bc, phi0), 1.0, 0.0, cfl * dx, steps, CENTRAL, order=order)().abs().max())
+            ends[cfl, order] = float(rk_march(G.fresh_field(mesh, bc, phi0), 1.0, 0.0, cfl * dx, steps, CENTRAL, order=order)().abs().max())
     print("max|phi| at the end:", ends)
     assert ends[1.0, 3] <= top and ends[1.5, 3] <= top, ends
     assert ends[1.0, 1] >= 2 * top, ends
@@ -336,7 +303,7 @@ def test_errors_leave_the_context_usable():
     from pyapes_amd.solver.fdc import div_kind
     mesh, bc, config, phis, phi0, u, nu, dt = _setup("sf_f64_mixed")
     ctx = context_for(mesh)
-    f = _field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     ctx.bind_bcs(f(), f.bcs, 0)
     kind = div_kind("upwind", False)
     out = torch.empty_like(phis)
@@ -353,9 +320,9 @@ def test_errors_leave_the_context_usable():
     with pytest.raises(PaError):
         ctx.rk_march(phis[0], out[0], torch.empty_like(out)[0], 3, 99, u, nu, dt, 2)     # bad Div kind
     with pytest.raises(ValueError):
-        rk_march(_field(mesh, bc, phis), u, nu, dt, 2, config, order=0)
+        rk_march(G.fresh_field(mesh, bc, phis), u, nu, dt, 2, config, order=0)
     with pytest.raises(ValueError):
-        rk_step(_field(mesh, bc, phis), u, nu, dt, config, order=4)
+        rk_step(G.fresh_field(mesh, bc, phis), u, nu, dt, config, order=4)
     vec = Field("v", 3, mesh, {"domain": mixed_bcs(*MIXED), "obstacle": None})
     with pytest.raises(NotImplementedError):
         rk_march(vec, u, nu, dt, 2, config)
@@ -371,7 +338,7 @@ def test_errors_leave_the_context_usable():
     with pytest.raises(NotImplementedError):
         rk_step(sf, u, nu, dt, config)
     # the context that saw the errors still steps, and gives what a fresh one gives
-    a = euler_step(_field(mesh, bc, phis), u, nu, dt, config)().clone()
+    a = euler_step(G.fresh_field(mesh, bc, phis), u, nu, dt, config)().clone()
     mesh_b, bc_b, _, phis_b, _, _, _, _ = _setup("sf_f64_mixed")
-    b = euler_step(_field(mesh_b, bc_b, phis_b), u, nu, dt, config)()
+    b = euler_step(G.fresh_field(mesh_b, bc_b, phis_b), u, nu, dt, config)()
     assert bit_equal(phis, phis_b) and bit_equal(a, b)

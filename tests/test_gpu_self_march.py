@@ -12,13 +12,11 @@ pointer for the whole call).  The facts tests/test_self_march_host.py establishe
 equation) must hold through rk_march on the GPU with the same bounds.
 """
 import math
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
+import march_gpu as G
 import test_gpu_rk as R
 import test_self_march_host as H
 from helpers import bit_equal
@@ -27,7 +25,7 @@ from pyapes_amd.hip.context import context_for
 from pyapes_amd.hip.lib import PaError
 from pyapes_amd.mesh import Mesh
 from pyapes_amd.solver.fdc import div_kind
-from pyapes_amd.solver.march import SSP_STAGES, euler_march, euler_step, rk_march, rk_step
+from pyapes_amd.solver.march import euler_march, euler_step, rk_march, rk_step
 from pyapes_amd.variables import Field
 from pyapes_amd.variables.bcs import mixed_bcs
 
@@ -115,16 +113,6 @@ def test_self_stage_is_the_stage_with_a_copy_as_speed_bit_for_bit(name):
     assert stage_mismatch(*_setup(name)) is None
 
 
-def _child(code):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pre = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, PYAPES_HIP_DEBUG="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(root, "oracle"), os.environ.get("PYTHONPATH", "")]))
-    r = subprocess.run([sys.executable, "-c", pre + code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
 def rj4_case():
     """[256, 512, 512] fp32, random data made on the GPU: upwind with the config-4 BCs, central all-dirichlet"""
     mesh = Mesh(Box[0:1, 0:1, 0:1], None, RJ4_SHAPE, "cuda", "single")
@@ -151,9 +139,9 @@ def rj4_case():
 
 
 def test_four_rows_per_wave():
-    log = _child("import torch\nimport test_gpu_self_march as S\n"
-                 "w = S.rj4_case(); torch.cuda.synchronize()\n"
-                 "assert all(w.values()), w\n")
+    log = G.child("import torch\nimport test_gpu_self_march as S\n"
+                  "w = S.rj4_case(); torch.cuda.synchronize()\n"
+                  "assert all(w.values()), w\n")
     lines = [ln for ln in log.splitlines() if "k_sf phase 3" in ln and "(self)" in ln]
     # Euler step and stage, upwind and central: four SELF instantiations, every one at four rows per wave
     assert len(lines) == 4 and all(" RJ 4" in ln for ln in lines), log[-3000:]
@@ -171,14 +159,7 @@ def test_paths():
             "    torch.cuda.synchronize(); sys.stderr.flush()\n"
             "sys.stderr.write('CASE march\\n'); sys.stderr.flush()\n"
             "S._march('sf_f32_neusym', {}, 3, 2); torch.cuda.synchronize()\n")
-    log = _child(code)
-    seen, cur = {}, None
-    for ln in log.splitlines():
-        if ln.startswith("CASE "):
-            cur = ln[5:].strip()
-            seen[cur] = []
-        elif cur is not None and "[pyapes_hip]" in ln:
-            seen[cur].append(ln)
+    seen = G.case_log(G.child(code), lambda ln: "[pyapes_hip]" in ln)
     for name, *_, kernel in CASES:
         lines = seen[name]
         stage = [ln for ln in lines if "(RK stage" in ln]
@@ -211,17 +192,18 @@ MARCH_CASES = ["sf_f32_neusym", "sf_f64_mixed", "sf_f64_mixed_compat", "sf_f64_c
 def _self_march_by_pieces(mesh, bc, config, phi, nu, dt, order, nsteps):
     ctx = context_for(mesh)
     kind = _kind(config)
-    for _ in range(nsteps):
-        phi0 = phi.clone()
-        cur = euler_step(R._field(mesh, bc, phi0), phi0.clone(), nu, dt, config)().clone()
-        for c0, c1 in SSP_STAGES[order]:
-            f = R._field(mesh, bc, cur)
-            ctx.bind_bcs(f(), f.bcs, 0)
-            out = torch.empty_like(cur)
-            ctx.rk_stage(cur[0], phi0[0], out[0], c0, c1, kind, cur.clone(), nu, dt)
-            cur = out
-        phi = cur
-    return phi
+
+    def step(phi0):
+        return euler_step(G.fresh_field(mesh, bc, phi0), phi0.clone(), nu, dt, config)().clone()
+
+    def stage(cur, phi0, c0, c1):
+        f = G.fresh_field(mesh, bc, cur)
+        ctx.bind_bcs(f(), f.bcs, 0)
+        out = torch.empty_like(cur)
+        ctx.rk_stage(cur[0], phi0[0], out[0], c0, c1, kind, cur.clone(), nu, dt)
+        return out
+
+    return G.march_by_stages(step, stage, phi, order, nsteps)
 
 
 @pytest.mark.parametrize("name", MARCH_CASES)
@@ -229,7 +211,7 @@ def _self_march_by_pieces(mesh, bc, config, phi, nu, dt, order, nsteps):
 def test_self_march_is_its_pieces(name, order):
     mesh, bc, config, phis, _, nu, dt = _setup(name)
     for nsteps in (1, 2, 3, 5):
-        f = R._field(mesh, bc, phis, time=True)
+        f = G.fresh_field(mesh, bc, phis, time=True)
         g = rk_march(f, f, nu, dt, nsteps, config, order=order)
         assert g is f
         ref = _self_march_by_pieces(mesh, bc, config, phis, nu, dt, order, nsteps)
@@ -237,21 +219,21 @@ def test_self_march_is_its_pieces(name, order):
         assert f().shape == phis.shape and f().is_contiguous()
         assert abs(float(f.t) - (1.5 + nsteps * dt)) <= 1e-12
         if order == 1:
-            e = R._field(mesh, bc, phis)
+            e = G.fresh_field(mesh, bc, phis)
             assert euler_march(e, e, nu, dt, nsteps, config) is e and bit_equal(e(), ref)
-        h = R._field(mesh, bc, phis)                     # the field's own tensor as the speed: self-advection as well
+        h = G.fresh_field(mesh, bc, phis)                     # the field's own tensor as the speed: self-advection as well
         assert bit_equal(rk_march(h, h(), nu, dt, nsteps, config, order=order)(), ref)
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     assert bit_equal(rk_step(f, f, nu, dt, config, order=order)(), _self_march_by_pieces(mesh, bc, config, phis, nu, dt, order, 1))
 
 
 def test_a_clone_is_a_frozen_speed_as_before():
     mesh, bc, config, phis, _, nu, dt = _setup("sf_f64_mixed")
     u = phis.clone()
-    a = rk_march(R._field(mesh, bc, phis), u, nu, dt, 3, config, order=3)()
+    a = rk_march(G.fresh_field(mesh, bc, phis), u, nu, dt, 3, config, order=3)()
     b = R._march_by_stages(mesh, bc, config, phis, u, nu, dt, 3, 3)
     assert bit_equal(a, b) and bit_equal(u, phis)
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     assert not bit_equal(rk_march(f, f, nu, dt, 3, config, order=3)(), a)
 
 
@@ -260,7 +242,7 @@ def _march(name, options, order, nsteps):
     mesh, bc, config, phis, _, nu, dt = _setup(name)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     rk_march(f, f, nu, dt, nsteps, config, order=order)
     return f().clone()
 
@@ -283,7 +265,7 @@ def test_order_in_time_of_the_self_march_on_the_gpu(order, config):
     nu, T = 0.05, 0.02
 
     def march(n, o):
-        f = R._field(mesh, bc, phi0)
+        f = G.fresh_field(mesh, bc, phi0)
         return rk_march(f, f, nu, T / n, n, config, order=o)().clone()
 
     ref = march(640, 3)
@@ -324,7 +306,7 @@ def test_burgers_upwind_on_the_gpu():
 def test_errors_leave_the_context_usable():
     mesh, bc, config, phis, phi0, nu, dt = _setup("sf_f64_mixed")
     ctx = context_for(mesh)
-    f = R._field(mesh, bc, phis)
+    f = G.fresh_field(mesh, bc, phis)
     ctx.bind_bcs(f(), f.bcs, 0)
     kind = div_kind("upwind", False)
     w1, w2 = torch.empty_like(phis), torch.empty_like(phis)
@@ -363,9 +345,9 @@ def test_errors_leave_the_context_usable():
     with pytest.raises(NotImplementedError):
         euler_march(vec, vec, nu, dt, 2, config)
     # the context that saw the errors still steps, and gives what a fresh one gives
-    g = R._field(mesh, bc, phis)
+    g = G.fresh_field(mesh, bc, phis)
     a = rk_march(g, g, nu, dt, 2, config)().clone()
     mesh_b, bc_b, _, phis_b, _, _, _ = _setup("sf_f64_mixed")
-    h = R._field(mesh_b, bc_b, phis_b)
+    h = G.fresh_field(mesh_b, bc_b, phis_b)
     b = rk_march(h, h, nu, dt, 2, config)()
     assert bit_equal(phis, phis_b) and bit_equal(a, b)

@@ -1,7 +1,7 @@
 """-m gpu: the source term S of the explicit steps and marches -- ``source=`` of euler_step / euler_march / rk_step / rk_march,
 pa_*_src at the C ABI, the SRC instantiations of k_sf and k_sfq and the generic k_euler.
 
-The yardstick is tests/source_ref.py, the step E_S restated on the CPU operation for operation
+The yardstick is tests/march_ref.py, the step E_S restated on the CPU operation for operation
     a = nu * lap;  a = a - adv;  a = a + s;  a = dt * a;  v = phi + a
 and the device must give its BITS: on every kernel path, for the three Div limiters, both signs of a scalar speed, a speed
 field, self-advection, Dirichlet and mixed faces, a source field and a scalar source, the Euler step and both fused stages of
@@ -15,35 +15,28 @@ itself -- are swept for the SRC instantiations in tests/test_gpu_chunks_terms.py
 read at the wrong cell: S = -(nu lap - adv)(phi*) makes phi* a fixed point bit for bit.
 """
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
+import march_gpu as G
+import march_ref as R
 import pyapes_oracle as O
-import source_ref as R
 from helpers import bit_equal
+from march_gpu import GENERIC, VECTOR, VECTOR_OPTIONS
 from pyapes_amd.geometry import Box, Cylinder
 from pyapes_amd.hip import lib as L
 from pyapes_amd.hip.context import context_for
 from pyapes_amd.hip.lib import PaError
 from pyapes_amd.mesh import Mesh
-from pyapes_amd.solver.fdc import div_kind
 from pyapes_amd.solver.march import SSP_STAGES, euler_march, euler_step, rk_march, rk_step
 from pyapes_amd.variables import Field
-from pyapes_amd.variables.bcs import mixed_bcs
 
 pytestmark = pytest.mark.gpu
 
-ALLDIR = ([0.0, 1.0, 0.25, -0.5, 2.0, 0.0], ["dirichlet"] * 6)
-MIXED = ([0.5, 0.1, None, 1.0, -0.3, None], ["dirichlet", "neumann", "symmetry", "dirichlet", "neumann", "symmetry"])
-XPER = ([None, None, 0.25, -0.5, 2.0, 0.0], ["periodic", "periodic", "dirichlet", "dirichlet", "dirichlet", "dirichlet"])
-BCS = {"dir": ALLDIR, "mix": MIXED, "xper": XPER}
 STAGES3 = SSP_STAGES[3]
 
-# scheme: limiter of source_ref, the speed ("field": a random tensor, "self": the field itself), the BC sets it is run with
+# scheme: limiter of march_ref, the speed ("field": a random tensor, "self": the field itself), the BC sets it is run with
 SCHEMES = {
     "upwind_pos": ("upwind", 0.9, ("dir", "mix")),
     "upwind_neg": ("upwind", -0.8, ("dir", "mix")),
@@ -58,50 +51,11 @@ SCHEMES = {
     "compat": ("compat", 0.7, ("dir", "mix")),     # no SRC instantiation: generic kernel
     "central_field": ("none", "field", ("dir",)),  # a foreign speed at the neighbours: generic kernel
 }
-VECTOR = [([7, 13, 132], "double"), ([9, 14, 132], "double"), ([7, 13, 260], "single"), ([9, 14, 260], "single")]
-GENERIC = [([6, 7, 9], "double"), ([17, 12], "double"), ([33], "single")]
-
-
-def _kind(limiter):
-    return div_kind("upwind" if limiter == "compat" else limiter, limiter == "compat")
-
-
-def _config(limiter):
-    return {"div": {"limiter": "upwind" if limiter == "compat" else limiter, "compat": limiter == "compat"}}
-
-
-def _box(nd):
-    return Box[0:1] if nd == 1 else (Box[0:1, 0:1] if nd == 2 else Box[0:1, 0:1, 0:1])
-
-
-_SETUPS = {}
 
 
 def _setup(n, dtype, bcname):
-    """the GPU mesh and BC config, the oracle's mesh and BCs, and CPU tensors: two BC-filled fields, a speed, a source"""
-    key = (tuple(n), dtype, bcname)
-    if key not in _SETUPS:
-        nd = len(n)
-        vals, types = BCS[bcname]
-        vals, types = vals[:2 * nd], types[:2 * nd]
-        mesh = Mesh(_box(nd), None, list(n), "cuda", dtype)
-        bc = {"domain": mixed_bcs(vals, types), "obstacle": None}
-        om = O.OMesh([0.0] * nd, [1.0] * nd, list(n), dtype)
-        obcs = O.make_bcs(om, O.mixed_cfg(vals, types, O.FACES[:2 * nd]))
-        g = torch.Generator().manual_seed(5)
-        tdt = mesh.dtype.float
-        fields = []
-        for _ in range(2):
-            t = torch.rand((1, *n), generator=g, dtype=torch.float64).to(tdt)
-            O.bc_fill(t, obcs)
-            fields.append(t)
-        speed = torch.randn((1, *n), generator=g, dtype=torch.float64).to(tdt)
-        src = (3.0 * torch.randn((1, *n), generator=g, dtype=torch.float64)).to(tdt)
-        dx = min(float(d) for d in mesh.dx_list)
-        nu = 1e-3
-        dt = 0.2 * min(dx * dx / (2 * nd * nu), dx / 1.3)
-        _SETUPS[key] = (mesh, bc, om, obcs, fields[0], fields[1], speed, src, nu, dt)
-    return _SETUPS[key]
+    """march_gpu.setup with ONE speed field: mesh, BC config, oracle mesh and BCs, two BC-filled fields, speed, source, nu, dt"""
+    return G.setup(n, dtype, bcname, 1)
 
 
 def _gpu_launch(mesh, bc, phi_d, phi0_d, stage, kind, u_d, nu, dt, source):
@@ -132,7 +86,7 @@ SCALAR_SOURCE = 1.75
 def run_scheme(n, dtype, scheme, option_sets, bcnames=None):
     limiter, u, scheme_bcs = SCHEMES[scheme]
     bcnames = bcnames or scheme_bcs
-    kind = _kind(limiter)
+    kind = G.kind(limiter)
     bad = []
     for bcname in bcnames:
         mesh, bc, om, obcs, phi_c, phi0_c, speed_c, src_c, nu, dt = _setup(n, dtype, bcname)
@@ -161,12 +115,11 @@ def run_scheme(n, dtype, scheme, option_sets, bcnames=None):
     return bad
 
 
-VECTOR_OPTIONS = [{"sf": sf, "chunks": ch} for sf in (2, 4) for ch in (1, 2, 3)]
 VECTOR_SCHEMES = [s for s in SCHEMES if s not in ("compat", "central_field")]
 
 
 @pytest.mark.parametrize("scheme", VECTOR_SCHEMES)
-@pytest.mark.parametrize("n,dtype", VECTOR, ids=lambda v: "x".join(map(str, v)) if isinstance(v, list) else v)
+@pytest.mark.parametrize("n,dtype", VECTOR, ids=G.mesh_id)
 def test_step_and_stage_on_the_vector_kernels(n, dtype, scheme):
     assert run_scheme(n, dtype, scheme, VECTOR_OPTIONS) == []
 
@@ -178,7 +131,7 @@ def test_step_and_stage_one_row_per_wave(n, dtype, scheme):
 
 
 @pytest.mark.parametrize("scheme", list(SCHEMES))
-@pytest.mark.parametrize("n,dtype", GENERIC, ids=lambda v: "x".join(map(str, v)) if isinstance(v, list) else v)
+@pytest.mark.parametrize("n,dtype", GENERIC, ids=G.mesh_id)
 def test_step_and_stage_on_the_generic_kernel(n, dtype, scheme):
     assert run_scheme(n, dtype, scheme, [{}]) == []
 
@@ -196,16 +149,6 @@ def test_step_and_stage_with_a_periodic_axis(scheme):
 
 
 # ---- routing --------------------------------------------------------------------------------------------------------
-def _child(code):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pre = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, PYAPES_HIP_DEBUG="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(root, "oracle"), os.environ.get("PYTHONPATH", "")]))
-    r = subprocess.run([sys.executable, "-c", pre + code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
 # name, mesh, dtype, BCs, scheme, options -> the kernel a step and a stage with a source must run on
 ROUTES = [
     ("sf_up_pos_f64", [9, 14, 132], "double", "mix", "upwind_pos", {"sf": 2}, "k_sf"),
@@ -237,12 +180,12 @@ def route_case(name, stage):
     _, n, dtype, bcname, scheme, options, _ = next(r for r in ROUTES if r[0] == name)
     limiter, u, _ = SCHEMES[scheme]
     _, bc, _, _, phi_c, phi0_c, speed_c, src_c, nu, dt = _setup(n, dtype, bcname)
-    mesh = Mesh(_box(len(n)), None, list(n), "cuda", dtype)
+    mesh = Mesh(G.box(len(n)), None, list(n), "cuda", dtype)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
     phi_d = phi_c.cuda()
     _, u_dev = _speeds(u, phi_c, speed_c, phi_d)
-    return _gpu_launch(mesh, bc, phi_d, phi0_c.cuda(), stage, _kind(limiter), u_dev, nu, dt, src_c.cuda()[0])
+    return _gpu_launch(mesh, bc, phi_d, phi0_c.cuda(), stage, G.kind(limiter), u_dev, nu, dt, src_c.cuda()[0])
 
 
 def test_every_case_runs_on_the_kernel_it_is_meant_for():
@@ -254,19 +197,12 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
             "        torch.cuda.synchronize(); sys.stderr.write('CASE %s %s\\n' % (r[0], 'stage' if stage else 'step')); sys.stderr.flush()\n"
             "        T.route_case(r[0], stage)\n"
             "        torch.cuda.synchronize(); sys.stderr.flush()\n")
-    log = _child(code)
-    seen, cur = {}, None
-    for ln in log.splitlines():
-        if ln.startswith("CASE "):
-            cur = tuple(ln[5:].split())
-            seen[cur] = []
-        elif cur is not None and ("k_sf" in ln or "k_euler" in ln or "k_cg3d" in ln):
-            seen[cur].append(ln)
+    seen = G.case_log(G.child(code), lambda ln: "k_sf" in ln or "k_euler" in ln or "k_cg3d" in ln)
     checked = 0
     for name, n, dtype, bcname, scheme, options, kernel in ROUTES:
         for what in ("step", "stage"):
-            lines = seen.get((name, what))
-            assert lines is not None, (name, what, log[-2000:])
+            lines = seen.get("%s %s" % (name, what))
+            assert lines is not None, (name, what, sorted(seen))
             if not lines:
                 continue   # the instantiation's log budget was used up by an earlier case
             assert len(lines) == 1, (name, what, lines)
@@ -279,25 +215,24 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
             if name == "sf_one_row_f64":
                 assert " RJ 1" in ln, ln
             checked += 1
-    assert checked >= len(ROUTES), (checked, log[-3000:])
+    assert checked >= len(ROUTES), (checked, seen)
     for name in ("sf_up_pos_f64", "sfq_pos_f32", "gen_compat_f64", "gen_central_field_f32", "gen_odd_rows_f64", "gen_2d_f64"):
-        assert seen[(name, "step")] and seen[(name, "stage")], name
+        assert seen[name + " step"] and seen[name + " stage"], name
 
 
 def march_case(n, dtype, bcname, scheme, options, order, nsteps, source):
     limiter, u, _ = SCHEMES[scheme]
     _, bc, _, _, phi_c, _, speed_c, src_c, nu, dt = _setup(n, dtype, bcname)
-    mesh = Mesh(_box(len(n)), None, list(n), "cuda", dtype)
+    mesh = Mesh(G.box(len(n)), None, list(n), "cuda", dtype)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
-    f = Field("phi", 1, mesh, bc)
-    f.set_var_tensor(phi_c.cuda())
+    f = G.fresh_field(mesh, bc, phi_c)
     src = {"field": src_c.cuda(), "scalar": SCALAR_SOURCE, None: None}[source]
     uu = f if u == "self" else (speed_c.cuda() if u == "field" else u)
     if order == 0:
-        euler_march(f, uu, nu, dt, nsteps, _config(limiter), source=src)
+        euler_march(f, uu, nu, dt, nsteps, G.config(limiter), source=src)
     else:
-        rk_march(f, uu, nu, dt, nsteps, _config(limiter), order=order, source=src)
+        rk_march(f, uu, nu, dt, nsteps, G.config(limiter), order=order, source=src)
     return f().clone()
 
 
@@ -309,16 +244,12 @@ def test_a_march_with_a_source_stays_in_the_bc_on_load_form():
             "T.march_case([9, 14, 132], 'double', 'mix', 'self_upwind', {'sf': 2}, 0, 3, 'scalar'); torch.cuda.synchronize()\n"
             "sys.stderr.write('CASE c\\n'); sys.stderr.flush()\n"
             "T.march_case([9, 14, 132], 'double', 'mix', 'upwind_neg', {'sf': 2, 'bcl': 0}, 3, 1, 'field'); torch.cuda.synchronize()\n")
-    log = _child(code)
-    a, rest = log.split("CASE a\n")[1].split("CASE b\n")
-    b, c = rest.split("CASE c\n")
-    la = [ln for ln in a.splitlines() if "k_sf phase 3" in ln]
-    lb = [ln for ln in b.splitlines() if "k_sf phase 3" in ln]
-    lc = [ln for ln in c.splitlines() if "k_sf phase 3" in ln]
-    assert len(la) == 6 and all("(BC on load)" in ln and "(source)" in ln and " RJ 4" in ln for ln in la), a
-    assert sum("(RK stage)" in ln for ln in la) == 4, a
-    assert len(lb) == 3 and all("(BC on load)" in ln and "(source)" in ln and "(self)" in ln for ln in lb), b
-    assert len(lc) == 3 and all("(source)" in ln and "(BC on load)" not in ln for ln in lc), c
+    seen = G.case_log(G.child(code), lambda ln: "k_sf phase 3" in ln)
+    la, lb, lc = seen["a"], seen["b"], seen["c"]
+    assert len(la) == 6 and all("(BC on load)" in ln and "(source)" in ln and " RJ 4" in ln for ln in la), la
+    assert sum("(RK stage)" in ln for ln in la) == 4, la
+    assert len(lb) == 3 and all("(BC on load)" in ln and "(source)" in ln and "(self)" in ln for ln in lb), lb
+    assert len(lc) == 3 and all("(source)" in ln and "(BC on load)" not in ln for ln in lc), lc
 
 
 # ---- switches, march = pieces, no source = today --------------------------------------------------------------------
@@ -344,16 +275,18 @@ def _march_by_stages(mesh, bc, phi, kind, u, self_adv, nu, dt, order, nsteps, so
     ctx = context_for(mesh)
     f = Field("phi", 1, mesh, bc)
     ctx.bind_bcs(f(), f.bcs, 0)
-    for _ in range(nsteps):
-        phi0 = phi.clone()
-        cur = torch.empty_like(phi0)
-        ctx.euler_step(phi0[0], cur[0], kind, phi0[0] if self_adv else u, nu, dt, source=source)
-        for c0, c1 in SSP_STAGES[order]:
-            out = torch.empty_like(cur)
-            ctx.rk_stage(cur[0], phi0[0], out[0], c0, c1, kind, cur[0] if self_adv else u, nu, dt, source=source)
-            cur = out
-        phi = cur
-    return phi
+
+    def step(phi0):
+        out = torch.empty_like(phi0)
+        ctx.euler_step(phi0[0], out[0], kind, phi0[0] if self_adv else u, nu, dt, source=source)
+        return out
+
+    def stage(cur, phi0, c0, c1):
+        out = torch.empty_like(cur)
+        ctx.rk_stage(cur[0], phi0[0], out[0], c0, c1, kind, cur[0] if self_adv else u, nu, dt, source=source)
+        return out
+
+    return G.march_by_stages(step, stage, phi, order, nsteps)
 
 
 @pytest.mark.parametrize("scheme", ["upwind_pos", "quick_field", "self_upwind", "self_central"])
@@ -367,19 +300,17 @@ def test_march_is_its_pieces(order, scheme):
     u_ref = speed_c if u == "field" else u
     for source, s_ref in ((src_c.cuda()[0], src_c), (SCALAR_SOURCE, SCALAR_SOURCE)):
         for nsteps in (1, 3):
-            f = Field("phi", 1, mesh, bc)
-            f.set_var_tensor(phi_c.cuda())
+            f = G.fresh_field(mesh, bc, phi_c)
             uu = f if self_adv else (speed_c.cuda() if u == "field" else u)
-            g = rk_march(f, uu, nu, dt, nsteps, _config(limiter), order=order, source=source)
+            g = rk_march(f, uu, nu, dt, nsteps, G.config(limiter), order=order, source=source)
             assert g is f
-            pieces = _march_by_stages(mesh, bc, phi_c.cuda(), _kind(limiter), u_dev, self_adv, nu, dt, order, nsteps, source)
+            pieces = _march_by_stages(mesh, bc, phi_c.cuda(), G.kind(limiter), u_dev, self_adv, nu, dt, order, nsteps, source)
             assert bit_equal(f(), pieces), (nsteps, float((f() - pieces).abs().max()))
             want = R.march(phi_c, u_ref, nu, dt, nsteps, om, obcs, limiter, order, s_ref, self_adv=self_adv)
             assert bit_equal(f(), want), (nsteps, float((f().cpu() - want).abs().max()))
-        f = Field("phi", 1, mesh, bc)
-        f.set_var_tensor(phi_c.cuda())
+        f = G.fresh_field(mesh, bc, phi_c)
         uu = f if self_adv else (speed_c.cuda() if u == "field" else u)
-        rk_step(f, uu, nu, dt, _config(limiter), order=order, source=_source_field(mesh, bc, src_c))   # a scalar Field as source
+        rk_step(f, uu, nu, dt, G.config(limiter), order=order, source=_source_field(mesh, bc, src_c))   # a scalar Field as source
         assert bit_equal(f(), R.march(phi_c, u_ref, nu, dt, 1, om, obcs, limiter, order, src_c, self_adv=self_adv))
 
 
@@ -397,16 +328,10 @@ def test_source_tensor_forms():
     wide = torch.zeros((1, 9, 14, 264), dtype=torch.float64, device="cuda")
     wide[..., ::2] = src_c.cuda()
     for s in (src_c.cuda(), src_c.cuda()[0], wide[..., ::2], wide[0, ..., ::2]):
-        f = Field("phi", 1, mesh, bc)
-        f.set_var_tensor(phi_c.cuda())
+        f = G.fresh_field(mesh, bc, phi_c)
         assert bit_equal(euler_step(f, 0.9, nu, dt, source=s)(), want)
-    f = Field("phi", 1, mesh, bc)
-    f.set_var_tensor(phi_c.cuda())
+    f = G.fresh_field(mesh, bc, phi_c)
     assert bit_equal(euler_step(f, 0.9, nu, dt, source=2)(), R.euler_step(phi_c, 0.9, nu, dt, om, obcs, "upwind", 2.0))
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 @pytest.mark.parametrize("n,dtype", [([9, 14, 260], "single"), ([6, 7, 9], "double")], ids=["vector", "generic"])
@@ -414,12 +339,10 @@ def test_no_source_is_today(n, dtype):
     """source=None and the argument left out: the same bits; the five _src entry points with NULL and with has = 0: their
     siblings"""
     mesh, bc, _, _, phi_c, phi0_c, speed_c, _, nu, dt = _setup(n, dtype, "mix")
-    cfg = _config("upwind")
+    cfg = G.config("upwind")
 
     def fresh():
-        f = Field("phi", 1, mesh, bc)
-        f.set_var_tensor(phi_c.cuda())
-        return f
+        return G.fresh_field(mesh, bc, phi_c)
 
     assert bit_equal(euler_step(fresh(), 0.9, nu, dt, cfg)(), euler_step(fresh(), 0.9, nu, dt, cfg, source=None)())
     assert bit_equal(euler_march(fresh(), 0.9, nu, dt, 5, cfg)(), euler_march(fresh(), 0.9, nu, dt, 5, cfg, source=None)())
@@ -431,32 +354,32 @@ def test_no_source_is_today(n, dtype):
     ctx = context_for(mesh)
     lib, h = ctx.lib, ctx.h
     ctx.bind_bcs(fresh()(), fresh().bcs, 0)
-    kind = _kind("upwind")
+    kind = G.kind("upwind")
     phi_d, phi0_d, uf = phi_c.cuda()[0].contiguous(), phi0_c.cuda()[0].contiguous(), speed_c.cuda()[0].contiguous()
     off = L.PaSource()
     off.has, off.value, off.field = 0, 123.0, uf.data_ptr()   # has = 0: value and field are not read
     for src in (None, C.byref(off)):
         a, b = torch.empty_like(phi_d), torch.empty_like(phi_d)
-        assert lib.pa_euler_step(h, _ptr(phi_d), _ptr(a), kind, 0.9, None, nu, dt) == 0
-        assert lib.pa_euler_step_src(h, _ptr(phi_d), _ptr(b), kind, 0.9, None, nu, dt, src) == 0
+        assert lib.pa_euler_step(h, G.ptr(phi_d), G.ptr(a), kind, 0.9, None, nu, dt) == 0
+        assert lib.pa_euler_step_src(h, G.ptr(phi_d), G.ptr(b), kind, 0.9, None, nu, dt, src) == 0
         assert bit_equal(a, b)
-        assert lib.pa_rk_stage(h, _ptr(phi_d), _ptr(phi0_d), _ptr(a), 0.75, 0.25, kind, 0.0, _ptr(uf), nu, dt) == 0
-        assert lib.pa_rk_stage_src(h, _ptr(phi_d), _ptr(phi0_d), _ptr(b), 0.75, 0.25, kind, 0.0, _ptr(uf), nu, dt, src) == 0
+        assert lib.pa_rk_stage(h, G.ptr(phi_d), G.ptr(phi0_d), G.ptr(a), 0.75, 0.25, kind, 0.0, G.ptr(uf), nu, dt) == 0
+        assert lib.pa_rk_stage_src(h, G.ptr(phi_d), G.ptr(phi0_d), G.ptr(b), 0.75, 0.25, kind, 0.0, G.ptr(uf), nu, dt, src) == 0
         assert bit_equal(a, b)
         pa, pb = phi_d.clone(), phi_d.clone()
-        assert lib.pa_euler_march(h, _ptr(pa), _ptr(a), kind, -0.8, None, nu, dt, 5) == 0
-        assert lib.pa_euler_march_src(h, _ptr(pb), _ptr(b), kind, -0.8, None, nu, dt, 5, src) == 0
+        assert lib.pa_euler_march(h, G.ptr(pa), G.ptr(a), kind, -0.8, None, nu, dt, 5) == 0
+        assert lib.pa_euler_march_src(h, G.ptr(pb), G.ptr(b), kind, -0.8, None, nu, dt, 5, src) == 0
         assert bit_equal(a, b) and bit_equal(pa, pb)
         fa, fb = C.c_int(-1), C.c_int(-1)
         for self_adv in (False, True):
             bufa = [phi_d.clone(), torch.empty_like(phi_d), torch.empty_like(phi_d)]
             bufb = [phi_d.clone(), torch.empty_like(phi_d), torch.empty_like(phi_d)]
             if self_adv:
-                assert lib.pa_rk_march_self(h, *map(_ptr, bufa), 3, kind, nu, dt, 4, C.byref(fa)) == 0
-                assert lib.pa_rk_march_self_src(h, *map(_ptr, bufb), 3, kind, nu, dt, 4, C.byref(fb), src) == 0
+                assert lib.pa_rk_march_self(h, *map(G.ptr, bufa), 3, kind, nu, dt, 4, C.byref(fa)) == 0
+                assert lib.pa_rk_march_self_src(h, *map(G.ptr, bufb), 3, kind, nu, dt, 4, C.byref(fb), src) == 0
             else:
-                assert lib.pa_rk_march(h, *map(_ptr, bufa), 3, kind, 0.9, None, nu, dt, 4, C.byref(fa)) == 0
-                assert lib.pa_rk_march_src(h, *map(_ptr, bufb), 3, kind, 0.9, None, nu, dt, 4, C.byref(fb), src) == 0
+                assert lib.pa_rk_march(h, *map(G.ptr, bufa), 3, kind, 0.9, None, nu, dt, 4, C.byref(fa)) == 0
+                assert lib.pa_rk_march_src(h, *map(G.ptr, bufb), 3, kind, 0.9, None, nu, dt, 4, C.byref(fb), src) == 0
             assert fa.value == fb.value and bit_equal(bufa[fa.value], bufb[fb.value])
 
 
@@ -477,17 +400,14 @@ def test_fixed_point_on_the_gpu(n, dtype, scheme):
     for sf in (2, 4):
         ctx = context_for(mesh)
         ctx.set_option("sf", sf)
-        f = Field("phi", 1, mesh, bc)
-        f.set_var_tensor(star.cuda())
-        euler_march(f, u, nu, dt, 50, _config(limiter), source=S.cuda())
+        f = G.fresh_field(mesh, bc, star)
+        euler_march(f, u, nu, dt, 50, G.config(limiter), source=S.cuda())
         assert torch.equal(f().cpu(), star), float((f().cpu() - star).abs().max())
-        f = Field("phi", 1, mesh, bc)
-        f.set_var_tensor(star.cuda())
-        rk_march(f, u, nu, dt, 50, _config(limiter), order=2, source=S.cuda())
+        f = G.fresh_field(mesh, bc, star)
+        rk_march(f, u, nu, dt, 50, G.config(limiter), order=2, source=S.cuda())
         assert torch.equal(f().cpu(), star)
-        f = Field("phi", 1, mesh, bc)
-        f.set_var_tensor(star.cuda())
-        rk_march(f, u, nu, dt, 50, _config(limiter), order=3, source=S.cuda())
+        f = G.fresh_field(mesh, bc, star)
+        rk_march(f, u, nu, dt, 50, G.config(limiter), order=3, source=S.cuda())
         dev = float((f().cpu() - star).abs().max())
         ulp = float(torch.finfo(tdt).eps) * float(star.abs().max())
         print(f"{scheme} {dtype} sf {sf}: order 3 max|phi - phi*| = {dev:.3e} ({dev / ulp:.2f} ulp)")
@@ -499,11 +419,11 @@ def test_fixed_point_on_the_gpu(n, dtype, scheme):
 def test_errors_leave_the_context_usable():
     n, dtype = [9, 14, 132], "double"
     mesh, bc, om, obcs, phi_c, phi0_c, speed_c, src_c, nu, dt = _setup(n, dtype, "mix")
-    mesh = Mesh(_box(3), None, list(n), "cuda", dtype)   # a context of its own
+    mesh = Mesh(G.box(3), None, list(n), "cuda", dtype)   # a context of its own
     ctx = context_for(mesh)
     f = Field("phi", 1, mesh, bc)
     ctx.bind_bcs(f(), f.bcs, 0)
-    kind = _kind("upwind")
+    kind = G.kind("upwind")
     phi, phi0, uf, src = (t.cuda()[0].contiguous() for t in (phi_c, phi0_c, speed_c, src_c))
     out, w2 = torch.empty_like(phi), torch.empty_like(phi)
 

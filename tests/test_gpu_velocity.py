@@ -2,7 +2,7 @@
 ``u`` of euler_step / euler_march / rk_step / rk_march, pa_*_vel at the C ABI, the VEL instantiations of k_sf (upwind, three
 scalar speeds or three speed fields) and of the generic k_euler (everything else).
 
-The yardstick is tests/velocity_ref.py, the step restated on the CPU operation for operation, and the device must give its
+The yardstick is tests/march_ref.py, the step in a velocity restated on the CPU operation for operation, and the device must give its
 BITS: on both kernels, for the three Div limiters, scalar and field velocities of mixed signs with three DISTINCT components (a
 swapped axis cannot pass), Dirichlet and mixed faces, no source / a source field / a scalar source, the Euler step and both
 fused stages of order 3.  Meshes as tests/test_gpu_source.py: whole 16-byte rows and two k tiles (132 fp64 / 260 fp32 nodes per
@@ -12,16 +12,14 @@ rows of 2 * VEC to 264 nodes, a periodic axis 1 or 2, all-Neumann faces, long ch
 tests/test_gpu_chunks_terms.py.)  The exact shift needs no reference at all: with dx = dt = 1 and u = +-e_a one upwind step moves small integers by one node.
 """
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
-import pyapes_oracle as O
-import velocity_ref as R
+import march_gpu as G
+import march_ref as R
 from helpers import bit_equal
+from march_gpu import GENERIC, LIMITER_BCS, VECTOR, VECTOR_OPTIONS
 from pyapes_amd.geometry import Box, Cylinder
 from pyapes_amd.hip import lib as L
 from pyapes_amd.hip.context import context_for
@@ -34,57 +32,16 @@ from pyapes_amd.variables.bcs import mixed_bcs
 
 pytestmark = pytest.mark.gpu
 
-ALLDIR = ([0.0, 1.0, 0.25, -0.5, 2.0, 0.0], ["dirichlet"] * 6)
-MIXED = ([0.5, 0.1, None, 1.0, -0.3, None], ["dirichlet", "neumann", "symmetry", "dirichlet", "neumann", "symmetry"])
-XPER = ([None, None, 0.25, -0.5, 2.0, 0.0], ["periodic", "periodic", "dirichlet", "dirichlet", "dirichlet", "dirichlet"])
-BCS = {"dir": ALLDIR, "mix": MIXED, "xper": XPER}
 STAGES3 = SSP_STAGES[3]
 SCALARS = (0.9, -0.8, 0.4)                        # mixed signs, three distinct speeds
 SCALAR_SOURCE = 1.75
-LIMITER_BCS = {"upwind": ("dir", "mix"), "quick": ("dir", "mix"), "none": ("dir",)}   # central Div refuses neumann / symmetry
 
-VECTOR = [([7, 13, 132], "double"), ([9, 14, 132], "double"), ([7, 13, 260], "single"), ([9, 14, 260], "single")]
-GENERIC = [([6, 7, 9], "double"), ([17, 12], "double"), ([33], "single")]
-_ids = lambda v: "x".join(map(str, v)) if isinstance(v, list) else v
-
-
-def _config(limiter):
-    return {"div": {"limiter": limiter}}
-
-
-def _box(nd):
-    return Box[0:1] if nd == 1 else (Box[0:1, 0:1] if nd == 2 else Box[0:1, 0:1, 0:1])
-
-
-_SETUPS = {}
+_ids = G.mesh_id
 
 
 def _setup(n, dtype, bcname):
-    """the GPU mesh and BC config, the oracle's mesh and BCs, and CPU tensors: two BC-filled fields, a velocity (nd, *n) with
-    distinct random components, a source"""
-    key = (tuple(n), dtype, bcname)
-    if key not in _SETUPS:
-        nd = len(n)
-        vals, types = BCS[bcname]
-        vals, types = vals[:2 * nd], types[:2 * nd]
-        mesh = Mesh(_box(nd), None, list(n), "cuda", dtype)
-        bc = {"domain": mixed_bcs(vals, types), "obstacle": None}
-        om = O.OMesh([0.0] * nd, [1.0] * nd, list(n), dtype)
-        obcs = O.make_bcs(om, O.mixed_cfg(vals, types, O.FACES[:2 * nd]))
-        g = torch.Generator().manual_seed(5)
-        tdt = mesh.dtype.float
-        fields = []
-        for _ in range(2):
-            t = torch.rand((1, *n), generator=g, dtype=torch.float64).to(tdt)
-            O.bc_fill(t, obcs)
-            fields.append(t)
-        vel = torch.randn((nd, *n), generator=g, dtype=torch.float64).to(tdt)
-        src = (3.0 * torch.randn((1, *n), generator=g, dtype=torch.float64)).to(tdt)
-        dx = min(float(d) for d in mesh.dx_list)
-        nu = 1e-3
-        dt = 0.2 * min(dx * dx / (2 * nd * nu), dx / 1.3)
-        _SETUPS[key] = (mesh, bc, om, obcs, fields[0], fields[1], vel, src, nu, dt)
-    return _SETUPS[key]
+    """march_gpu.setup with a velocity (nd, *n) of distinct random components in place of the one speed field"""
+    return G.setup(n, dtype, bcname, len(n))
 
 
 def _vels(which, vel_c):
@@ -135,9 +92,6 @@ def run_case(n, dtype, limiter, option_sets, bcnames=None):
     return bad
 
 
-VECTOR_OPTIONS = [{"sf": sf, "chunks": ch} for sf in (2, 4) for ch in (1, 2, 3)]
-
-
 @pytest.mark.parametrize("n,dtype", VECTOR, ids=_ids)
 def test_upwind_step_and_stage_on_the_vector_kernel(n, dtype):
     assert run_case(n, dtype, "upwind", VECTOR_OPTIONS) == []
@@ -163,28 +117,20 @@ def test_quick_and_central_on_the_vector_meshes(n, dtype, limiter):
 
 
 # ---- equal components are today's call ------------------------------------------------------------------------------
-def _fresh(mesh, bc, phi_c, time=False):
-    f = Field("phi", 1, mesh, bc)
-    f.set_var_tensor(phi_c.cuda())
-    if time:
-        f.set_time(0.0, 1.5)
-    return f
-
-
 @pytest.mark.parametrize("limiter", ["upwind", "quick", "none"])
 @pytest.mark.parametrize("n,dtype", [([9, 14, 260], "single"), ([6, 7, 9], "double")], ids=["vector", "generic"])
 def test_equal_components_are_todays_call(n, dtype, limiter):
     bcname = LIMITER_BCS[limiter][-1]
     mesh, bc, _, _, phi_c, _, vel_c, _, nu, dt = _setup(n, dtype, bcname)
-    cfg = _config(limiter)
+    cfg = G.config(limiter)
     U = vel_c.cuda()[0:1].contiguous()
     for c in (0.9, -0.8):
-        assert bit_equal(euler_step(_fresh(mesh, bc, phi_c), (c, c, c), nu, dt, cfg)(), euler_step(_fresh(mesh, bc, phi_c), c, nu, dt, cfg)())
-        assert bit_equal(rk_march(_fresh(mesh, bc, phi_c), (c, c, c), nu, dt, 3, cfg, order=3)(),
-                         rk_march(_fresh(mesh, bc, phi_c), c, nu, dt, 3, cfg, order=3)())
-    assert bit_equal(euler_step(_fresh(mesh, bc, phi_c), (U[0], U[0], U[0]), nu, dt, cfg)(), euler_step(_fresh(mesh, bc, phi_c), U, nu, dt, cfg)())
-    assert bit_equal(rk_march(_fresh(mesh, bc, phi_c), (U[0], U[0], U[0]), nu, dt, 3, cfg, order=3)(),
-                     rk_march(_fresh(mesh, bc, phi_c), U, nu, dt, 3, cfg, order=3)())
+        assert bit_equal(euler_step(G.fresh_field(mesh, bc, phi_c), (c, c, c), nu, dt, cfg)(), euler_step(G.fresh_field(mesh, bc, phi_c), c, nu, dt, cfg)())
+        assert bit_equal(rk_march(G.fresh_field(mesh, bc, phi_c), (c, c, c), nu, dt, 3, cfg, order=3)(),
+                         rk_march(G.fresh_field(mesh, bc, phi_c), c, nu, dt, 3, cfg, order=3)())
+    assert bit_equal(euler_step(G.fresh_field(mesh, bc, phi_c), (U[0], U[0], U[0]), nu, dt, cfg)(), euler_step(G.fresh_field(mesh, bc, phi_c), U, nu, dt, cfg)())
+    assert bit_equal(rk_march(G.fresh_field(mesh, bc, phi_c), (U[0], U[0], U[0]), nu, dt, 3, cfg, order=3)(),
+                     rk_march(G.fresh_field(mesh, bc, phi_c), U, nu, dt, 3, cfg, order=3)())
 
 
 # ---- exact shift ----------------------------------------------------------------------------------------------------
@@ -209,21 +155,11 @@ def test_exact_shift(fastpath, dtype):
             for vel in (tuple(u), tuple(torch.full_like(phi[0], v) for v in u)):
                 f = Field("phi", 1, mesh, bc)
                 f.set_var_tensor(phi.clone())
-                got = euler_step(f, vel, 0.0, 1.0, _config("upwind"))()
+                got = euler_step(f, vel, 0.0, 1.0, G.config("upwind"))()
                 assert torch.equal(got[0][inner], want[inner]), (axis, sign)
 
 
 # ---- routing --------------------------------------------------------------------------------------------------------
-def _child(code):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    pre = "import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n" % (root, os.path.join(root, "tests"))
-    env = dict(os.environ, PYAPES_HIP_DEBUG="1",
-               PYTHONPATH=os.pathsep.join([os.path.join(root, "oracle"), os.environ.get("PYTHONPATH", "")]))
-    r = subprocess.run([sys.executable, "-c", pre + code], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return r.stderr
-
-
 # name, mesh, dtype, BCs, limiter, velocity, source, options -> the kernel a step and a stage must run on.  The launch log is
 # limited per kernel instantiation: the k_sf routes use distinct instantiations (dtype x VEL x source)
 ROUTES = [
@@ -251,7 +187,7 @@ def route_case(name, stage):
     """one launch of the named route (a fresh mesh, so that its options are its own)"""
     _, n, dtype, bcname, limiter, which, source, options, _ = next(r for r in ROUTES if r[0] == name)
     _, bc, _, _, phi_c, phi0_c, vel_c, src_c, nu, dt = _setup(n, dtype, bcname)
-    mesh = Mesh(_box(len(n)), None, list(n), "cuda", dtype)
+    mesh = Mesh(G.box(len(n)), None, list(n), "cuda", dtype)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
     _, v_dev = _vels(which, vel_c)
@@ -267,18 +203,11 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
             "        torch.cuda.synchronize(); sys.stderr.write('CASE %s %s\\n' % (r[0], 'stage' if stage else 'step')); sys.stderr.flush()\n"
             "        T.route_case(r[0], stage)\n"
             "        torch.cuda.synchronize(); sys.stderr.flush()\n")
-    log = _child(code)
-    seen, cur = {}, None
-    for ln in log.splitlines():
-        if ln.startswith("CASE "):
-            cur = tuple(ln[5:].split())
-            seen[cur] = []
-        elif cur is not None and ("k_sf" in ln or "k_euler" in ln or "k_cg3d" in ln):
-            seen[cur].append(ln)
+    seen = G.case_log(G.child(code), lambda ln: "k_sf" in ln or "k_euler" in ln or "k_cg3d" in ln)
     for name, n, dtype, bcname, limiter, which, source, options, kernel in ROUTES:
         for what in ("step", "stage"):
-            lines = seen.get((name, what))
-            assert lines is not None, (name, what, log[-2000:])
+            lines = seen.get("%s %s" % (name, what))
+            assert lines is not None, (name, what, sorted(seen))
             assert len(lines) == 1, (name, what, lines)
             ln = lines[0]
             assert kernel + " " in ln and " (velocity)" in ln and "k_cg3d" not in ln and "k_sfq" not in ln, (name, what, ln)
@@ -292,16 +221,16 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
 # ---- switches, march = pieces ---------------------------------------------------------------------------------------
 def march_case(n, dtype, bcname, limiter, which, options, order, nsteps, source):
     _, bc, _, _, phi_c, _, vel_c, src_c, nu, dt = _setup(n, dtype, bcname)
-    mesh = Mesh(_box(len(n)), None, list(n), "cuda", dtype)
+    mesh = Mesh(G.box(len(n)), None, list(n), "cuda", dtype)
     for k, v in options.items():
         context_for(mesh).set_option(k, v)
-    f = _fresh(mesh, bc, phi_c)
+    f = G.fresh_field(mesh, bc, phi_c)
     _, v_dev = _vels(which, vel_c)
     src = {"field": src_c.cuda(), "scalar": SCALAR_SOURCE, None: None}[source]
     if order == 0:
-        euler_march(f, tuple(v_dev), nu, dt, nsteps, _config(limiter), source=src)
+        euler_march(f, tuple(v_dev), nu, dt, nsteps, G.config(limiter), source=src)
     else:
-        rk_march(f, tuple(v_dev), nu, dt, nsteps, _config(limiter), order=order, source=src)
+        rk_march(f, tuple(v_dev), nu, dt, nsteps, G.config(limiter), order=order, source=src)
     return f().clone()
 
 
@@ -324,16 +253,18 @@ def _march_by_stages(mesh, bc, phi, kind, vel, nu, dt, order, nsteps, source):
     ctx = context_for(mesh)
     f = Field("phi", 1, mesh, bc)
     ctx.bind_bcs(f(), f.bcs, 0)
-    for _ in range(nsteps):
-        phi0 = phi.clone()
-        cur = torch.empty_like(phi0)
-        ctx.euler_step_vel(phi0[0], cur[0], kind, vel, nu, dt, source=source)
-        for c0, c1 in SSP_STAGES[order]:
-            out = torch.empty_like(cur)
-            ctx.rk_stage_vel(cur[0], phi0[0], out[0], c0, c1, kind, vel, nu, dt, source=source)
-            cur = out
-        phi = cur
-    return phi
+
+    def step(phi0):
+        out = torch.empty_like(phi0)
+        ctx.euler_step_vel(phi0[0], out[0], kind, vel, nu, dt, source=source)
+        return out
+
+    def stage(cur, phi0, c0, c1):
+        out = torch.empty_like(cur)
+        ctx.rk_stage_vel(cur[0], phi0[0], out[0], c0, c1, kind, vel, nu, dt, source=source)
+        return out
+
+    return G.march_by_stages(step, stage, phi, order, nsteps)
 
 
 @pytest.mark.parametrize("limiter", ["upwind", "quick"])
@@ -341,12 +272,12 @@ def _march_by_stages(mesh, bc, phi, kind, vel, nu, dt, order, nsteps, source):
 def test_march_is_its_pieces(order, limiter):
     n, dtype, bcname, nsteps = [9, 14, 132], "double", "mix", 3
     mesh, bc, om, obcs, phi_c, _, vel_c, src_c, nu, dt = _setup(n, dtype, bcname)
-    kind, cfg = div_kind(limiter, False), _config(limiter)
+    kind, cfg = div_kind(limiter, False), G.config(limiter)
     vd = vel_c.cuda()
     for which in ("scalar", "field"):
         v_ref, v_dev = _vels(which, vel_c)
         for source, s_ref in ((None, None), (src_c.cuda()[0], src_c)):
-            f = _fresh(mesh, bc, phi_c, time=True)
+            f = G.fresh_field(mesh, bc, phi_c, time=True)
             g = rk_march(f, tuple(v_dev), nu, dt, nsteps, cfg, order=order, source=source)
             assert g is f
             assert abs(float(f.t) - (1.5 + nsteps * dt)) <= 1e-12          # phi's time advances by nsteps * dt
@@ -355,21 +286,21 @@ def test_march_is_its_pieces(order, limiter):
             want = R.march(phi_c, v_ref, nu, dt, nsteps, om, obcs, limiter, order, s_ref)
             assert bit_equal(f(), want), (which, float((f().cpu() - want).abs().max()))
             if order == 1:
-                e = euler_march(_fresh(mesh, bc, phi_c), list(v_dev), nu, dt, nsteps, cfg, source=source)
+                e = euler_march(G.fresh_field(mesh, bc, phi_c), list(v_dev), nu, dt, nsteps, cfg, source=source)
                 assert bit_equal(e(), want)
     # the three forms of a velocity give the same bits: the tuple, the (dim, *n) tensor, the vector Field; rk_step too
     want = R.march(phi_c, [vel_c[a] for a in range(3)], nu, dt, nsteps, om, obcs, limiter, order)
     uf = Field("u", 3, mesh, bc)
     uf.set_var_tensor(vd.clone())
     for form in ((vd[0], vd[1], vd[2]), [vd[0], vd[1], vd[2]], vd, uf):
-        assert bit_equal(rk_march(_fresh(mesh, bc, phi_c), form, nu, dt, nsteps, cfg, order=order)(), want)
+        assert bit_equal(rk_march(G.fresh_field(mesh, bc, phi_c), form, nu, dt, nsteps, cfg, order=order)(), want)
     one = R.march(phi_c, [vel_c[a] for a in range(3)], nu, dt, 1, om, obcs, limiter, order)
-    assert bit_equal(rk_step(_fresh(mesh, bc, phi_c), vd, nu, dt, cfg, order=order)(), one)
+    assert bit_equal(rk_step(G.fresh_field(mesh, bc, phi_c), vd, nu, dt, cfg, order=order)(), one)
     # mixed number / tensor entries equal the filled tensors
     mixed = (vd[0], -0.8, vd[2])
     filled = (vd[0], torch.full_like(vd[1], -0.8), vd[2])
-    a = rk_march(_fresh(mesh, bc, phi_c), mixed, nu, dt, nsteps, cfg, order=order)()
-    b = rk_march(_fresh(mesh, bc, phi_c), filled, nu, dt, nsteps, cfg, order=order)()
+    a = rk_march(G.fresh_field(mesh, bc, phi_c), mixed, nu, dt, nsteps, cfg, order=order)()
+    b = rk_march(G.fresh_field(mesh, bc, phi_c), filled, nu, dt, nsteps, cfg, order=order)()
     assert bit_equal(a, b)
     assert bit_equal(a, R.march(phi_c, [vel_c[0], -0.8, vel_c[2]], nu, dt, nsteps, om, obcs, limiter, order))
 
@@ -386,14 +317,10 @@ def test_a_c_level_mix_of_scalar_and_field_components():
 
 
 # ---- errors ---------------------------------------------------------------------------------------------------------
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
 def test_c_abi_errors_leave_the_context_usable():
     n, dtype = [9, 14, 132], "double"
     _, bc, om, obcs, phi_c, phi0_c, vel_c, src_c, nu, dt = _setup(n, dtype, "mix")
-    mesh = Mesh(_box(3), None, list(n), "cuda", dtype)   # a context of its own
+    mesh = Mesh(G.box(3), None, list(n), "cuda", dtype)   # a context of its own
     ctx = context_for(mesh)
     f = Field("phi", 1, mesh, bc)
     ctx.bind_bcs(f(), f.bcs, 0)
@@ -419,9 +346,9 @@ def test_c_abi_errors_leave_the_context_usable():
     off = L.PaVelocity()
     off.has = 0
     for v in (None, C.byref(off)):
-        assert lib.pa_euler_step_vel(h, _ptr(phi), _ptr(out), kind, v, nu, dt, None) == L.PA_E_ARG
-        assert lib.pa_rk_stage_vel(h, _ptr(phi), _ptr(phi0), _ptr(out), 0.5, 0.5, kind, v, nu, dt, None) == L.PA_E_ARG
-        assert lib.pa_rk_march_vel(h, _ptr(phi.clone()), _ptr(out), _ptr(w2), 3, kind, v, nu, dt, 2, C.byref(final), None) == L.PA_E_ARG
+        assert lib.pa_euler_step_vel(h, G.ptr(phi), G.ptr(out), kind, v, nu, dt, None) == L.PA_E_ARG
+        assert lib.pa_rk_stage_vel(h, G.ptr(phi), G.ptr(phi0), G.ptr(out), 0.5, 0.5, kind, v, nu, dt, None) == L.PA_E_ARG
+        assert lib.pa_rk_march_vel(h, G.ptr(phi.clone()), G.ptr(out), G.ptr(w2), 3, kind, v, nu, dt, 2, C.byref(final), None) == L.PA_E_ARG
         good()
     # the literal upwind form
     compat = div_kind("upwind", True)

@@ -1,6 +1,6 @@
-"""No GPU: the momentum march -- a vector field that advects itself -- on the CPU.  tests/momentum_ref.py (the stage restated
-from tests/velocity_ref.py) against what it is built from, the oblique steady viscous shock, and the argument checks of
-``momentum_step`` / ``momentum_march`` (pyapes_amd/solver/march.py), which fire before a device is touched.
+"""No GPU: the momentum march -- a vector field that advects itself -- on the CPU.  The momentum functions of tests/march_ref.py
+(the stage restated from its step in a velocity) against what they are built from, the oblique steady viscous shock, and the
+argument checks of ``momentum_step`` / ``momentum_march`` (pyapes_amd/solver/march.py), which fire before a device is touched.
 
 Oblique steady viscous shock (measured on the CPU, printed by the test): with the unit vector n = (1, 1) / sqrt(2) and
 s = n . (x - x0), U = -A n tanh(A s / (2 nu)) is a steady solution of the advective-form momentum equation (u u' = nu u'').
@@ -20,9 +20,9 @@ import math
 import pytest
 import torch
 
-import momentum_ref as MR
+import march_ref as R
 import pyapes_oracle as O
-import velocity_ref as R
+from march_ref import momentum as MR
 from pyapes_amd.solver import march as M
 from pyapes_amd.solver.march import euler_march, euler_step, momentum_march, momentum_step, rk_march, rk_step
 
@@ -49,7 +49,7 @@ def _vector_case(n, dtype, seed=11):
 @pytest.mark.parametrize("limiter", ["upwind", "quick"])
 @pytest.mark.parametrize("n,dtype", [([7, 9, 12], "single"), ([17, 12], "double")], ids=["3d_f32", "2d_f64"])
 def test_a_stage_is_the_velocity_step_of_every_component(n, dtype, limiter):
-    """component c of a stage is velocity_ref's step of V_c in the velocity V with c's BCs, computed from the INPUT: stepping
+    """component c of a stage is march_ref's step of V_c in the velocity V with c's BCs, computed from the INPUT: stepping
     the components one after another in place (each seeing its predecessors' output) is another result"""
     mesh, bcs, U, S = _vector_case(n, dtype)
     nd = len(n)

@@ -1,4 +1,4 @@
-"""No GPU: the QUICK advection scheme (Div limiter "quick"), restated on the CPU in tests/quick_ref.py, and the host-side
+"""No GPU: the QUICK advection scheme (Div limiter "quick"), restated on the CPU in tests/march_ref.py, and the host-side
 checks in front of the device.  Figures are what the restatement gives on the CPU (float64); bounds carry about 20 % margin.
 
 1. Quadratic 1 + 2x - y + 3z + x^2 - 2y^2 + z^2/2 on 9 x 11 x 13, u = 1.3 and -0.7: exact at every interior node (the central
@@ -24,8 +24,8 @@ import math
 import pytest
 import torch
 
+import march_ref as Q
 import pyapes_oracle as O
-import quick_ref as Q
 from test_rk_host import ORDER_BOUNDS, _case as pulse_case
 from test_self_march_host import BURGERS_NU, burgers_error
 
@@ -80,8 +80,8 @@ def test_mirror_symmetry_bit_for_bit():
     mesh, bcs = _line(201)
     g = _gauss(mesh, bcs, 0.6)
     dt = 0.4 * mesh.dx_list[0]
-    a = Q.march_quick(g, 1.0, 0.0, dt, 50, mesh, bcs, 3)
-    b = Q.march_quick(torch.flip(g, [1]).contiguous(), -1.0, 0.0, dt, 50, mesh, bcs, 3)
+    a = Q.march(g, 1.0, 0.0, dt, 50, mesh, bcs, "quick", 3)
+    b = Q.march(torch.flip(g, [1]).contiguous(), -1.0, 0.0, dt, 50, mesh, bcs, "quick", 3)
     assert torch.equal(a, torch.flip(b, [1]))
     assert float((a - g).abs().max()) > 0.1     # it moved
 
@@ -115,8 +115,8 @@ def check_advected_gaussian(e):
 def test_advected_gaussian():
     def march(mesh, bcs, start, dt, nsteps, limiter):
         if limiter == "quick":
-            return Q.march_quick(start, 1.0, 0.0, dt, nsteps, mesh, bcs, 3)
-        return Q.march_limiter(start, 1.0, 0.0, dt, nsteps, mesh, bcs, limiter, 3)
+            return Q.march(start, 1.0, 0.0, dt, nsteps, mesh, bcs, "quick", 3)
+        return Q.march(start, 1.0, 0.0, dt, nsteps, mesh, bcs, limiter, 3, step=O.euler_step)
     check_advected_gaussian(advected_gaussian_errors(march))
 
 
@@ -129,8 +129,8 @@ def test_stability_needs_the_order_three_march():
     mesh, bcs = _line(129, 1.0)
     start = O.bc_fill(stability_start(), bcs)
     dx = mesh.dx_list[0]
-    euler = float(Q.march_quick(start, 1.0, 0.0, 0.5 * dx, 600, mesh, bcs, 1).abs().max())
-    rk3 = float(Q.march_quick(start, 1.0, 0.0, 1.0 * dx, 600, mesh, bcs, 3).abs().max())
+    euler = float(Q.march(start, 1.0, 0.0, 0.5 * dx, 600, mesh, bcs, "quick", 1).abs().max())
+    rk3 = float(Q.march(start, 1.0, 0.0, 1.0 * dx, 600, mesh, bcs, "quick", 3).abs().max())
     print(f"stability: Euler CFL 0.5 -> {euler:.3e}, order 3 CFL 1.0 -> {rk3:.3e}")
     assert euler > 1e6
     assert rk3 <= 1.0
@@ -141,8 +141,8 @@ def test_stability_needs_the_order_three_march():
 def test_order_in_time(order, self_adv):
     mesh, bcs, phi0 = pulse_case()
     nu, T = 0.05, 0.02
-    ref = Q.march_quick(phi0, 1.0, nu, T / 640, 640, mesh, bcs, 3, self_adv)
-    err = [float((Q.march_quick(phi0, 1.0, nu, T / n, n, mesh, bcs, order, self_adv) - ref).abs().max()) for n in (20, 40, 80)]
+    ref = Q.march(phi0, 1.0, nu, T / 640, 640, mesh, bcs, "quick", 3, self_adv=self_adv)
+    err = [float((Q.march(phi0, 1.0, nu, T / n, n, mesh, bcs, "quick", order, self_adv=self_adv) - ref).abs().max()) for n in (20, 40, 80)]
     ratios = (err[0] / err[1], err[1] / err[2])
     print(f"order {order} self {self_adv}: errors {err}, ratios {ratios}")
     lo, hi = ORDER_BOUNDS[order]
@@ -162,7 +162,7 @@ def test_burgers_second_order():
         n = start.shape[1]
         mesh = O.OMesh([0.0], [2 * math.pi], [n], "double")
         bcs = O.make_bcs(mesh, O.mixed_cfg(list(ends), ["dirichlet", "dirichlet"]))
-        return Q.march_quick(O.bc_fill(start.clone(), bcs), None, BURGERS_NU, dt, steps, mesh, bcs, 3, True)
+        return Q.march(O.bc_fill(start.clone(), bcs), None, BURGERS_NU, dt, steps, mesh, bcs, "quick", 3, self_adv=True)
     check_burgers(*(burgers_error(n, "quick", march) for n in (101, 201)))
 
 

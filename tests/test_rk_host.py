@@ -1,5 +1,6 @@
 """No GPU: the SSP Runge-Kutta stage table of pyapes_amd/solver/march.py and what the schemes built from it do, on the
-CPU, composed from the oracle's own Euler step (oracle.euler_step, the function the GPU Euler step is pinned against).
+CPU, composed by tests/march_ref.py from the oracle's own Euler step (oracle.euler_step, the function the GPU Euler step is
+pinned against).
 
 A stage of a step is  c0 * phi0 + c1 * E(phi_s)  (Shu-Osher form); the plain first stage phi1 = E(phi0) is implied.
   order 2:  phi' = 1/2 phi0 + 1/2 E(phi1)
@@ -22,6 +23,7 @@ from fractions import Fraction
 import pytest
 import torch
 
+import march_ref
 import pyapes_oracle as O
 from pyapes_amd.solver.march import SSP_STAGES, rk_march, rk_step
 
@@ -36,18 +38,6 @@ def _case():
     phi = torch.exp(-((x - 0.4) ** 2 + (y - 0.5) ** 2) / 0.01).unsqueeze(0)
     O.bc_fill(phi, bcs)
     return mesh, bcs, phi
-
-
-def oracle_rk_march(phi, u, nu, dt, nsteps, mesh, bcs, limiter, order):
-    """the scheme of ``order`` from march.py's stage table, every stage  B(c0 phi0 + c1 E(phi_s))  with the oracle's E"""
-    for _ in range(nsteps):
-        phi0 = phi
-        phi = O.euler_step(phi0, u, nu, dt, mesh, bcs, limiter)
-        for c0, c1 in SSP_STAGES[order]:
-            e = O.euler_step(phi, u, nu, dt, mesh, bcs, limiter)
-            phi = (c0 * phi0) + (c1 * e)
-            O.bc_fill(phi, bcs)
-    return phi
 
 
 def test_stage_table_is_convex_and_sums_to_one():
@@ -83,8 +73,9 @@ def test_bad_order_raises_before_a_device_is_touched():
 def test_order_in_time(order, limiter):
     mesh, bcs, phi0 = _case()
     u, nu, T = 1.0, 0.05, 0.02
-    ref = oracle_rk_march(phi0, u, nu, T / 640, 640, mesh, bcs, limiter, 3)
-    err = [float((oracle_rk_march(phi0, u, nu, T / n, n, mesh, bcs, limiter, order) - ref).abs().max()) for n in (20, 40, 80)]
+    ref = march_ref.march(phi0, u, nu, T / 640, 640, mesh, bcs, limiter, 3, step=O.euler_step)
+    err = [float((march_ref.march(phi0, u, nu, T / n, n, mesh, bcs, limiter, order, step=O.euler_step) - ref).abs().max())
+           for n in (20, 40, 80)]
     ratios = (err[0] / err[1], err[1] / err[2])
     print(f"order {order} {limiter}: errors {err}, ratios {ratios}")
     lo, hi = ORDER_BOUNDS[order]
@@ -99,7 +90,7 @@ def test_order_three_marches_central_advection_that_euler_cannot():
     ends = {}
     for cfl, steps in ((1.0, 8), (1.5, 5)):
         for order in (1, 2, 3):
-            ends[cfl, order] = float(oracle_rk_march(phi0, 1.0, 0.0, cfl * dx / 1.0, steps, mesh, bcs, "none", order).abs().max())
+            ends[cfl, order] = float(march_ref.march(phi0, 1.0, 0.0, cfl * dx / 1.0, steps, mesh, bcs, "none", order, step=O.euler_step).abs().max())
     print("max|phi| at the end:", ends)
     assert ends[1.0, 3] <= top and ends[1.5, 3] <= top, ends
     assert ends[1.0, 1] >= 2 * top, ends

@@ -1,4 +1,4 @@
-"""No GPU: the source term of the explicit marches, ``source=S``, on the CPU -- tests/source_ref.py (the step E_S, the stage and
+"""No GPU: the source term of the explicit marches, ``source=S``, on the CPU -- tests/march_ref.py (the step E_S, the stage and
 the march restated operation for operation as the kernels compute them) against the oracle, what the schemes built from E_S
 do, and the argument checks of pyapes_amd/solver/march.py that fire before a device is touched.
 
@@ -25,8 +25,8 @@ import math
 import pytest
 import torch
 
+import march_ref as R
 import pyapes_oracle as O
-import source_ref as R
 from pyapes_amd.solver.march import euler_march, euler_step, rk_march, rk_step
 
 N = 33

@@ -1,7 +1,7 @@
-"""No GPU: the marches in a velocity field -- one advection speed per mesh axis -- on the CPU.  tests/velocity_ref.py (the step,
-the stage and the march restated operation for operation as the kernels compute them) against tests/source_ref.py and the
-oracle, what the scheme does (an exact shift, a solid-body rotation), and the argument checks of pyapes_amd/solver/march.py,
-which fire before a device is touched.
+"""No GPU: the marches in a velocity field -- one advection speed per mesh axis -- on the CPU.  The velocity form of
+tests/march_ref.py (the step, the stage and the march restated operation for operation as the kernels compute them) against
+its one-speed form and the oracle, what the scheme does (an exact shift, a solid-body rotation), and the argument checks of
+pyapes_amd/solver/march.py, which fire before a device is touched.
 
 Solid-body rotation (measured on the CPU, printed by the test): a Gaussian of width 0.08 at (0.5, 0.3) on [0, 1]^2, angular
 speed 2 pi about the centre, a quarter turn, order 3, nu = 0, dt = 0.2 dx / max|u|, all faces dirichlet 0.  Max-abs error
@@ -16,9 +16,8 @@ import math
 import pytest
 import torch
 
+import march_ref as R
 import pyapes_oracle as O
-import source_ref as S
-import velocity_ref as R
 from pyapes_amd.solver import march as M
 from pyapes_amd.solver.march import euler_march, euler_step, rk_march, rk_step
 
@@ -39,23 +38,23 @@ def _mesh_and_field(n, dtype, seed=3):
 @pytest.mark.parametrize("n,dtype", [([7, 9, 12], "single"), ([7, 9, 12], "double"), ([17, 12], "double"), ([33], "single")],
                          ids=["3d_f32", "3d_f64", "2d_f64", "1d_f32"])
 def test_equal_components_are_the_single_speed(n, dtype, limiter):
-    """(c, .., c) and (U, .., U): bit-identical to source_ref.euler_step with the one speed, with and without a source"""
+    """(c, .., c) and (U, .., U): bit-identical to the one-speed march_ref.euler_step, with and without a source"""
     mesh, bcs, phi, U = _mesh_and_field(n, dtype)
     nd = len(n)
     src = torch.randn(phi.shape, generator=torch.Generator().manual_seed(5), dtype=torch.float64).to(phi.dtype)
     for c in (0.9, -0.8):
         for s in (None, src, 1.75):
             assert torch.equal(R.euler_step(phi, [c] * nd, 0.05, 1e-3, mesh, bcs, limiter, s),
-                               S.euler_step(phi, c, 0.05, 1e-3, mesh, bcs, limiter, s))
+                               R.euler_step(phi, c, 0.05, 1e-3, mesh, bcs, limiter, s))
     one = U[0:1]
     for s in (None, src):
         assert torch.equal(R.euler_step(phi, [one[0]] * nd, 0.05, 1e-3, mesh, bcs, limiter, s),
-                           S.euler_step(phi, one, 0.05, 1e-3, mesh, bcs, limiter, s))
+                           R.euler_step(phi, one, 0.05, 1e-3, mesh, bcs, limiter, s))
     assert torch.equal(R.march(phi, [one[0]] * nd, 0.05, 1e-3, 2, mesh, bcs, limiter, 3, src),
-                       S.march(phi, one, 0.05, 1e-3, 2, mesh, bcs, limiter, 3, src))
+                       R.march(phi, one, 0.05, 1e-3, 2, mesh, bcs, limiter, 3, src))
 
 
-# the eight BC sets and the mesh shapes of tests/test_gpu_chunks.py / test_gpu_chunks_terms.py, which use BOTH references
+# the eight BC sets and the mesh shapes of tests/test_gpu_chunks.py / test_gpu_chunks_terms.py, which use BOTH forms
 _D, _N, _S, _P = "dirichlet", "neumann", "symmetry", "periodic"
 CHUNK_BCS = {
     "NEUSYM": ([0.0, 0.0, None, None, None, None], [_N, _N, _S, _S, _S, _S]),
@@ -72,9 +71,9 @@ CHUNK_BCS = {
 @pytest.mark.parametrize("limiter", ["upwind", "quick", "none"])
 @pytest.mark.parametrize("dtype", ["double", "single"])
 def test_the_two_references_agree_on_the_chunk_test_meshes(dtype, limiter):
-    """with a source field, a stage of velocity_ref with three equal components is the stage of source_ref, bit for bit and
-    finite: on the eight BC sets and the row counts / row lengths of the chunk tests (eight-node rows, one- and two-tile rows),
-    so that both references are defined on every input those tests hand them"""
+    """with a source field, a stage of march_ref in a velocity of three equal components is its stage with the one speed, bit for
+    bit and finite: on the eight BC sets and the row counts / row lengths of the chunk tests (eight-node rows, one- and two-tile rows),
+    so that both forms are defined on every input those tests hand them"""
     tdt = torch.float64 if dtype == "double" else torch.float32
     ran = 0
     for n in ([5, 19, 36], [9, 5, 32], [6, 6, 32], [7, 8, 8], [13, 9, 132 if dtype == "double" else 260]):
@@ -93,7 +92,7 @@ def test_the_two_references_agree_on_the_chunk_test_meshes(dtype, limiter):
             nu, dt = 1e-3, 0.2 * min(dx * dx / 6e-3, dx / 1.3)
             for u_vel, u_one in (([-0.8] * 3, -0.8), ([U[0]] * 3, U)):
                 a = R.rk_stage(phi, phi0, 0.75, 0.25, u_vel, nu, dt, mesh, bcs, limiter, src)
-                b = S.rk_stage(phi, phi0, 0.75, 0.25, u_one, nu, dt, mesh, bcs, limiter, src)
+                b = R.rk_stage(phi, phi0, 0.75, 0.25, u_one, nu, dt, mesh, bcs, limiter, src)
                 assert bool(torch.isfinite(a).all()) and torch.equal(a, b), (n, name)
                 ran += 1
     assert ran == (40 if limiter == "none" else 80)
