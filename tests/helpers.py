@@ -119,6 +119,40 @@ def bit_equal(a, b):
     return torch.equal(torch.as_tensor(a).cpu(), torch.as_tensor(b).cpu())
 
 
+GUARD_SENTINEL = -123456.789   # finite, and no input of the tests holds it (fields are rand / randn / small BC values)
+
+
+def offset_view(t, k, guard=16):
+    """``t`` as an operand that is NOT 16-byte aligned: a contiguous view of ``t``'s shape, holding ``t``'s values, that
+    starts ``k`` elements past a 16-byte boundary inside a fresh allocation (same dtype and device) with at least ``guard``
+    elements in front of it and behind it, all GUARD_SENTINEL.  ``k`` = 0 gives an aligned view with the same guards.
+    Returns (view, allocation).  Every access a kernel makes to the view, of any width, stays inside the allocation; a
+    store outside the array shows up as a changed guard (``guards_intact``)."""
+    t = torch.as_tensor(t)
+    n = t.numel()
+    guard, k = max(int(guard), 1), int(k)
+    alloc = torch.full((guard + 16 + k + n + guard + 16,), GUARD_SENTINEL, dtype=t.dtype, device=t.device)
+    es = alloc.element_size()
+    # the first 16-byte boundary at least `guard` elements in (device allocations start on one; a host one need not)
+    front = guard + (-(alloc.data_ptr() // es + guard)) % max(16 // es, 1) + k
+    view = alloc[front:front + n].view(t.shape)
+    view.copy_(t)
+    assert view.is_contiguous() and view.data_ptr() == alloc.data_ptr() + front * es
+    assert view.data_ptr() % 16 == (k * es) % 16
+    return view, alloc
+
+
+def guards_intact(alloc, view):
+    """True when every element of ``alloc`` outside ``view`` still holds GUARD_SENTINEL, bit for bit."""
+    es = alloc.element_size()
+    front = (view.data_ptr() - alloc.data_ptr()) // es
+    bits = {8: torch.int64, 4: torch.int32, 2: torch.int16}[es]
+    a = alloc.view(bits)
+    want = torch.full((1,), GUARD_SENTINEL, dtype=alloc.dtype, device=alloc.device).view(bits)
+    lo, hi = a[:front], a[front + view.numel():]
+    return lo.numel() > 0 and hi.numel() > 0 and bool((lo == want).all()) and bool((hi == want).all())
+
+
 class SumTap:
     """Records the value of every ``torch.sum(t, dim=...)`` made while it is active -- the dot products of the
     reference's (and the oracle's) solver loops (linalg.py:119-137, 204-250), which is all they use it for.

@@ -19,7 +19,7 @@ import pyapes_oracle as O
 import test_gpu_rk as R
 import test_quick_host as H
 import test_self_march_host as HS
-from helpers import bit_equal
+from helpers import bit_equal, offset_view
 from march_gpu import XPER
 from pyapes_amd.geometry import Box, Cylinder
 from pyapes_amd.hip import lib as L
@@ -81,11 +81,10 @@ def _setup(name, seed=13):
     finally:
         del R.CASE[key]
     if misaligned:
-        big = torch.empty(phis.numel() + 8, dtype=phis.dtype, device="cuda")
-        view = big[1:1 + phis.numel()].view(phis.shape)
-        view.copy_(phis)
-        phis = view
-        assert phis.data_ptr() % 16 != 0
+        shape, values = phis.shape, phis.clone()
+        phis, _ = offset_view(phis, 1)
+        assert phis.is_contiguous() and phis.data_ptr() % 16 != 0
+        assert phis.shape == shape and phis.is_cuda and torch.equal(phis, values)
     if u == "self":
         uu = phis
     return mesh, bc, phis, phi0, uu, nu, dt

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import march_gpu as G
-from helpers import bit_equal
+from helpers import bit_equal, offset_view
 from march_gpu import ALLDIR, MIXED
 from pyapes_amd.geometry import Box
 from pyapes_amd.hip.context import context_for
@@ -89,11 +89,10 @@ def _setup(name, seed=9):
         filled.append(f().clone())
     phis, phi0 = filled
     if misaligned:   # a contiguous view one element into a larger allocation: not 16-byte aligned
-        big = torch.empty(phi0.numel() + 8, dtype=phi0.dtype, device="cuda")
-        view = big[1:1 + phi0.numel()].view(phi0.shape)
-        view.copy_(phi0)
-        phi0 = view
+        shape, values = phi0.shape, phi0.clone()
+        phi0, _ = offset_view(phi0, 1)
         assert phi0.is_contiguous() and phi0.data_ptr() % 16 != 0
+        assert phi0.shape == shape and phi0.is_cuda and torch.equal(phi0, values)
     dx = min(float(d) for d in mesh.dx_list)
     nu = 1e-3
     dt = 0.2 * min(dx * dx / (2 * len(n) * nu), dx / 1.3)
