@@ -57,7 +57,10 @@ def main():
                          "fused stages against the composition of public pieces, then the self-advected march; self: those rows "
                          "alone; self_baselines: their two comparison rows alone, which need no self march in the library), "
                          "quick (the QUICK Euler step and order-3 march on k_sfq beside the generic kernel and beside upwind; not in "
-                         "the default list; quick_baseline: the upwind rows alone, which a library without QUICK can run), source (euler_march "
+                         "the default list; quick_baseline: the upwind rows alone, which a library without QUICK can run), tvd (rk_march orders 1 and 3 with "
+                         "the slope-limited limiters minmod and mc, a scalar speed and a speed field, on k_sfq and with sfq 0, beside quick and "
+                         "upwind, 256^3 fp32 config-4 BCs and 256^3 fp64 all-dirichlet; not in the default list; tvd_baseline: the quick and "
+                         "upwind rows alone, which a library without the limiters can run), source (euler_march "
                          "and rk_march order 3 with a scalar source and a source field, beside no source, the euler_step + torch add + "
                          "apply_bcs workaround and the generic kernel; not in the default list; source_baseline: the no-source rows alone, "
                          "which a library without the source term can run), velocity (euler_march and rk_march order 3 with a "
@@ -113,6 +116,8 @@ def main():
         rk_rows(q, emit)
     if sections & {"quick", "quick_baseline"}:
         quick_rows(q, emit, with_quick="quick" in sections)
+    if sections & {"tvd", "tvd_baseline"}:
+        tvd_rows(q, emit, with_tvd="tvd" in sections)
     if sections & {"rk", "self", "self_baselines"}:
         self_rows(q, emit, with_self=bool(sections & {"rk", "self"}))
     if sections & {"source", "source_baseline"}:
@@ -264,6 +269,65 @@ def quick_rows(q, emit, with_quick=True):
                 emit(f"{what} {n}^3 f32 {vname} {uname} (config 4 BCs)", n ** 3, ms, passes, 4,
                      {"ms_rounds": rounds[vname], "over_upwind_bcl0": ms / base, "options": opts})
         for k, v in (("sfq", 1), ("bcl", 1)) if with_quick else (("bcl", 1),):
+            ctx.set_option(k, v)
+        del mesh, start, ut
+        torch.cuda.empty_cache()
+
+
+def tvd_rows(q, emit, with_tvd=True):
+    """Div limiters "minmod" and "mc" (the SCH instantiations of k_sfq, csrc/pa_sft.hip): rk_march of orders 1 and 3 with a scalar
+    speed and with a speed field, 256^3 fp32 with the config-4 BCs and 256^3 fp64 all-dirichlet -- each limiter on k_sfq and on the
+    generic kernel ("sfq": 0), beside "quick" (same footprint, same streams), "quick" with "sfq": 0 and "upwind" with "bcl": 0 (step
+    + fill per launch, what the schemes with a reach of 2 do too).  One sample is ONE march of 20 steps (ms per STEP); the variants
+    of a row are timed in turn, five rounds after a warm-up march each: "ms" is the median, "ms_min" the minimum, "ms_rounds" all
+    five.  Algorithmic passes as for upwind: per Euler stage 2 (3 with a speed field), the two fused stages of order 3 read phi0
+    as well."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.march import rk_march
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    cfg = {lim: {"div": {"limiter": lim}} for lim in ("upwind", "quick", "minmod", "mc")}
+    nu, steps, rounds_n = 1e-3, 20, 5
+    variants = [("upwind bcl 0", "upwind", {"bcl": 0, "sfq": 1}), ("quick", "quick", {"bcl": 1, "sfq": 1}), ("quick sfq 0", "quick", {"sfq": 0})]
+    if with_tvd:   # (a library from before the limiters does not know the kinds)
+        variants += [("minmod", "minmod", {"sfq": 1}), ("minmod sfq 0", "minmod", {"sfq": 0}), ("mc", "mc", {"sfq": 1}),
+                     ("mc sfq 0", "mc", {"sfq": 0})]
+    n = 128 if q else 256
+    setups = [("single", "f32", 4, "config 4 BCs", mixed_bcs([0.0, 0.0, None, None, None, None],
+                                                           ["neumann", "neumann", "symmetry", "symmetry", "symmetry", "symmetry"])),
+              ("double", "f64", 8, "all dirichlet", mixed_bcs([0.0] * 6, ["dirichlet"] * 6))]
+    for dtype, fname, esize, bcname, bcs in setups:
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", dtype)
+        ctx = context_for(mesh)
+        start = torch.exp(-((mesh.X - 0.5) ** 2 + (mesh.Y - 0.5) ** 2 + (mesh.Z - 0.5) ** 2) / 0.02).unsqueeze(0).contiguous()
+        dx = mesh.dx_list[0]
+        dt = 0.2 * min(dx * dx / (6 * nu), dx / 1.0)
+        ut = (0.7 * torch.cos(6.0 * mesh.X) * torch.cos(4.0 * mesh.Y + 2.0 * mesh.Z)).unsqueeze(0).contiguous()   # both signs
+        for order in (1, 3):
+            for uname, u, passes in (("scalar u", 1.0, 2 if order == 1 else 8), ("speed field", ut, 3 if order == 1 else 11)):
+                def one_march(lim):
+                    phi = Field("phi", 1, mesh, {"domain": bcs, "obstacle": None})
+                    phi.set_var_tensor(start.clone())
+                    phi.apply_bcs()
+                    ms = timed(lambda: rk_march(phi, u, nu, dt, steps, cfg[lim], order=order), 1, warm=0) / steps
+                    assert bool(torch.isfinite(phi()).all())
+                    return ms
+                rounds = {v[0]: [] for v in variants}
+                for r in range(rounds_n + 1):        # round 0: the warm-up march of every variant
+                    for vname, lim, opts in variants:
+                        for k, v in opts.items():
+                            ctx.set_option(k, v)
+                        ms = one_march(lim)
+                        if r:
+                            rounds[vname].append(ms)
+                base = sorted(rounds["quick"])[rounds_n // 2]
+                for vname, lim, opts in variants:
+                    ms = sorted(rounds[vname])[rounds_n // 2]
+                    emit(f"rk_march order {order} ({steps} steps per call) {n}^3 {fname} {vname} {uname} ({bcname})", n ** 3, ms, passes,
+                         esize, {"ms_min": min(rounds[vname]), "ms_rounds": rounds[vname], "over_quick": ms / base, "options": opts})
+        for k, v in (("sfq", 1), ("bcl", 1)):
             ctx.set_option(k, v)
         del mesh, start, ut
         torch.cuda.empty_cache()

@@ -47,7 +47,24 @@ enum {
   /* QUICK, advective form, the speed taken at the node (DESIGN.md "QUICK"): explicit entry points only -- pa_div,
    * pa_euler_step / _march, pa_rk_stage / _march / _march_self -- on one GPU and an xyz mesh, every active axis with at
    * least 5 nodes.  pa_eq_set, pa_rhs_adjust and pa_div_general refuse it (PA_E_ARG), a slab does (PA_E_STATE). */
-  PA_OP_DIV_QUICK = 5
+  PA_OP_DIV_QUICK = 5,
+  /* Slope-limited (TVD) second-order advection, "bounded advection" (DESIGN.md section 4): advective form, the speed u read
+   * at the node, u+ = max(u, 0), u- = min(u, 0).  Per active axis a, with wrap-around neighbours at distance 1 and 2, every
+   * operation rounded on its own (no FMA):
+   *     dm = x - x[-1];  dp = x[+1] - x;  dmm = x[-1] - x[-2];  dpp = x[+2] - x[+1]
+   *     s0 = L(dm, dp);  sm = L(dmm, dm);  sp = L(dp, dpp)
+   *     t = s0 - sm;  t = 0.5 t;  bq = dm + t            (with u+)
+   *     t = sp - s0;  t = 0.5 t;  fq = dp - t            (with u-)
+   *     p = u+ bq;  m = u- fq;  p = p + m;  term_a = p * fl(1 / dx_a);      adv = (+0) + term_0 + term_1 + term_2
+   * L = minmod for PA_OP_DIV_MINMOD: v = 0; a, b >= 0: v = min(a, b); a, b < 0: v = max(a, b); a * b <= 0: v = 0 (the
+   * limiter of pa_limiter, which = 0).  PA_OP_DIV_MC: v = minmod(a, b); s = a + b; L = minmod(2 v, s / 2) (which = 1).
+   * On an axis without a periodic face the half whose far-upwind node would wrap falls back to FIRST-ORDER UPWIND (not to
+   * central, as QUICK does: the scheme stays bounded beside a wall): bq = dm at node index <= 1, fq = dp at index >= N - 2.
+   * Accepted and refused where PA_OP_DIV_QUICK is: the explicit entry points only (pa_div, the steps, stages and marches,
+   * their _src and _vel forms, pa_momentum_march), one GPU (PA_E_STATE on a slab), xyz meshes, at least 5 nodes per active
+   * axis (PA_E_ARG); neumann / symmetry faces are allowed; pa_eq_set, pa_rhs_adjust and pa_div_general refuse them. */
+  PA_OP_DIV_MINMOD = 6,
+  PA_OP_DIV_MC = 7
 };
 
 enum {

@@ -335,7 +335,7 @@ int pa_ctx_set_option(pa_ctx* c, const char* name, int value) {
   else if (!strcmp(name, "sf")) c->sf = (value == 2 || value == 4) ? value : (value != 0);   // k_sf (else k_cg3d's single-field phases; 2 / 4: that many rows per wave, tests)
   else if (!strcmp(name, "chunks")) c->chunks = value < 0 ? 0 : value;   // cap of the axis-0 chunk count of k_sf / k_sfq / k_cg3d (0: their rule alone; tests)
   else if (!strcmp(name, "vself")) c->vself = value != 0;   // pa_momentum_march: VEL 3 (0: the aliased VEL 2 instantiations, same bits; A/B runs)
-  else if (!strcmp(name, "sfq")) c->sfq = value < 0 ? 0 : value;   // k_sfq for QUICK (0: the generic Euler kernel; 2 / 4: that many rows per wave, A/B runs)
+  else if (!strcmp(name, "sfq")) c->sfq = value < 0 ? 0 : value;   // k_sfq for QUICK / minmod / mc (0: the generic Euler kernel; 2 / 4: that many rows per wave, A/B runs; minmod / mc: 4 means 2)
   else if (!strcmp(name, "fold")) c->fold = value != 0;         // scalar steps in the next kernel's prologue
   else if (!strcmp(name, "resident")) c->resident = value != 0; // small meshes: one cooperative launch per solve
   else if (!strcmp(name, "cg2d_mincells")) c->cg2d_mincells = value;   // k_cg2d from this many cells on (< 0: never)
@@ -510,6 +510,7 @@ int pa_eq_set(pa_ctx* c, int nterms, const pa_term* terms) {
   for (int q = 0; q < nterms; ++q) {
     int k = terms[q].kind;
     if (k == PA_OP_DIV_QUICK) { pa_set_err(c, "pa_eq_set: Div quick is explicit-only (no solver equations)"); return PA_E_ARG; }
+    if (k == PA_OP_DIV_MINMOD || k == PA_OP_DIV_MC) { pa_set_err(c, "pa_eq_set: Div minmod / mc is explicit-only (no solver equations)"); return PA_E_ARG; }
     if (k < PA_OP_LAPLACIAN || k > PA_OP_DIV_UPWIND) { pa_set_err(c, "pa_eq_set: bad kind"); return PA_E_ARG; }
     if (k == PA_OP_DIV_CENTRAL)
       for (int f = 0; f < 6; ++f)

@@ -166,6 +166,60 @@ __device__ __forceinline__ void pa_nbrs2(const DevGeom& G, const Acc& a, int ax,
   }
 }
 
+// ---- the slope-limited (TVD) advection halves, PA_OP_DIV_MINMOD = 6 / PA_OP_DIV_MC = 7 (include/pyapes_hip.h, DESIGN.md
+// section 4 "Bounded advection") ----
+// minmod(a, b) as pa_rfp.hip's minmod1 states it (the reference's limiter, bit for bit)
+template <typename T>
+__device__ __forceinline__ T pa_minmod1(T a, T b) {
+  T v = (T)0;
+  if (a >= (T)0 && b >= (T)0) v = a < b ? a : b;
+  if (a < (T)0 && b < (T)0) v = a > b ? a : b;
+  if (a * b <= (T)0) v = (T)0;
+  return v;
+}
+
+// the limited slope L(a, b): minmod (scheme 6), or monotonized central minmod(2 minmod(a, b), (a + b) / 2) (scheme 7,
+// k_limiter's order of operations)
+template <typename T>
+__device__ __forceinline__ T pa_tvd_slope(T a, T b, int scheme) {
+  T v = pa_minmod1<T>(a, b);
+  if (scheme == 7) {
+    T s = a + b;
+    v = pa_minmod1<T>((T)2 * v, s / (T)2);
+  }
+  return v;
+}
+
+// The two halves of one axis at one node from x[-2] .. x[+2]: bq goes with u+ = max(u, 0), fq with u- = min(u, 0).
+//   dm = x - x[-1]; dp = x[+1] - x; dmm = x[-1] - x[-2]; dpp = x[+2] - x[+1]
+//   s0 = L(dm, dp); sm = L(dmm, dm); sp = L(dp, dpp)
+//   bq = dm + 0.5 (s0 - sm);  fq = dp - 0.5 (sp - s0)        every operation rounded on its own
+// lo / hi: the half's far-upwind node would wrap on an axis without a periodic face (node index <= 1 / >= N - 2) -- the
+// half falls back to first-order upwind, bq = dm / fq = dp, so that the scheme stays bounded beside a wall.
+// BQ / FQ: the halves that are wanted (the tiled kernel with a scalar speed forms one; the other one is not touched).
+template <typename T, bool BQ = true, bool FQ = true>
+__device__ __forceinline__ void pa_tvd_halves(T xmm, T xm, T xc, T xp, T xpp, bool lo, bool hi, int scheme, T& bq, T& fq) {
+  const T dm = xc - xm;
+  const T dp = xp - xc;
+  const T s0 = pa_tvd_slope<T>(dm, dp, scheme);
+  if constexpr (BQ) {
+    const T dmm = xm - xmm;
+    const T sm = pa_tvd_slope<T>(dmm, dm, scheme);
+    T t = s0 - sm;
+    t = (T)0.5 * t;
+    t = dm + t;
+    bq = lo ? dm : t;
+  }
+  if constexpr (FQ) {
+    const T dpp = xpp - xp;
+    const T sp = pa_tvd_slope<T>(dp, dpp, scheme);
+    T t = sp - s0;
+    t = (T)0.5 * t;
+    t = dp - t;
+    fq = hi ? dp : t;
+  }
+}
+
 __device__ __forceinline__ void pa_gidx(const DevGeom& G, int64_t i, int64_t j, int64_t k, int64_t* g,
                                         int64_t* N) {
   g[0] = i + G.off0; g[1] = j; g[2] = k;
@@ -195,7 +249,10 @@ __device__ __forceinline__ int pa_row_case(const DevGeom& G, int ax, int64_t g, 
 }
 
 // sum_k sign_k * param_k * Op_k(acc)   at local node (i,j,k); xc = acc.at(i,j,k)
-template <typename T, class Acc>
+// TVD: the term list may hold the explicit-only kinds PA_OP_DIV_MINMOD / _MC (the TVD instantiations of k_aop for pa_div and of
+// k_euler for the steps).  Every other kernel -- the solver kernels never see them, pa_eq_set refuses -- is compiled without
+// that branch and stays the code it was.
+template <typename T, bool TVD = false, class Acc>
 __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E, const Acc& acc, int64_t i,
                                             int64_t j, int64_t k, T xc) {
   int64_t g[3], N[3];
@@ -329,6 +386,25 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
         sq = (T)0.125 * xpp;
         T fq = tq - sq;
         if (!per && g[a] >= N[a] - 2) fq = cen;
+        T s = upl * bq;
+        T m = umi * fq;
+        s = s + m;
+        s = s * E.grd.ih[a];
+        ax = ax + s;
+      }
+    } else if (TVD && (t.kind == 6 || t.kind == 7)) {  // PA_OP_DIV_MINMOD / _MC (DESIGN.md "Bounded advection"): as QUICK, limited halves
+      T ucen = t.u_f ? t.u_f[o] : t.u;
+      T upl = ucen > (T)0 ? ucen : (T)0;
+      T umi = ucen < (T)0 ? ucen : (T)0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        if (!G.act[a]) continue;
+        T xp, xm, xpp, xmm;
+        pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
+        pa_nbrs2<T>(G, acc, a, i, j, k, xpp, xmm);
+        const bool per = G.bct[2 * a] == 4 || G.bct[2 * a + 1] == 4;
+        T bq, fq;
+        pa_tvd_halves<T>(xmm, xm, xc, xp, xpp, !per && g[a] <= 1, !per && g[a] >= N[a] - 2, t.kind, bq, fq);
         T s = upl * bq;
         T m = umi * fq;
         s = s + m;

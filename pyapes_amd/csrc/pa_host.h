@@ -189,7 +189,7 @@ struct pa_ctx {
   int64_t prof_n[2] = {0, 0};
   // 3-D fast path switch (PYAPES_HIP_FASTPATH=0 disables; tests compare both)
   int fastpath = 1;
-  int sfq = 1;                   // option "sfq": k_sfq for the QUICK Euler step / stage (0: the generic k_euler; 2 / 4: rows per wave forced); pa_sfq_kernel.h
+  int sfq = 1;                   // option "sfq": k_sfq for the QUICK / minmod / mc Euler step / stage (0: the generic k_euler; 2 / 4: rows per wave forced); pa_sfq_kernel.h
   int sf = 1;                    // option "sf": k_sf for the Div-carrying single-field operations (0: k_cg3d's phases; 2 / 4: rows per wave forced, pa_sf_kernel.h sf_rows_per_wave)
   int vself = 1;                 // option "vself": pa_momentum_march's upwind step on k_sf's VEL 3 instantiations (0: VEL 2 with the own component's pointer aliased into the input; same bits)
   int chunks = 0;                // option "chunks": N > 0 caps the axis-0 chunk count of k_sf / k_sfq / k_cg3d behind their rule (0: the rule alone)
@@ -317,10 +317,12 @@ template <typename T>
 int pa_tile3d_aop(pa_ctx* c, const DevEq<T>& E, Vec<T> x, T* y, int interior_only);
 template <typename T>
 int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd);
-// the QUICK Euler step / stage on k_sfq (pa_sfq.hip): blocks launched, 0 when k_sfq does not take the launch
+// the Euler step / stage of the schemes with a reach of 2 on k_sfq (pa_sfq.hip) -- kind: PA_OP_DIV_QUICK, _MINMOD or _MC (the
+// limited kinds: pa_sft.hip, never with a source): blocks launched, 0 when k_sfq does not take the launch
 template <typename T>
 int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, double nu, double dt, const T* phi0 = nullptr,
-                 double c0 = 0.0, double c1 = 0.0, const pa_source* src = nullptr);   // src: the source term (pa_*_src) or null
+                 double c0 = 0.0, double c1 = 0.0, const pa_source* src = nullptr,   // src: the source term (pa_*_src) or null
+                 int kind = PA_OP_DIV_QUICK);
 // u_field == phi.p: the field advects itself -- k_sf's SELF instantiations (pa_sf_self.hip), central Div included
 template <typename T>
 int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt,

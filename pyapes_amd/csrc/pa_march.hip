@@ -26,8 +26,9 @@ template <typename T, bool VEL> struct EulerVel {};
 template <typename T> struct EulerVel<T, true> { const T* f[3]; T val[3]; int kind; };
 
 // adv = (+0) + t_0 + t_1 + t_2 over the active axes: the per-axis term of pa_apply_terms' scheme `kind` (central, QUICK,
-// upwind), operation for operation, with axis a's own speed W.f[a] / W.val[a] in the place of the one speed
-template <typename T>
+// minmod / mc, upwind), operation for operation, with axis a's own speed W.f[a] / W.val[a] in the place of the one speed
+// TVD: W.kind may be PA_OP_DIV_MINMOD / _MC (k_euler's TVD instantiations); without it that branch is not compiled
+template <typename T, bool TVD = false>
 __device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd, const EulerVel<T, true>& W, const FieldAcc<T>& acc,
                                         int64_t i, int64_t j, int64_t k, T xc) {
   int64_t g[3], N[3];
@@ -91,6 +92,17 @@ __device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd
         s = s + m;
         s = s * grd.ih[a];
         ax = ax + s;
+      } else if (TVD && (W.kind == 6 || W.kind == 7)) {   // PA_OP_DIV_MINMOD / PA_OP_DIV_MC
+        T xpp, xmm;
+        pa_nbrs2<T>(G, acc, a, i, j, k, xpp, xmm);
+        const bool per = G.bct[2 * a] == 4 || G.bct[2 * a + 1] == 4;
+        T bq, fq;
+        pa_tvd_halves<T>(xmm, xm, xc, xp, xpp, !per && g[a] <= 1, !per && g[a] >= N[a] - 2, W.kind, bq, fq);
+        T s = upl * bq;
+        T m = umi * fq;
+        s = s + m;
+        s = s * grd.ih[a];
+        ax = ax + s;
       } else {             // PA_OP_DIV_UPWIND
         T bwd = xc - xm;
         T fwd = xp - xc;
@@ -105,7 +117,9 @@ __device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd
   return ax;
 }
 
-template <typename T, bool STG = false, bool SRC = false, bool VEL = false>
+// TVD: the advection term is a slope-limited scheme, PA_OP_DIV_MINMOD / _MC (pa_device.h pa_tvd_halves) -- instantiations of
+// their own, so that the kernels of every other scheme are the code they were
+template <typename T, bool STG = false, bool SRC = false, bool VEL = false, bool TVD = false>
 __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, DevEq<T> Eadv, Vec<T> pv,
                                                      T* __restrict__ out, T nu, T dt, EulerStage<T, STG> S = {},
                                                      EulerSrc<T, SRC> Q = {}, EulerVel<T, VEL> W = {}) {
@@ -119,8 +133,8 @@ __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, De
     if (pa_in_S(G, i, j, k)) {
       T lap = pa_apply_terms<T>(G, Elap, acc, i, j, k, pc);
       T adv;
-      if constexpr (VEL) adv = pa_adv_vel<T>(G, Elap.grd, W, acc, i, j, k, pc);
-      else adv = pa_apply_terms<T>(G, Eadv, acc, i, j, k, pc);
+      if constexpr (VEL) adv = pa_adv_vel<T, TVD>(G, Elap.grd, W, acc, i, j, k, pc);
+      else adv = pa_apply_terms<T, TVD>(G, Eadv, acc, i, j, k, pc);
       T a = nu * lap;
       a = a - adv;
       if constexpr (SRC) {
@@ -225,12 +239,12 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
     pv.ghi = c->x_ghi ? (const T*)c->x_ghi : in + (c->G.n0 - 1) * c->G.s0;
   }
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);   // slot 0: the step kernel (without its BC fill)
-  // QUICK: k_sfq or the generic kernel (the tiled paths of pa_tile3d_euler do not know the kind and decline it; never with
+  // QUICK, minmod, mc: k_sfq or the generic kernel (the tiled paths of pa_tile3d_euler do not know the kind and decline it; never with
   // bcl, march_bcl_wanted)
   // a source: the SRC instantiations of k_sf / k_sfq or the generic kernel (k_cg3d's Euler phase takes none)
   const int fr = vel ? pa_tile3d_euler_vel<T>(c, pv, out, adv.kind, vel, nu, dt, phi0, stage.c0, stage.c1, src, adv.own)
-                 : adv.kind == PA_OP_DIV_QUICK
-                     ? pa_sfq_euler<T>(c, pv, out, adv.u, adv.u_field, nu, dt, phi0, stage.c0, stage.c1, src)
+                 : (adv.kind == PA_OP_DIV_QUICK || adv.kind == PA_OP_DIV_MINMOD || adv.kind == PA_OP_DIV_MC)
+                     ? pa_sfq_euler<T>(c, pv, out, adv.u, adv.u_field, nu, dt, phi0, stage.c0, stage.c1, src, adv.kind)
                      : pa_tile3d_euler<T>(c, pv, out, adv.kind, adv.u, adv.u_field, nu, dt, bcl ? 1 : 0, phi0, stage.c0, stage.c1, src);
   if (fr < 0) return fr;
   if (fr == 0 && bcl) return PA_STEP_DECLINED;
@@ -255,7 +269,8 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
     with_bool(phi0 != nullptr, [&](auto stg) {
       with_bool(src != nullptr, [&](auto sc) {
         with_bool(vel != nullptr, [&](auto vl) {
-          constexpr bool STG = decltype(stg)::value, SRC = decltype(sc)::value, VEL = decltype(vl)::value;
+         with_bool(adv.kind == PA_OP_DIV_MINMOD || adv.kind == PA_OP_DIV_MC, [&](auto tv) {
+          constexpr bool STG = decltype(stg)::value, SRC = decltype(sc)::value, VEL = decltype(vl)::value, TVD = decltype(tv)::value;
           EulerStage<T, STG> S;
           EulerSrc<T, SRC> Q;
           EulerVel<T, VEL> W;
@@ -266,8 +281,9 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
             W.kind = adv.kind;
           }
           // (with a velocity El stands in for Eadv: unread)
-          hipLaunchKernelGGL((k_euler<T, STG, SRC, VEL>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G,
+          hipLaunchKernelGGL((k_euler<T, STG, SRC, VEL, TVD>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G,
                              El, VEL ? El : Ea, pv, out, (T)nu, (T)dt, S, Q, W);
+         });
         });
       });
     });
@@ -305,7 +321,7 @@ static int march_t(T* const buf[3], int order, int64_t nsteps, int* final, Launc
   return PA_OK;
 }
 
-// (QUICK marches with a BC fill per step or stage: kind == PA_OP_DIV_UPWIND below)
+// (QUICK, minmod and mc march with a BC fill per step or stage: kind == PA_OP_DIV_UPWIND below)
 // "BC on load" (pa_sf_kernel.h): when every face has a scalar dirichlet / neumann / symmetry BC the steps of a
 // march need no fill between them -- each forms the face values it reads from its own operands, bit for bit what
 // the fill would have stored -- and ONE ordered fill after the last step completes the result.  (A source term is read on

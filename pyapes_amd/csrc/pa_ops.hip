@@ -12,7 +12,9 @@
 #include <new>
 
 // ---- y = A(x) (pyapes/solver/ops.py:122-154) -----------------------------------------
-template <typename T>
+// TVD: the term list holds PA_OP_DIV_MINMOD / _MC (pa_div alone; pa_apply_terms): an instantiation of its own, so that the
+// kernel of every other call is the code it was
+template <typename T, bool TVD = false>
 __global__ void __launch_bounds__(PA_BLOCK) k_aop(DevGeom G, DevEq<T> E, Vec<T> xv, T* __restrict__ y,
                                                    int interior_only) {
   FieldAcc<T> acc{xv};
@@ -23,7 +25,7 @@ __global__ void __launch_bounds__(PA_BLOCK) k_aop(DevGeom G, DevEq<T> E, Vec<T> 
     T out = (T)0;
     if (!interior_only || pa_in_S(G, i, j, k)) {
       T xc = xv.p[idx];
-      out = pa_apply_terms<T>(G, E, acc, i, j, k, xc);
+      out = pa_apply_terms<T, TVD>(G, E, acc, i, j, k, xc);
     }
     y[idx] = out;
   }
@@ -260,9 +262,16 @@ static int aop_t(pa_ctx* c, const T* x, T* y, int interior_only, int nterms, con
   }
   int fr = pa_tile3d_aop<T>(c, E, xv, y, interior_only);
   if (fr < 0) return fr;
-  if (fr == 0)
-    hipLaunchKernelGGL(k_aop<T>, dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, y,
-                       interior_only);
+  if (fr == 0) {
+    bool tvd = false;
+    for (int q = 0; q < nterms; ++q) tvd = tvd || terms[q].kind == PA_OP_DIV_MINMOD || terms[q].kind == PA_OP_DIV_MC;
+    if (tvd)
+      hipLaunchKernelGGL((k_aop<T, true>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, y,
+                         interior_only);
+    else
+      hipLaunchKernelGGL(k_aop<T>, dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, y,
+                         interior_only);
+  }
   PA_HIP(c, hipGetLastError());
   return PA_OK;
 }
@@ -360,8 +369,17 @@ static int grad_t(pa_ctx* c, const T* x, T* y, int edge) {
   return PA_OK;
 }
 
-// `who`: the entry point, for the messages of the QUICK checks
+// `who`: the entry point, for the messages of the checks of the schemes with a reach of 2 (QUICK, minmod, mc)
 int pa_check_div_kind(pa_ctx* c, int kind, const char* who) {
+  if (kind == PA_OP_DIV_MINMOD || kind == PA_OP_DIV_MC) {   // QUICK's rules (below), the messages name the limiter
+    const char* nm = kind == PA_OP_DIV_MINMOD ? "minmod" : "mc";
+    if (c->slab || (c->G.n0 != c->G.g0 && c->ndim == 3)) { pa_set_err(c, "%s: Div %s is single GPU only (no slabs)", who, nm); return PA_E_STATE; }
+    if (c->coord != PA_COORD_XYZ) { pa_set_err(c, "%s: Div %s is for xyz meshes (no axisymmetric rows)", who, nm); return PA_E_ARG; }
+    const int64_t n[3] = {c->G.n0, c->G.n1, c->G.n2};
+    for (int a = 0; a < 3; ++a)
+      if (c->G.act[a] && n[a] < 5) { pa_set_err(c, "%s: Div %s needs at least 5 nodes per axis (%lld)", who, nm, (long long)n[a]); return PA_E_ARG; }
+    return PA_OK;
+  }
   if (kind == PA_OP_DIV_QUICK) {
     // the reach of 2: no ghost planes at that distance, no r-dependent rows.  Neumann / symmetry faces are allowed -- the
     // fallback next to a face reads BC-filled values only
@@ -490,8 +508,10 @@ int pa_aop(pa_ctx* c, const void* x, void* y, int interior_only) {
 
 int pa_rhs_adjust(pa_ctx* c, void* rhs) {
   if (!c || !c->grid_set || !c->eq_set) { if (c) pa_set_err(c, "pa_rhs_adjust: grid/equation not set"); return PA_E_STATE; }
-  for (int q = 0; q < c->nterms; ++q)
+  for (int q = 0; q < c->nterms; ++q) {
     if (c->terms[q].kind == PA_OP_DIV_QUICK) { pa_set_err(c, "pa_rhs_adjust: Div quick is explicit-only"); return PA_E_ARG; }
+    if (c->terms[q].kind == PA_OP_DIV_MINMOD || c->terms[q].kind == PA_OP_DIV_MC) { pa_set_err(c, "pa_rhs_adjust: Div minmod / mc is explicit-only"); return PA_E_ARG; }
+  }
   PA_HIP(c, hipSetDevice(c->device));
   return c->dtype == PA_F64 ? rhs_adjust_t<double>(c, (double*)rhs) : rhs_adjust_t<float>(c, (float*)rhs);
 }

@@ -372,6 +372,7 @@ extern "C" {
 int pa_div_general(pa_ctx* c, const pa_div_spec* s, void* y) {
   if (!c || !c->grid_set || !s || !y) { if (c) pa_set_err(c, "pa_div_general: bad arguments"); return c ? PA_E_ARG : PA_E_STATE; }
   if (s->kind == PA_OP_DIV_QUICK) { pa_set_err(c, "pa_div_general: Div quick is for scalar fields without edge (pa_div)"); return PA_E_ARG; }
+  if (s->kind == PA_OP_DIV_MINMOD || s->kind == PA_OP_DIV_MC) { pa_set_err(c, "pa_div_general: Div minmod / mc is explicit-only, for scalar fields without edge (pa_div)"); return PA_E_ARG; }
   if (s->kind != PA_OP_DIV_CENTRAL && s->kind != PA_OP_DIV_UPWIND_COMPAT && s->kind != PA_OP_DIV_UPWIND) {
     pa_set_err(c, "bad div kind %d", s->kind);
     return PA_E_ARG;

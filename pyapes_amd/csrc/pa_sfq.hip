@@ -1,6 +1,7 @@
 // pa_sfq.hip -- the explicit Euler step / fused Runge-Kutta stage with the QUICK advection term on k_sfq
 // (pa_sfq_kernel.h).  A translation unit of its own: k_sf and its instantiations (pa_sf.hip, pa_sf_self.hip) are untouched.
-// step_t (pa_march.hip) asks here first for PA_OP_DIV_QUICK; 0 = not for k_sfq, the generic k_euler runs.
+// step_t (pa_march.hip) asks here first for PA_OP_DIV_QUICK and for the limited kinds PA_OP_DIV_MINMOD / _MC (their
+// instantiations: pa_sft.hip); 0 = not for k_sfq, the generic k_euler runs.
 #include "pa_sfq_kernel.h"
 
 // Rows per wave.  Four rows read (4 + 4) / 4 = 2 rows per row computed, two rows (2 + 4) / 2 = 3 -- the halo rows are the
@@ -24,8 +25,11 @@ static int launch_sfq_any(pa_ctx* c, Cg3dArgs<T>& A) {
 
 template <typename T>
 int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, double nu, double dt, const T* phi0, double c0,
-                 double c1, const pa_source* src) {
+                 double c1, const pa_source* src, int kind) {
   const DevGeom& G = c->G;
+  const bool limited = kind == PA_OP_DIV_MINMOD || kind == PA_OP_DIV_MC;
+  if (kind != PA_OP_DIV_QUICK && !limited) return 0;
+  if (limited && src) return 0;   // no SRC instantiations of the limited schemes (pa_sft.hip): the generic kernel
   if (!c->sfq || !c->sf || c->slab || c->ndim != 3 || !G.act[0] || G.n0 != G.g0 || G.off0 != 0) return 0;
   if (G.n0 < 5 || G.n1 < 5 || G.n2 < 5) return 0;
   if (G.bct[0] == PA_BC_PERIODIC || G.bct[1] == PA_BC_PERIODIC) return 0;   // the planes beyond the ends are not wrapped
@@ -37,7 +41,7 @@ int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, d
   memset(&A, 0, sizeof(A));
   fill_common<T>(c, E, A);
   fill_h<T>(c, A);
-  A.d = phi; A.out = out; A.aux = (const T*)u_field; A.u = (T)u; A.p0 = (T)nu; A.p1 = (T)dt; A.kind = PA_OP_DIV_QUICK;
+  A.d = phi; A.out = out; A.aux = (const T*)u_field; A.u = (T)u; A.p0 = (T)nu; A.p1 = (T)dt; A.kind = kind;
   A.stg_phi0 = phi0; A.stg_c0 = (T)c0; A.stg_c1 = (T)c1;
   {  // k_sfq writes the step's value at EVERY node: only where the BC fill behind it rewrites all nodes outside the interior set
     int faces = 0;
@@ -46,7 +50,9 @@ int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, d
   }
   if (!sf_applies<T, 3>(c, A, 1)) return 0;
   int n;
-  if (src) {   // the SRC instantiations (pa_sfq_src.hip): two rows per wave, whatever option "sfq" says
+  if (limited) {   // pa_sft.hip: two rows per wave, whatever option "sfq" says
+    n = pa_sft_launch<T>(c, A, kind, phi0 != nullptr);
+  } else if (src) {   // the SRC instantiations (pa_sfq_src.hip): two rows per wave, whatever option "sfq" says
     A.src = (const T*)src->field; A.src_val = (T)src->value;
     n = pa_sfq_launch_src<T>(c, A, phi0 != nullptr);
   } else {
@@ -56,5 +62,5 @@ int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, d
   return n;
 }
 
-template int pa_sfq_euler<float>(pa_ctx*, Vec<float>, float*, double, const void*, double, double, const float*, double, double, const pa_source*);
-template int pa_sfq_euler<double>(pa_ctx*, Vec<double>, double*, double, const void*, double, double, const double*, double, double, const pa_source*);
+template int pa_sfq_euler<float>(pa_ctx*, Vec<float>, float*, double, const void*, double, double, const float*, double, double, const pa_source*, int);
+template int pa_sfq_euler<double>(pa_ctx*, Vec<double>, double*, double, const void*, double, double, const double*, double, double, const pa_source*, int);

@@ -38,11 +38,24 @@
 // file and parks values in AGPRs -- ONE wave per SIMD.  The rows-per-wave rule and what was measured: pa_sfq.hip, DESIGN.md
 // section 4 "QUICK".
 // SRC: the source term, k_sf's (pa_sf_kernel.h "SRC") word for word; instantiated for two rows per wave only (pa_sfq_src.hip).
+// SCH: the scheme of the two halves, a trailing parameter whose default PA_OP_DIV_QUICK is every instantiation above.
+// PA_OP_DIV_MINMOD / PA_OP_DIV_MC (pa_sft.hip; DESIGN.md section 4 "Bounded advection") take bq / fq from pa_tvd_halves
+// (pa_device.h), component by component: the limited second-order halves, which read the same nodes i-2 .. i+2, and where
+// QUICK falls back to central they fall back to first-order upwind, bq = x - x[-1] / fq = x[+1] - x -- so x[-1] of plane 0 /
+// x[+1] of plane n0-1 are read there too (the wrap planes), and x[-2] / x[+2] beyond the ends again only feed halves the
+// fallback replaces (dmm -> sm -> bq at plane <= 1, dpp -> sp -> fq at plane >= n0-2).  Nothing else depends on SCH: plane
+// slots, halo rows, DPP moves, edge cells, the US dead half, the masks, the Laplacian half and STG are the code above.
+// Registers of the SCH instantiations (two rows per wave, same source; no private segment, no AGPRs, two waves per SIMD):
+//                    fp32 minmod   fp32 mc      fp64 minmod   fp64 mc
+//   US 1 (u >= 0)    173 (179)     171 (178)    171 (179)     173 (181)
+//   US 2 (u < 0)     173 (181)     173 (181)    171 (179)     173 (181)
+//   HASU             205 (214)     211 (220)    213 (221)     215 (223)
 #pragma once
 #include "pa_sf_kernel.h"
 
-template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false>
+template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false, int SCH = PA_OP_DIV_QUICK>
 __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
+  static_assert(SCH == PA_OP_DIV_QUICK || SCH == PA_OP_DIV_MINMOD || SCH == PA_OP_DIV_MC, "SCH: a scheme with a reach of 2");
   static_assert(US == 0 || !HASU, "US: scalar speed");
   static_assert(HASU || US != 0, "a scalar speed has a sign");
   constexpr int VEC = VecOf<T>::N;
@@ -268,11 +281,21 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
       auto axis = [&](auto FBC, const V& xp, const V& xm, const V& xpp, const V& xmm, auto lo, auto hi, T ih) {
         constexpr bool FB = decltype(FBC)::value;
         V cen = (V)(T)0;
-        if constexpr (FB) {
+        if constexpr (FB && SCH == PA_OP_DIV_QUICK) {
           cen = xp - xm;
           cen = (T)0.5 * cen;
         }
         V bq = (V)(T)0, fq = (V)(T)0;
+        if constexpr (SCH != PA_OP_DIV_QUICK) {   // the limited halves (pa_device.h), first-order upwind where QUICK is central
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) {
+            bool l = false, h = false;
+            if constexpr (FB) { l = lo(v); h = hi(v); }
+            T b = (T)0, f = (T)0;
+            pa_tvd_halves<T, BQ, FQ>(xmm[v], xm[v], xc[v], xp[v], xpp[v], l, h, SCH, b, f);
+            bq[v] = b; fq[v] = f;
+          }
+        } else {
         if constexpr (BQ) {
           V t = xp + xc;
           t = (T)0.375 * t;
@@ -297,6 +320,7 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
             for (int v = 0; v < VEC; ++v) fq[v] = hi(v) ? cen[v] : fq[v];
           }
         }
+        }   // QUICK
         V t;
         if constexpr (US == 1) {          // u >= 0: u- = +0, its half is a signed zero
           t = upl * bq;
@@ -349,18 +373,21 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
 // the SRC instantiations (two rows per wave), in pa_sfq_src.hip: A as pa_sfq_euler fills it, A.src / A.src_val set
 template <typename T>
 int pa_sfq_launch_src(pa_ctx* c, Cg3dArgs<T>& A, bool stage);
-template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false>
+// the SCH instantiations for PA_OP_DIV_MINMOD / _MC (two rows per wave, no source), in pa_sft.hip: A as pa_sfq_euler fills it
+template <typename T>
+int pa_sft_launch(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage);
+template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false, int SCH = PA_OP_DIV_QUICK>
 static int sfq_blocks_per_cu() {
   static int cached = 0;
   if (!cached) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sfq<T, RJ, HASU, US, STG, SRC>, 256, 0) != hipSuccess || n <= 0) n = 2;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sfq<T, RJ, HASU, US, STG, SRC, SCH>, 256, 0) != hipSuccess || n <= 0) n = 2;
     cached = n;
   }
   return cached;
 }
 
-template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false>
+template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false, int SCH = PA_OP_DIV_QUICK>
 static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr int VEC = VecOf<T>::N;
   constexpr int TJ = 4 * RJ, TK = 64 * VEC;
@@ -368,7 +395,7 @@ static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
   A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
   A.tiles_k = (int)((G.n2 + TK - 1) / TK);
   const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC>();
+  const int capacity = cus_of(c) * sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC, SCH>();
   int chunks = capacity / tiles;
   if (chunks < 1) chunks = 1;
   if (chunks > G.n0) chunks = (int)G.n0;
@@ -381,10 +408,10 @@ static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
   if (dbg > 0) {
     --dbg;
     fprintf(stderr, "[pyapes_hip] k_sfq phase 3 kind %d RJ %d%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            PA_OP_DIV_QUICK, RJ, HASU ? " (speed field)" : (US == 1 ? " (u >= 0)" : " (u < 0)"), STG ? " (RK stage)" : "",
+            SCH, RJ, HASU ? " (speed field)" : (US == 1 ? " (u >= 0)" : " (u < 0)"), STG ? " (RK stage)" : "",
             A.aux && (const void*)A.aux == (const void*)A.d.p ? " (self)" : "", SRC ? " (source)" : "", A.tiles_j, A.tiles_k, chunks,
-            (long long)(G.n0 / chunks), nblk, sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC>());
+            (long long)(G.n0 / chunks), nblk, sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC, SCH>());
   }
-  hipLaunchKernelGGL((k_sfq<T, RJ, HASU, US, STG, SRC>), dim3(nblk), dim3(256), 0, c->stream, A);
+  hipLaunchKernelGGL((k_sfq<T, RJ, HASU, US, STG, SRC, SCH>), dim3(nblk), dim3(256), 0, c->stream, A);
   return nblk;
 }

@@ -19,6 +19,8 @@ BC_CODE = {"dirichlet": BC_DIRICHLET, "neumann": BC_NEUMANN, "symmetry": BC_SYMM
            "periodic": BC_PERIODIC}
 OP_LAPLACIAN, OP_GRAD, OP_DIV_CENTRAL, OP_DIV_UPWIND_COMPAT, OP_DIV_UPWIND = 0, 1, 2, 3, 4
 OP_DIV_QUICK = 5   # explicit operators and marches only (include/pyapes_hip.h)
+OP_DIV_MINMOD = 6  # slope-limited (TVD) advection, minmod limiter: explicit operators and marches only
+OP_DIV_MC = 7      # the same with the monotonized-central limiter
 PA_COORD_XYZ, PA_COORD_RZ = 0, 1
 PA_OK, PA_E_ARG, PA_E_HIP, PA_E_STATE, PA_E_NONFINITE = 0, -1, -2, -3, -4
 PA_NSUM = 8

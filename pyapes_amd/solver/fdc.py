@@ -41,23 +41,32 @@ def div_kind(limiter: str, compat: bool) -> int:
         if compat:
             raise ValueError('FDC Div: limiter "quick" has no compat form (the reference has no quick scheme to reproduce)')
         return L.OP_DIV_QUICK
+    if limiter in ("minmod", "mc"):   # the slope-limited (TVD) schemes, DESIGN.md section 4 "Bounded advection"
+        if compat:
+            raise ValueError(f'FDC Div: limiter "{limiter}" has no compat form (the reference has no {limiter} scheme to reproduce)')
+        return L.OP_DIV_MINMOD if limiter == "minmod" else L.OP_DIV_MC
     raise RuntimeError(f"FDC Div: {limiter=} is an unknown limiter type.")
 
 
+# the schemes with a reach of 2 (QUICK and the slope-limited minmod / mc): explicit operators and marches only
+REACH2_NAMES = {L.OP_DIV_QUICK: "quick", L.OP_DIV_MINMOD: "minmod", L.OP_DIV_MC: "mc"}
+
+
 def quick_explicit_only(kind: int, what: str) -> None:
-    """QUICK exists as an explicit operator only: no stencil rows for a solver equation, no rhs adjustment."""
-    if kind == L.OP_DIV_QUICK:
-        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter quick is explicit-only")
+    """QUICK, minmod and mc exist as explicit operators only: no stencil rows for a solver equation, no rhs adjustment."""
+    if kind in REACH2_NAMES:
+        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter {REACH2_NAMES[kind]} is explicit-only")
 
 
 def quick_mesh_check(kind: int, mesh: Any, what: str) -> None:
-    """the meshes QUICK's reach of 2 does not cover, refused before a device is touched"""
-    if kind != L.OP_DIV_QUICK:
+    """the meshes a reach of 2 (QUICK, minmod, mc) does not cover, refused before a device is touched"""
+    if kind not in REACH2_NAMES:
         return
+    name = REACH2_NAMES[kind]
     if getattr(mesh, "slab", None) is not None:
-        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter quick on a slab mesh (single GPU only)")
+        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter {name} on a slab mesh (single GPU only)")
     if mesh.coord_sys != "xyz":
-        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter quick on a Cylinder (rz) mesh")
+        raise NotImplementedError(f"pyapes_amd: {what}: Div limiter {name} on a Cylinder (rz) mesh")
 
 
 def _adv_of(var_j: Any, var_i: Field) -> float | Tensor:
@@ -263,11 +272,11 @@ class Div(Discretizer):
         assert A_coeffs is not None, "FDC: A_A_coeffs is not defined!"
         edge = self._edge()
         kind = div_kind(A_coeffs.limiter, A_coeffs.compat)
-        if kind == L.OP_DIV_QUICK:   # a scalar field, the speed a float / Tensor / Field: the explicit operator, no edge form
+        if kind in REACH2_NAMES:   # a scalar field, the speed a float / Tensor / Field: the explicit operator, no edge form
             quick_mesh_check(kind, var.mesh, "FDC.div")
             if var.dim != 1 or edge or isinstance(A_coeffs.var_j, (Jac, Hess)):
-                raise NotImplementedError("pyapes_amd: FDC.div: limiter quick is for scalar fields with a float / Tensor / Field "
-                                          "speed and edge=False")
+                raise NotImplementedError(f"pyapes_amd: FDC.div: limiter {REACH2_NAMES[kind]} is for scalar fields with a float / "
+                                          "Tensor / Field speed and edge=False")
         require_gpu(var(), "FDC.div")
         ctx = context_for(var.mesh)
         ctx.bind_bcs(var(), A_coeffs.bcs, 0)

@@ -7,7 +7,7 @@ from torch import Tensor
 
 
 class DivConfigType(TypedDict, total=False):
-    limiter: str   # "none" | "upwind" | "quick" (quick: explicit Div of a scalar field and the marches only)
+    limiter: str   # "none" | "upwind" | "quick" | "minmod" | "mc" (the last three: explicit Div of a scalar field and the marches only)
     edge: bool
     compat: bool   # new: limiter "upwind" reproduces the reference's literal output
 
