@@ -79,6 +79,7 @@ static int jacobi_run_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_i
     if (c->terms[q].kind != PA_OP_LAPLACIAN) { pa_set_err(c, "pa_jacobi: laplacian terms only"); return PA_E_ARG; }
   if (c->slab) { pa_set_err(c, "pa_jacobi is single-GPU only"); return PA_E_ARG; }
   int rc;
+  c->jac_dir = 0;   // every solve starts with a forward sweep, whatever ran on this context before (the stop-test sum is ordered by it)
   if (try_resident<T>(c, 1, x, rhs, tol, max_it, omega, out, &rc)) return rc;
   const size_t fb = (size_t)G.ncell * sizeof(T);
   const int nblk = pa_grid_blocks(G.ncell);
@@ -217,6 +218,7 @@ int jacobi_slab_begin_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_i
   c->fold_a_n = c->fold_b_n = c->fold_b_nsh = 0;
   c->cg_pitch = 0;
   c->cg_ps1 = 0;
+  c->jac_dir = 0;   // the first sweep marches forwards: an earlier solve may have ended on an odd count of sweep launches
   // the driver has filled the BCs (it needs the far planes for that) and exchanged the ghost planes of x: only the
   // shell of the start is recorded here (x_old of the first stop test)
   if ((rc = pa_bc_fill_start<T>(c, x, true))) return rc;

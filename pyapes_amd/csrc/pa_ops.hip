@@ -406,8 +406,7 @@ int pa_check_div_kind(pa_ctx* c, int kind, const char* who) {
 // ---- vector steps of the host-stepped solver loops (pyapes_amd/solver/host_stepped.py) ------------------------------
 // out = y + a x, the product rounded before the sum (torch: y + a * x; "y - a x" is the same bits with -a)
 template <typename T>
-__global__ void __launch_bounds__(PA_BLOCK) k_vec_axpy(T* __restrict__ out, const T* __restrict__ y, T a,
-                                                        const T* __restrict__ x, int64_t n) {
+__global__ void __launch_bounds__(PA_BLOCK) k_vec_axpy(T* out, const T* y, T a, const T* x, int64_t n) {   // (out may alias y or x)
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     T t = a * x[i];
     out[i] = y[i] + t;
