@@ -1092,22 +1092,64 @@ static int cus_of(pa_ctx* c) {
   return cus;
 }
 
-template <typename T, int RJ, int PHASE, bool CF, int KIND = 0, int LAY = 0, bool STG = false>
-static int blocks_per_cu() {
-  static int cached = 0;
-  if (!cached) {
+// ---- one launch plan --------------------------------------------------------------------------
+// tiles of 4 rj rows x 64 vec cells over n1e x n2e, and the axis-0 chunks that fill `capacity` workgroups with them (at least 1)
+static inline int64_t tile_count(int64_t n1e, int64_t n2e, int rj, int vec) {
+  return ((n1e + 4 * rj - 1) / (4 * rj)) * ((n2e + 64 * vec - 1) / (64 * vec));
+}
+static inline int64_t chunk_count(int64_t capacity, int64_t tiles) { return capacity / tiles > 0 ? capacity / tiles : 1; }
+
+// One instantiation of a tiled marching kernel (k_cg3d, k_sf, k_sfq) as its launcher names it.  bpc / dbg: the instantiation's
+// OWN cached occupancy (0: not asked yet) and budget of PYAPES_HIP_DEBUG lines (-1: not read yet) -- statics of the launcher.
+struct TileKernel {
+  const void* fn;
+  int rj, vec;
+  int bpc_fallback;   // blocks / CU when the occupancy query fails
+  int* bpc;
+  int* dbg;
+  void (*label)(char* s, size_t n, const void* args);   // "k_sf phase 3 kind 5 RJ 2 (source)": called for a debug line only
+  bool with_cus;      // the line ends in " x <CUs> CUs"
+};
+
+// Everything after "which kernel, which extents": tiles, chunks = capacity / tiles clamped to [1, n0] and capped by option
+// "chunks", the refusal of more than PA_MAX_PARTIALS blocks (0), the debug line, the launch.  grid: the tiles_j, tiles_k,
+// chunks members of args.  Blocks launched -- or, under plan_only (pa_cg_fold_plan), the blocks this launch would use.
+static int launch_tiled(pa_ctx* c, const TileKernel& K, int64_t n1e, int64_t n2e, void* args, int* grid, bool may_plan_only = false) {
+  const DevGeom& G = c->G;
+  if (!*K.bpc) {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_cg3d<T, RJ, PHASE, CF, KIND, LAY, STG>, 256, 0) != hipSuccess || n <= 0) n = 2;
-    cached = n;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K.fn, 256, 0) != hipSuccess || n <= 0) n = K.bpc_fallback;
+    *K.bpc = n;
   }
-  return cached;
+  const int TJ = 4 * K.rj, TK = 64 * K.vec;
+  grid[0] = (int)((n1e + TJ - 1) / TJ);
+  grid[1] = (int)((n2e + TK - 1) / TK);
+  const int tiles = grid[0] * grid[1];
+  const int capacity = cus_of(c) * *K.bpc;
+  int chunks = capacity / tiles;
+  if (chunks < 1) chunks = 1;
+  if (chunks > G.n0) chunks = (int)G.n0;
+  if (c->chunks > 0 && chunks > c->chunks) chunks = c->chunks;   // option "chunks": a cap behind the rule (tests: chunks longer than one plane on small meshes)
+  grid[2] = chunks;
+  const int nblk = tiles * chunks;
+  if (nblk > PA_MAX_PARTIALS) return 0;
+  if (*K.dbg < 0) *K.dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
+  if (*K.dbg > 0) {
+    --*K.dbg;
+    char label[160], tail[32] = "";
+    K.label(label, sizeof(label), args);
+    if (K.with_cus) snprintf(tail, sizeof(tail), " x %d CUs", cus_of(c));
+    fprintf(stderr, "[pyapes_hip] %s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU%s\n", label, grid[0], grid[1], chunks,
+            (long long)(G.n0 / chunks), nblk, *K.bpc, tail);
+  }
+  if (may_plan_only && c->plan_only) return nblk;   // pa_cg_fold_plan: the grid this launch would use
+  void* kargs[] = {args};
+  (void)hipLaunchKernel(K.fn, dim3(nblk), dim3(256), kargs, 0, c->stream);   // (the callers ask hipGetLastError)
+  return nblk;
 }
 
 template <typename T, int RJ, int PHASE, bool CF = false, int KIND = 0, int LAY = 0, bool STG = false>
 static int launch_cg3d(pa_ctx* c, Cg3dArgs<T>& A) {
-  constexpr bool NARROW = LAY == 1;
-  constexpr int VEC = NARROW ? 1 : VecOf<T>::N;
-  constexpr int TJ = 4 * RJ, TK = 64 * VEC;
   const DevGeom& G = c->G;
   // The CG phases only ever change cells of the interior set: the last row / column of a non-periodic
   // axis is a boundary node whose d', r stay 0 and whose x is left alone, so no tile needs to cover
@@ -1120,28 +1162,12 @@ static int launch_cg3d(pa_ctx* c, Cg3dArgs<T>& A) {
     if (G.bct[3] != PA_BC_PERIODIC && n1e > 2) n1e -= 1;
     if (G.bct[5] != PA_BC_PERIODIC && n2e > 2) n2e -= 1;
   }
-  A.tiles_j = (int)((n1e + TJ - 1) / TJ);
-  A.tiles_k = (int)((n2e + TK - 1) / TK);
-  const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * blocks_per_cu<T, RJ, PHASE, CF, KIND, LAY, STG>();
-  int chunks = capacity / tiles;
-  if (chunks < 1) chunks = 1;
-  if (chunks > G.n0) chunks = (int)G.n0;
-  if (c->chunks > 0 && chunks > c->chunks) chunks = c->chunks;   // option "chunks": a cap behind the rule (tests: chunks longer than one plane on small meshes)
-  A.chunks = chunks;
-  const int nblk = tiles * chunks;
-  if (nblk > PA_MAX_PARTIALS) return 0;
-  static int dbg = -1;
-  if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
-  if (dbg > 0) {
-    --dbg;
-    fprintf(stderr, "[pyapes_hip] k_cg3d phase %c%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU x %d CUs\n",
-            (char)('A' + PHASE), LAY == 1 ? " (narrow)" : (LAY == 2 ? " (pitched)" : ""), STG ? " (RK stage)" : "", A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
-            blocks_per_cu<T, RJ, PHASE, CF, KIND, LAY, STG>(), cus_of(c));
-  }
-  if (c->plan_only) return nblk;   // pa_cg_fold_plan: the grid this launch would use
-  hipLaunchKernelGGL((k_cg3d<T, RJ, PHASE, CF, KIND, LAY, STG>), dim3(nblk), dim3(256), 0, c->stream, A);
-  return nblk;
+  static int bpc = 0, dbg = -1;
+  static const TileKernel K = {(const void*)k_cg3d<T, RJ, PHASE, CF, KIND, LAY, STG>, RJ, LAY == 1 ? 1 : VecOf<T>::N, 2, &bpc, &dbg,
+    [](char* s, size_t n, const void*) {
+      snprintf(s, n, "k_cg3d phase %c%s%s", (char)('A' + PHASE), LAY == 1 ? " (narrow)" : (LAY == 2 ? " (pitched)" : ""), STG ? " (RK stage)" : "");
+    }, true};
+  return launch_tiled(c, K, n1e, n2e, &A, &A.tiles_j, true);
 }
 
 // rows per thread.  Measured over 48^3 .. 512^3, long and flat boxes, fp64 and fp32: for
@@ -1158,13 +1184,7 @@ static int pick_rj(pa_ctx* c, bool narrow = false, bool cg_phase = false) {
   // 256 cells to cover, and the rule must see the tiles that will really be launched
   const int64_t n1e = G.n1 - ((cg_phase && G.bct[3] != PA_BC_PERIODIC && G.n1 > 2) ? 1 : 0);
   const int64_t n2e = G.n2 - ((cg_phase && G.bct[5] != PA_BC_PERIODIC && G.n2 > 2) ? 1 : 0);
-  const int64_t tk = (n2e + 64 * VEC - 1) / (64 * VEC);
-  const int cap = cus_of(c) * 2;
-  auto chunk_len = [&](int rj) {
-    const int64_t tiles = ((n1e + 4 * rj - 1) / (4 * rj)) * tk;
-    const int64_t chunks = cap / tiles > 0 ? cap / tiles : 1;
-    return G.n0 / chunks;
-  };
+  auto chunk_len = [&](int rj) { return G.n0 / chunk_count(cus_of(c) * 2, tile_count(n1e, n2e, rj, VEC)); };
   if (PHASE == 3) {
     // more rows per thread amortise the per-plane bookkeeping, and the step tolerates shorter chunks
     // (256^3 fp32: RJ 2 48 us / step, RJ 1 54); below that 2 rows stay best (fp32 64^3 12.9 vs 14.1 us,
@@ -1181,56 +1201,28 @@ static int launch_any_w(pa_ctx* c, Cg3dArgs<T>& A) {
   constexpr bool CF_OK = (PHASE == 0 || PHASE == 1 || PHASE == 2 || PHASE == 4 || PHASE == 9);
   if (A.coeff_f) {  // tensor coefficient: separate instantiation, so the scalar-coefficient kernels stay lean
     if (!CF_OK) return 0;
-    if constexpr (CF_OK) {
-      switch (pick_rj<T>(c, NARROW == 1)) {
-        case 1: return launch_cg3d<T, 1, PHASE, true, 0, NARROW>(c, A);
-        case 2: return launch_cg3d<T, 2, PHASE, true, 0, NARROW>(c, A);
-        default: return launch_cg3d<T, 4, PHASE, true, 0, NARROW>(c, A);
-      }
-    }
+    if constexpr (CF_OK)
+      return with_int<1, 2, 4>(pick_rj<T>(c, NARROW == 1), [&](auto rj) { return launch_cg3d<T, decltype(rj)::value, PHASE, true, 0, NARROW>(c, A); });
   }
   if constexpr (PHASE == 3) {  // one instantiation per Div scheme
-    const int rj = pick_rj<T, 3>(c, NARROW == 1);
-#define PA_EULER_CASE(K)                                                   \
-    case K:                                                                \
-      switch (rj) {                                                        \
-        case 1: return launch_cg3d<T, 1, 3, false, K, NARROW, STG>(c, A);  \
-        case 2: return launch_cg3d<T, 2, 3, false, K, NARROW, STG>(c, A);  \
-        default: return launch_cg3d<T, 4, 3, false, K, NARROW, STG>(c, A); \
-      }
-    switch (A.kind) {
-      PA_EULER_CASE(PA_OP_DIV_CENTRAL)
-      PA_EULER_CASE(PA_OP_DIV_UPWIND_COMPAT)
-      PA_EULER_CASE(PA_OP_DIV_UPWIND)
-      default: return 0;
-    }
-#undef PA_EULER_CASE
+    const int rows = pick_rj<T, 3>(c, NARROW == 1);
+    return with_int<PA_OP_DIV_CENTRAL, PA_OP_DIV_UPWIND_COMPAT, PA_OP_DIV_UPWIND>(A.kind, [&](auto kind) {
+      return with_int<1, 2, 4>(rows, [&](auto rj) { return launch_cg3d<T, decltype(rj)::value, 3, false, decltype(kind)::value, NARROW, STG>(c, A); });
+    });
   }
   if constexpr (PHASE == 2 || PHASE == 5 || PHASE == 6 || PHASE == 8) {
     if (A.kind != 0) {  // Laplacian + Div(scalar u): one instantiation per scheme, two or four rows per thread
-      const bool four = pick_rj<T>(c, NARROW == 1) == 4;
-#define PA_DIV_CASE(K)                                                                   \
-      case K:                                                                            \
-        return four ? launch_cg3d<T, 4, PHASE, false, K, NARROW>(c, A)                   \
-                    : launch_cg3d<T, 2, PHASE, false, K, NARROW>(c, A);
-      switch (A.kind) {
-        PA_DIV_CASE(PA_OP_DIV_CENTRAL)
-        PA_DIV_CASE(PA_OP_DIV_UPWIND_COMPAT)
-        PA_DIV_CASE(PA_OP_DIV_UPWIND)
-        default: return 0;
-      }
-#undef PA_DIV_CASE
+      const int rows = pick_rj<T>(c, NARROW == 1) == 4 ? 4 : 2;
+      return with_int<PA_OP_DIV_CENTRAL, PA_OP_DIV_UPWIND_COMPAT, PA_OP_DIV_UPWIND>(A.kind, [&](auto kind) {
+        return with_int<2, 4>(rows, [&](auto rj) { return launch_cg3d<T, decltype(rj)::value, PHASE, false, decltype(kind)::value, NARROW>(c, A); });
+      });
     }
   }
-  const int rj = pick_rj<T>(c, NARROW == 1, PHASE == 0 || PHASE == 1 || PHASE == 5 || PHASE == 6 || PHASE == 8);
+  const int rows = pick_rj<T>(c, NARROW == 1, PHASE == 0 || PHASE == 1 || PHASE == 5 || PHASE == 6 || PHASE == 8);
   // (Round 4 tried 32-row tiles, RJ = 8, for the fp64 CG phases at 512^3 -- half the halo rows per cell, against phase
   // A's +5.7 % of re-read halo rows: 370 / 411 VGPRs instead of 223 / 237, i.e. ONE wave per SIMD, and phase A went from
   // 0.59 to 0.69 ms while phase B stayed at 0.92-0.94 (three interleaved pairs on one box).  The instantiation is gone.)
-  switch (rj) {
-    case 1: return launch_cg3d<T, 1, PHASE, false, 0, NARROW>(c, A);
-    case 2: return launch_cg3d<T, 2, PHASE, false, 0, NARROW>(c, A);
-    default: return launch_cg3d<T, 4, PHASE, false, 0, NARROW>(c, A);
-  }
+  return with_int<1, 2, 4>(rows, [&](auto rj) { return launch_cg3d<T, decltype(rj)::value, PHASE, false, 0, NARROW>(c, A); });
 }
 
 // the CG phases in the PITCH layout (a plain Laplacian only: the other instantiations do not exist)
@@ -1238,11 +1230,7 @@ template <typename T, int PHASE>
 static int launch_pitched(pa_ctx* c, Cg3dArgs<T>& A) {
   static_assert(PHASE == 0 || PHASE == 1 || PHASE == 5 || PHASE == 6 || PHASE == 8, "PITCH: CG / BiCGSTAB phases");
   if (A.coeff_f || A.kind != 0) return 0;
-  switch (pick_rj<T>(c, false, true)) {
-    case 1: return launch_cg3d<T, 1, PHASE, false, 0, 2>(c, A);
-    case 2: return launch_cg3d<T, 2, PHASE, false, 0, 2>(c, A);
-    default: return launch_cg3d<T, 4, PHASE, false, 0, 2>(c, A);
-  }
+  return with_int<1, 2, 4>(pick_rj<T>(c, false, true), [&](auto rj) { return launch_cg3d<T, decltype(rj)::value, PHASE, false, 0, 2>(c, A); });
 }
 
 template <typename T, int PHASE, bool STG = false>

@@ -4,6 +4,8 @@
 #include <stdarg.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/pyapes_hip.h"
 #include "pa_device.h"
 
@@ -270,6 +272,21 @@ int pa_bc_fill_start(pa_ctx* c, T* x, bool filled_by_driver);
 template <typename T>
 int pa_bc_fill_step(pa_ctx* c, T* x, double* part2, int* nsh);
 
+// f(std::bool_constant<b>): a run-time fact as a template argument
+template <typename F>
+static auto with_bool(bool b, F&& f) {
+  if (b) return f(std::true_type{});
+  return f(std::false_type{});
+}
+// f(std::integral_constant<int, v>) for the one of the STATED values that v equals, else 0: the list names the instantiations
+// that exist (rows per wave 1 / 2 / 4 or 2 / 4, the Div kinds of a kernel) -- nothing outside it is compiled
+template <int... VALS, typename F>
+static int with_int(int v, F&& f) {
+  int n = 0;
+  (void)(... || (v == VALS ? (n = f(std::integral_constant<int, VALS>{}), true) : false));
+  return n;
+}
+
 #define PA_HIP(c, call)                                              \
   do {                                                               \
     hipError_t e__ = (call);                                         \
@@ -317,24 +334,37 @@ template <typename T>
 int pa_tile3d_aop(pa_ctx* c, const DevEq<T>& E, Vec<T> x, T* y, int interior_only);
 template <typename T>
 int pa_tile3d_grad(pa_ctx* c, Vec<T> x, T* y, int nd);
-// the Euler step / stage of the schemes with a reach of 2 on k_sfq (pa_sfq.hip) -- kind: PA_OP_DIV_QUICK, _MINMOD or _MC (the
-// limited kinds: pa_sft.hip, never with a source): blocks launched, 0 when k_sfq does not take the launch
+// The advection of a step.  vel null: ONE speed for every axis, u or the field u_field (u_field == the step's input: the
+// field advects itself).  vel non-null (pa_*_vel): a velocity indexed by INTERNAL axis; own >= 0 (pa_momentum_march):
+// vel->field[own] is the step's input itself -- the target is a component of the velocity.  Nothing on the way needs the
+// speed fields to be distinct from the field read through the stencil: cg3d_mode ORs the pointers for their alignment,
+// sf_applies does not look at them, and the kernels read every operand through plain (non-restrict) global loads; `out`
+// alone is written, and it is a buffer of its own.
+struct StepAdv {
+  int kind;
+  double u;
+  const void* u_field;
+  const pa_velocity* vel;
+  int own;
+};
+// phi0 != null: the Runge-Kutta stage out = B( c0 phi0 + c1 E(in) ) (pa_rk_stage); null: the plain Euler step
 template <typename T>
-int pa_sfq_euler(pa_ctx* c, Vec<T> phi, T* out, double u, const void* u_field, double nu, double dt, const T* phi0 = nullptr,
-                 double c0 = 0.0, double c1 = 0.0, const pa_source* src = nullptr,   // src: the source term (pa_*_src) or null
-                 int kind = PA_OP_DIV_QUICK);
-// u_field == phi.p: the field advects itself -- k_sf's SELF instantiations (pa_sf_self.hip), central Div included
+struct StepStage { const T* phi0; double c0, c1; };
+// one Euler step / stage as step_t (pa_march.hip) asks the tiled layer for it.  src: the source term (pa_*_src) or null;
+// bcl: the "BC on load" form (pa_sf_kernel.h)
 template <typename T>
-int pa_tile3d_euler(pa_ctx* c, Vec<T> phi, T* out, int kind, double u, const void* u_field, double nu, double dt,
-                    int bcl = 0,    // bcl: "BC on load" (pa_sf_kernel.h); 0 is returned when that form does not apply
-                    const T* phi0 = nullptr, double c0 = 0.0, double c1 = 0.0,    // phi0: the stage c0 phi0 + c1 E(phi) of pa_rk_stage
-                    const pa_source* src = nullptr);   // src: the source term (pa_*_src) or null; k_sf's SRC instantiations or 0
-// the upwind Euler step / stage with a velocity (pa_*_vel; vel indexed by INTERNAL axis) on k_sf's VEL instantiations
-// (pa_sf_vel.hip): blocks launched, 0 when k_sf does not take the launch (the generic k_euler then runs).  own >= 0
-// (pa_momentum_march): vel->field[own] IS phi.p -- the VEL 3 instantiations (pa_sf_vself.hip) unless option "vself" is 0
+struct StepRequest {
+  StepAdv adv;
+  double nu, dt;
+  StepStage<T> stage;
+  const pa_source* src;
+  bool bcl;
+};
+// The step on a tiled kernel (pa_sf.hip): k_sfq for the kinds with a reach of 2 (QUICK, minmod, mc), k_sf with a velocity,
+// else k_sf or k_cg3d's Euler phase.  Blocks launched; 0 when no tiled kernel takes the launch (the generic k_euler then
+// runs; with bcl: that form does not apply); < 0: error.
 template <typename T>
-int pa_tile3d_euler_vel(pa_ctx* c, Vec<T> phi, T* out, int kind, const pa_velocity* vel, double nu, double dt, const T* phi0,
-                        double c0, double c1, const pa_source* src, int own = -1);
+int pa_tile3d_step(pa_ctx* c, Vec<T> phi, T* out, const StepRequest<T>& rq);
 template <typename T>
 int pa_tile3d_jacobi(pa_ctx* c, const DevEq<T>& E, Vec<T> x, const T* rhs, T* xnew, double omega, double* partials);
 template <typename T>

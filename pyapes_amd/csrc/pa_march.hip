@@ -164,23 +164,6 @@ __global__ void __launch_bounds__(PA_BLOCK) k_rk_combine(T* __restrict__ x, cons
 }
 
 // ---- one step routine ---------------------------------------------------------------------------
-// The advection of a step.  vel null: ONE speed for every axis, u or the field u_field (u_field == the step's input: the
-// field advects itself).  vel non-null (pa_*_vel): a velocity indexed by INTERNAL axis; own >= 0 (pa_momentum_march):
-// vel->field[own] is the step's input itself -- the target is a component of the velocity.  Nothing on the way needs the
-// speed fields to be distinct from the field read through the stencil: cg3d_mode ORs the pointers for their alignment,
-// sf_applies does not look at them, and the kernels read every operand through plain (non-restrict) global loads; `out`
-// alone is written, and it is a buffer of its own.
-struct StepAdv {
-  int kind;
-  double u;
-  const void* u_field;
-  const pa_velocity* vel;
-  int own;
-};
-// phi0 != null: the Runge-Kutta stage out = B( c0 phi0 + c1 E(in) ) (pa_rk_stage); null: the plain Euler step
-template <typename T>
-struct StepStage { const T* phi0; double c0, c1; };
-
 // what step_t answers, besides PA_OK and an error, when the BC-on-load form was asked for and does not apply: nothing was launched
 #define PA_STEP_DECLINED 1
 
@@ -192,15 +175,8 @@ static bool step_dbg(int* left, int budget) {
   return true;
 }
 
-// f(std::bool_constant<b>): a run-time fact as a template argument
-template <typename F>
-static void with_bool(bool b, F&& f) {
-  if (b) f(std::true_type{});
-  else f(std::false_type{});
-}
-
-// The Euler step or the fused stage, in -> out, on the path that takes it: k_sfq (QUICK), k_sf / k_cg3d (pa_tile3d_euler, with a
-// velocity pa_tile3d_euler_vel), else the generic k_euler; then the ordered BC fill.  bcl: the "BC on load" form of a march
+// The Euler step or the fused stage, in -> out, on the path that takes it: a tiled kernel (pa_tile3d_step: k_sfq, k_sf, k_cg3d),
+// else the generic k_euler; then the ordered BC fill.  bcl: the "BC on load" form of a march
 // (pa_sf_kernel.h) -- the step kernel alone, no fill behind it, the boundary nodes of `out` stay whatever they were; the answer is
 // PA_STEP_DECLINED when that form does not apply here.
 template <typename T>
@@ -239,13 +215,9 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
     pv.ghi = c->x_ghi ? (const T*)c->x_ghi : in + (c->G.n0 - 1) * c->G.s0;
   }
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);   // slot 0: the step kernel (without its BC fill)
-  // QUICK, minmod, mc: k_sfq or the generic kernel (the tiled paths of pa_tile3d_euler do not know the kind and decline it; never with
-  // bcl, march_bcl_wanted)
-  // a source: the SRC instantiations of k_sf / k_sfq or the generic kernel (k_cg3d's Euler phase takes none)
-  const int fr = vel ? pa_tile3d_euler_vel<T>(c, pv, out, adv.kind, vel, nu, dt, phi0, stage.c0, stage.c1, src, adv.own)
-                 : (adv.kind == PA_OP_DIV_QUICK || adv.kind == PA_OP_DIV_MINMOD || adv.kind == PA_OP_DIV_MC)
-                     ? pa_sfq_euler<T>(c, pv, out, adv.u, adv.u_field, nu, dt, phi0, stage.c0, stage.c1, src, adv.kind)
-                     : pa_tile3d_euler<T>(c, pv, out, adv.kind, adv.u, adv.u_field, nu, dt, bcl ? 1 : 0, phi0, stage.c0, stage.c1, src);
+  // the tiled layer first: k_sfq (QUICK, minmod, mc), k_sf, k_cg3d's Euler phase; 0: none of them takes the launch
+  // (a source: the SRC instantiations of k_sf / k_sfq or the generic kernel -- k_cg3d's Euler phase takes none)
+  const int fr = pa_tile3d_step<T>(c, pv, out, StepRequest<T>{adv, nu, dt, stage, src, bcl});
   if (fr < 0) return fr;
   if (fr == 0 && bcl) return PA_STEP_DECLINED;
   if (fr == 0) {

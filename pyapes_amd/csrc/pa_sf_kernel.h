@@ -513,7 +513,7 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
           mm = cMkV * xmk;
           s = s + mm;
           axv = axv + s;
-          if (PHASE != 3) {   // the Euler step's Laplacian: no coefficient, sign +1 (pa_tile3d_euler); x * 1 is x
+          if (PHASE != 3) {   // the Euler step's Laplacian: no coefficient, sign +1 (pa_tile3d_step); x * 1 is x
             axv = axv * cf;
             axv = axv * sgn;
           }
@@ -665,42 +665,15 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 
 // ---- host side ---------------------------------------------------------------------------------------
 template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false, int VEL = 0>
-static int sf_blocks_per_cu() {
-  static int cached = 0;
-  if (!cached) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>, 256, 0) != hipSuccess || n <= 0) n = 4;
-    cached = n;
-  }
-  return cached;
-}
-
-template <typename T, int RJ, int PHASE, int KIND, bool HASU, bool BCL = false, int US = 0, bool STG = false, bool SELF = false, bool SRC = false, int VEL = 0>
 static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
-  constexpr int VEC = VecOf<T>::N;
-  constexpr int TJ = 4 * RJ, TK = 64 * VEC;
-  const DevGeom& G = c->G;
-  A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
-  A.tiles_k = (int)((G.n2 + TK - 1) / TK);
-  const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>();
-  int chunks = capacity / tiles;
-  if (chunks < 1) chunks = 1;
-  if (chunks > G.n0) chunks = (int)G.n0;
-  if (c->chunks > 0 && chunks > c->chunks) chunks = c->chunks;   // option "chunks": a cap behind the rule (tests: chunks longer than one plane on small meshes)
-  A.chunks = chunks;
-  const int nblk = tiles * chunks;
-  if (nblk > PA_MAX_PARTIALS) return 0;
-  static int dbg = -1;
-  if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
-  if (dbg > 0) {
-    --dbg;
-    fprintf(stderr, "[pyapes_hip] k_sf phase %d kind %d RJ %d%s%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", SRC ? " (source)" : "", VEL == 3 ? (A.vel_own == 0 ? " (velocity, own 0)" : (A.vel_own == 1 ? " (velocity, own 1)" : " (velocity, own 2)")) : (VEL ? " (velocity)" : ""), A.tiles_j, A.tiles_k, chunks, (long long)(G.n0 / chunks), nblk,
-            sf_blocks_per_cu<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>());
-  }
-  hipLaunchKernelGGL((k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>), dim3(nblk), dim3(256), 0, c->stream, A);
-  return nblk;
+  static int bpc = 0, dbg = -1;
+  static const TileKernel K = {(const void*)k_sf<T, RJ, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>, RJ, VecOf<T>::N, 4, &bpc, &dbg,
+    [](char* s, size_t n, const void* args) {
+      const int own = ((const Cg3dArgs<T>*)args)->vel_own;
+      snprintf(s, n, "k_sf phase %d kind %d RJ %d%s%s%s%s%s", PHASE, KIND, RJ, BCL ? " (BC on load)" : "", STG ? " (RK stage)" : "", SELF ? " (self)" : "", SRC ? " (source)" : "",
+               VEL == 3 ? (own == 0 ? " (velocity, own 0)" : (own == 1 ? " (velocity, own 1)" : " (velocity, own 2)")) : (VEL ? " (velocity)" : ""));
+    }, false};
+  return launch_tiled(c, K, c->G.n1, c->G.n2, &A, &A.tiles_j);
 }
 
 // Rows per wave (measured, MI355X, us per launch of the upwind Div at 1 / 2 / 4 rows; k_cg3d for comparison):
@@ -710,98 +683,91 @@ static int launch_sf(pa_ctx* c, Cg3dArgs<T>& A) {
 // marches >= 32 planes, else two (the three planes of prologue weigh less on short chunks).
 template <typename T>
 static int sf_rows_per_wave(pa_ctx* c) {
-  constexpr int VEC = VecOf<T>::N;
   const DevGeom& G = c->G;
   if (G.n1 <= 4) return 1;
   if (G.n1 <= 8) return 2;
   if (c->sf == 2 || c->sf == 4) return c->sf;   // option "sf" 2 / 4: forced (tests)
-  const int64_t tiles4 = ((G.n1 + 15) / 16) * ((G.n2 + 64 * VEC - 1) / (64 * VEC));
-  const int64_t chunks4 = std::max<int64_t>(1, (int64_t)cus_of(c) * 2 / tiles4);
-  return G.n0 / chunks4 >= 32 ? 4 : 2;
+  return G.n0 / chunk_count(cus_of(c) * 2, tile_count(G.n1, G.n2, 4, VecOf<T>::N)) >= 32 ? 4 : 2;
 }
 
-template <typename T, int PHASE, int KIND, bool STG = false>
-static int launch_sf_any(pa_ctx* c, Cg3dArgs<T>& A) {
-  const int rj = sf_rows_per_wave<T>(c);
-  if constexpr (PHASE == 3 && KIND == PA_OP_DIV_UPWIND) {   // BC on load: the upwind march (BASELINE config 4)
-    if (A.bcl_type[0] | A.bcl_type[1] | A.bcl_type[2] | A.bcl_type[3] | A.bcl_type[4] | A.bcl_type[5]) {
-      if (rj < 2 || (c->G.n1 - 1) % rj == 0) return 0;   // PATCH: rows n1 - 2, n1 - 1 in one wave's block
-      if (A.aux) return rj == 2 ? launch_sf<T, 2, 3, KIND, true, true, 0, STG>(c, A) : launch_sf<T, 4, 3, KIND, true, true, 0, STG>(c, A);
-      if (PA_SF_USIGN) {   // scalar speed: its sign is a launch-time fact (US, above)
-        if (A.u < (T)0) return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 2, STG>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 2, STG>(c, A);
-        return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 1, STG>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 1, STG>(c, A);
-      }
-      return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 0, STG>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 0, STG>(c, A);
-    }
+// ---- one variant record -------------------------------------------------------------------------------
+// The run-time values of the template parameters of k_sf / k_sfq for one launch.  sf_variant alone decides them; every
+// translation unit that holds instantiations exports one function that maps the record onto the ones it holds and answers 0
+// for any other.  rows 0: no instantiation takes the launch.
+struct SfVariant {
+  int kind;   // KIND of k_sf, SCH of k_sfq
+  int rows;   // RJ
+  int us;     // US: the sign of a scalar speed as a launch-time fact (1: u >= 0, 2: u < 0; 0: not used)
+  int vel;    // VEL
+  bool hasu, bcl, stg, self, src;
+};
+
+// A as the caller filled it (kind, aux / u, bcl_type, stg_phi0, vel_f / vel_own).  src: the step has a source term;
+// self: the field advects itself (aux == the field); velocity: vel_f / vel_v hold one speed per axis.
+template <typename T>
+static SfVariant sf_variant(pa_ctx* c, Cg3dArgs<T>& A, bool src = false, bool self = false, bool velocity = false) {
+  SfVariant V = {};
+  V.kind = A.kind;
+  V.stg = A.stg_phi0 != nullptr;
+  V.src = src;
+  if (A.kind == PA_OP_DIV_QUICK || A.kind == PA_OP_DIV_MINMOD || A.kind == PA_OP_DIV_MC) {   // k_sfq
+    // Rows per wave.  Four rows read (4 + 4) / 4 = 2 rows per row computed, two rows (2 + 4) / 2 = 3 -- the halo rows are the
+    // neighbour waves' own rows, cache hits.  But the four-row instantiations do not fit the 256-VGPR file (pa_sfq_kernel.h:
+    // 256 + 8 .. 88 AGPRs, ONE wave per SIMD, hundreds of v_accvgpr moves in the plane loop) where the two-row ones keep two
+    // waves per SIMD at 169 - 221 VGPRs: two rows everywhere.  The four-row kernels of plain QUICK stay reachable through
+    // option "sfq" = 4 for the A/B rows of bench_ops.py --sections quick (DESIGN.md section 4 "QUICK"); with a source and for
+    // the limited schemes there are none.  An axis has at least 5 nodes here, so there is no one-row form.
+    V.rows = (c->sfq == 4 && A.kind == PA_OP_DIV_QUICK && !src) ? 4 : 2;
+    V.hasu = A.aux != nullptr;   // (a field that advects itself is a speed field like any other here)
+    V.us = V.hasu ? 0 : (A.u < (T)0 ? 2 : 1);
+    return V;
   }
-  if constexpr (KIND == PA_OP_DIV_UPWIND) {
-    if (PA_SF_USIGN && !A.aux) {
-      if (A.u < (T)0) {
-        switch (rj) {
-          case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 2, STG>(c, A);
-          case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 2, STG>(c, A);
-          default: return launch_sf<T, 4, PHASE, KIND, false, false, 2, STG>(c, A);
-        }
-      }
-      switch (rj) {
-        case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 1, STG>(c, A);
-        case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 1, STG>(c, A);
-        default: return launch_sf<T, 4, PHASE, KIND, false, false, 1, STG>(c, A);
-      }
-    }
+  if (velocity) {   // upwind, two rows per wave only
+    V.rows = 2;
+    // the target is itself the speed field of axis vel_own (pa_momentum_march): VEL 3 reads two speed fields instead of
+    // three, the same bits as VEL 2 on the aliased operand (option "vself" 0)
+    const int own = A.vel_own;
+    V.vel = !A.vel_f[0] ? 1 : ((own >= 0 && own < 3 && c->vself && A.vel_f[own] == A.d.p) ? 3 : 2);
+    return V;
   }
-  constexpr bool CAN_U = (PHASE == 3 || (PHASE == 2 && KIND != 0));
-  if constexpr (CAN_U) {
-    if (A.aux) {
-      switch (rj) {
-        case 1: return launch_sf<T, 1, PHASE, KIND, true, false, 0, STG>(c, A);
-        case 2: return launch_sf<T, 2, PHASE, KIND, true, false, 0, STG>(c, A);
-        default: return launch_sf<T, 4, PHASE, KIND, true, false, 0, STG>(c, A);
-      }
-    }
-  }
-  switch (rj) {
-    case 1: return launch_sf<T, 1, PHASE, KIND, false, false, 0, STG>(c, A);
-    case 2: return launch_sf<T, 2, PHASE, KIND, false, false, 0, STG>(c, A);
-    default: return launch_sf<T, 4, PHASE, KIND, false, false, 0, STG>(c, A);
-  }
+  V.self = self;
+  if (self) A.aux = nullptr;   // the speed is the stencil's own operands: nothing is loaded through aux
+  V.hasu = A.aux != nullptr;
+  // a scalar speed of the upwind form: its sign selects the half of the stencil that is read at all
+  if (PA_SF_USIGN && A.kind == PA_OP_DIV_UPWIND && !V.hasu && !self) V.us = A.u < (T)0 ? 2 : 1;
+  V.rows = sf_rows_per_wave<T>(c);
+  V.bcl = (A.bcl_type[0] | A.bcl_type[1] | A.bcl_type[2] | A.bcl_type[3] | A.bcl_type[4] | A.bcl_type[5]) != 0;
+  // BC on load patches rows n1 - 2, n1 - 1 inside one wave's block: no one-row form, and none where n1 - 1 starts a block
+  if (V.bcl && (V.rows < 2 || (c->G.n1 - 1) % V.rows == 0)) V.rows = 0;
+  return V;
 }
 
-// The Euler step / stage of a field that advects itself (SELF), rows per wave and the BC-on-load condition as above.  The
-// instantiations live in a translation unit of their own (pa_sf_self.hip), behind pa_sf_euler_self.
-template <typename T, int KIND, bool STG>
-static int launch_sf_self(pa_ctx* c, Cg3dArgs<T>& A) {
-  const int rj = sf_rows_per_wave<T>(c);
-  if constexpr (KIND == PA_OP_DIV_UPWIND) {
-    if (A.bcl_type[0] | A.bcl_type[1] | A.bcl_type[2] | A.bcl_type[3] | A.bcl_type[4] | A.bcl_type[5]) {
-      if (rj < 2 || (c->G.n1 - 1) % rj == 0) return 0;   // PATCH: rows n1 - 2, n1 - 1 in one wave's block
-      return rj == 2 ? launch_sf<T, 2, 3, KIND, false, true, 0, STG, true>(c, A) : launch_sf<T, 4, 3, KIND, false, true, 0, STG, true>(c, A);
-    }
-  }
-  switch (rj) {
-    case 1: return launch_sf<T, 1, 3, KIND, false, false, 0, STG, true>(c, A);
-    case 2: return launch_sf<T, 2, 3, KIND, false, false, 0, STG, true>(c, A);
-    default: return launch_sf<T, 4, 3, KIND, false, false, 0, STG, true>(c, A);
-  }
+// V's instantiation of k_sf with one of the STATED row counts, launched; 0 for any other row count
+template <typename T, int PHASE, int KIND, bool HASU, bool BCL, int US, bool STG, bool SELF, bool SRC, int VEL, int... ROWS>
+static int launch_sf_rows(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V) {
+  return with_int<ROWS...>(V.rows, [&](auto rj) { return launch_sf<T, decltype(rj)::value, PHASE, KIND, HASU, BCL, US, STG, SELF, SRC, VEL>(c, A); });
 }
-// blocks launched, or 0 when k_sf does not take the launch (A as pa_tile3d_euler fills it; aux is not read)
-template <typename T>
-int pa_sf_euler_self(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage);
-// The Euler step / stage with a source term (SRC; A.src / A.src_val set): upwind with a scalar speed (US 1 / 2), a speed
-// field or SELF, central with a scalar speed or SELF.  Translation units of their own: pa_sf_src.hip, and pa_sf_src_bcl.hip
-// for the BC-on-load instantiations (rj 2 / 4, the condition of launch_sf_any checked by the caller).
-template <typename T>
-int pa_sf_euler_src(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage, bool self);
-template <typename T>
-int pa_sf_euler_src_bcl(pa_ctx* c, Cg3dArgs<T>& A, int rj, bool stage, bool self);
 
-// The upwind Euler step / stage with a velocity (VEL 1: three scalar speeds A.vel_v, VEL 2: three speed fields A.vel_f), two
-// rows per wave, with and without STG and SRC.  A translation unit of its own: pa_sf_vel.hip.
+// The units and what they hold -- (c, A, V) -> blocks launched, or 0 when the unit does not hold V's instantiation:
+template <typename T> int pa_sf_launch(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);           // pa_sf.hip: the three Div schemes, plain
+template <typename T> int pa_sf_launch_self(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);      // pa_sf_self.hip: SELF
+template <typename T> int pa_sf_launch_src(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);       // pa_sf_src.hip: SRC
+template <typename T> int pa_sf_launch_src_bcl(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);   // pa_sf_src_bcl.hip: SRC, BC on load
+template <typename T> int pa_sf_launch_vel(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);       // pa_sf_vel.hip: VEL 1 / 2
+template <typename T> int pa_sf_launch_vself(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);     // pa_sf_vself.hip: VEL 3
+template <typename T> int pa_sfq_launch(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);          // pa_sfq.hip: QUICK
+template <typename T> int pa_sfq_launch_src(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);      // pa_sfq_src.hip: QUICK, SRC
+template <typename T> int pa_sft_launch(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);          // pa_sft.hip: minmod, mc
+
+// the unit that holds V's instantiation, asked
 template <typename T>
-int pa_sf_euler_vel(pa_ctx* c, Cg3dArgs<T>& A, bool stage, bool fields, bool source);
-// VEL 3: the target is the speed field of internal axis A.vel_own (pa_momentum_march).  Its own unit: pa_sf_vself.hip.
-template <typename T>
-int pa_sf_euler_vself(pa_ctx* c, Cg3dArgs<T>& A, bool stage, bool source);
+static int sf_launch_variant(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V) {
+  if (V.kind == PA_OP_DIV_MINMOD || V.kind == PA_OP_DIV_MC) return pa_sft_launch<T>(c, A, V);
+  if (V.kind == PA_OP_DIV_QUICK) return V.src ? pa_sfq_launch_src<T>(c, A, V) : pa_sfq_launch<T>(c, A, V);
+  if (V.vel) return V.vel == 3 ? pa_sf_launch_vself<T>(c, A, V) : pa_sf_launch_vel<T>(c, A, V);
+  if (V.src) return V.bcl ? pa_sf_launch_src_bcl<T>(c, A, V) : pa_sf_launch_src<T>(c, A, V);
+  return V.self ? pa_sf_launch_self<T>(c, A, V) : pa_sf_launch<T>(c, A, V);
+}
 
 // can k_sf take this launch?  Full 16-byte vectors only (mode 1 of cg3d_mode), scalar coefficient.
 template <typename T, int PHASE>

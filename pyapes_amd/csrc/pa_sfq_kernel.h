@@ -19,7 +19,7 @@
 //   * fallback masks: per plane (uniform; the planes 0, 1, n0-2, n0-1 take the second copy of the body, like k_sf's planes
 //     beside an axis-0 face), per row (uniform) and per lane component -- formed once in front of the loop.
 //   * the planes -1 / -2 and n0 / n0+1 (clamped to the wrap planes glo / ghi): axis 0 is never periodic here
-//     (pa_sfq_euler declines), so x[-2] at plane <= 1 and x[+2] at plane >= n0-2 only feed halves the fallback replaces;
+//     (pa_tile3d_step declines), so x[-2] at plane <= 1 and x[+2] at plane >= n0-2 only feed halves the fallback replaces;
 //     x[-1] of plane 0 / x[+1] of plane n0-1 ARE read by the central fallback -- the wrap planes, as the generic kernel.
 // US: sign of a SCALAR speed, known at launch -- 1: u >= 0 (bq only: planes i-2 .. i+1, rows j-2 .. j+1), 2: u < 0 (fq
 // only).  The dead half is a signed zero that the accumulation absorbs: k_sf's argument (pa_sf_kernel.h "US") word for word,
@@ -370,48 +370,28 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
 }
 
 // ---- host side ---------------------------------------------------------------------------------------
-// the SRC instantiations (two rows per wave), in pa_sfq_src.hip: A as pa_sfq_euler fills it, A.src / A.src_val set
-template <typename T>
-int pa_sfq_launch_src(pa_ctx* c, Cg3dArgs<T>& A, bool stage);
-// the SCH instantiations for PA_OP_DIV_MINMOD / _MC (two rows per wave, no source), in pa_sft.hip: A as pa_sfq_euler fills it
-template <typename T>
-int pa_sft_launch(pa_ctx* c, Cg3dArgs<T>& A, int kind, bool stage);
-template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false, int SCH = PA_OP_DIV_QUICK>
-static int sfq_blocks_per_cu() {
-  static int cached = 0;
-  if (!cached) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_sfq<T, RJ, HASU, US, STG, SRC, SCH>, 256, 0) != hipSuccess || n <= 0) n = 2;
-    cached = n;
-  }
-  return cached;
-}
-
 template <typename T, int RJ, bool HASU, int US, bool STG, bool SRC = false, int SCH = PA_OP_DIV_QUICK>
 static int launch_sfq(pa_ctx* c, Cg3dArgs<T>& A) {
-  constexpr int VEC = VecOf<T>::N;
-  constexpr int TJ = 4 * RJ, TK = 64 * VEC;
-  const DevGeom& G = c->G;
-  A.tiles_j = (int)((G.n1 + TJ - 1) / TJ);
-  A.tiles_k = (int)((G.n2 + TK - 1) / TK);
-  const int tiles = A.tiles_j * A.tiles_k;
-  const int capacity = cus_of(c) * sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC, SCH>();
-  int chunks = capacity / tiles;
-  if (chunks < 1) chunks = 1;
-  if (chunks > G.n0) chunks = (int)G.n0;
-  if (c->chunks > 0 && chunks > c->chunks) chunks = c->chunks;   // option "chunks": a cap behind the rule (tests: chunks longer than one plane on small meshes)
-  A.chunks = chunks;
-  const int nblk = tiles * chunks;
-  if (nblk > PA_MAX_PARTIALS) return 0;
-  static int dbg = -1;
-  if (dbg < 0) dbg = getenv("PYAPES_HIP_DEBUG") ? 8 : 0;
-  if (dbg > 0) {
-    --dbg;
-    fprintf(stderr, "[pyapes_hip] k_sfq phase 3 kind %d RJ %d%s%s%s%s: tiles %dx%d chunks %d (CI ~%lld) blocks %d, %d blocks/CU\n",
-            SCH, RJ, HASU ? " (speed field)" : (US == 1 ? " (u >= 0)" : " (u < 0)"), STG ? " (RK stage)" : "",
-            A.aux && (const void*)A.aux == (const void*)A.d.p ? " (self)" : "", SRC ? " (source)" : "", A.tiles_j, A.tiles_k, chunks,
-            (long long)(G.n0 / chunks), nblk, sfq_blocks_per_cu<T, RJ, HASU, US, STG, SRC, SCH>());
-  }
-  hipLaunchKernelGGL((k_sfq<T, RJ, HASU, US, STG, SRC, SCH>), dim3(nblk), dim3(256), 0, c->stream, A);
-  return nblk;
+  static int bpc = 0, dbg = -1;
+  static const TileKernel K = {(const void*)k_sfq<T, RJ, HASU, US, STG, SRC, SCH>, RJ, VecOf<T>::N, 2, &bpc, &dbg,
+    [](char* s, size_t n, const void* args) {
+      const Cg3dArgs<T>& A = *(const Cg3dArgs<T>*)args;
+      snprintf(s, n, "k_sfq phase 3 kind %d RJ %d%s%s%s%s", SCH, RJ, HASU ? " (speed field)" : (US == 1 ? " (u >= 0)" : " (u < 0)"), STG ? " (RK stage)" : "",
+               A.aux && (const void*)A.aux == (const void*)A.d.p ? " (self)" : "", SRC ? " (source)" : "");
+    }, false};
+  return launch_tiled(c, K, c->G.n1, c->G.n2, &A, &A.tiles_j);
+}
+
+// V's instantiation of k_sfq for scheme SCH with / without SRC -- a speed field, or a scalar speed by its sign (US 1 / 2); plain
+// and STG; one of the STATED row counts -- launched, or 0
+template <typename T, bool SRC, int SCH, int... ROWS>
+static int launch_sfq_speed(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V) {
+  return with_bool(V.stg, [&](auto stg) {
+    return with_int<ROWS...>(V.rows, [&](auto rj) {
+      constexpr bool STG = decltype(stg)::value;
+      constexpr int RJ = decltype(rj)::value;
+      if (V.hasu) return launch_sfq<T, RJ, true, 0, STG, SRC, SCH>(c, A);
+      return with_int<1, 2>(V.us, [&](auto us) { return launch_sfq<T, RJ, false, decltype(us)::value, STG, SRC, SCH>(c, A); });
+    });
+  });
 }

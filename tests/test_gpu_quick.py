@@ -167,7 +167,7 @@ def test_every_case_runs_on_the_kernel_it_is_meant_for():
 
 
 # ---- 2. rows per wave -----------------------------------------------------------------------------------------------
-# The dispatcher (csrc/pa_sfq.hip sfq_rows_per_wave) picks TWO rows per wave on every mesh unless option "sfq" is 4, and the
+# The dispatcher (csrc/pa_sf_kernel.h sf_variant) picks TWO rows per wave on every mesh unless option "sfq" is 4, and the
 # option values 2 / 4 force a row count on any mesh -- so [40, 36, 72] (three tiles of 16 rows, the last one partly
 # filled; six of 8 rows) is the smallest mesh that reaches both instantiations with more than one tile and an overhanging one.
 def rows_per_wave_case():

@@ -61,7 +61,7 @@ CASES = [
     ("euler_f64_central_fastpath_off", [12, 20, 136], "double", R.ALLDIR, CENTRAL, False, {"fastpath": 0}, "k_euler"),
 ]
 CASE = {c[0]: c for c in CASES}
-# a mesh on which the rule itself selects four rows per wave (launch_sf_any on 256 CUs: 16-row tiles must leave chunks of >= 32
+# a mesh on which the rule itself selects four rows per wave (sf_rows_per_wave on 256 CUs: 16-row tiles must leave chunks of >= 32
 # planes) -- 67 M cells; not the smallest: thin meshes such as [256, 1010, 8] meet the rule with 2 M (tests/test_gpu_chunks.py).
 # What runs on it compares a SELF launch with a speed-field launch of the same kernel family, no reference.
 RJ4_SHAPE = [256, 512, 512]
