@@ -1019,3 +1019,68 @@ def solve_poisson(mesh: OMesh, bc_cfg: Sequence[dict], rhs: Tensor, x0: Tensor |
     terms = [OTerm("laplacian", tabs, coeff, sign)]
     fn = {"cg": cg, "bicgstab": bicgstab, "jacobi": jacobi}[method.lower()]
     return fn(x, rhs, terms, mesh, bcs, tol, max_it, **kw)
+
+
+# --------------------------------------------------------------------------
+# convenience: a multi-term equation  sum_k sign_k * op_k(x) == rhs  end to end
+# (fdm.py:27-105 + ops.py:47-81 + linalg.py:33-71)
+# --------------------------------------------------------------------------
+def equation_terms(mesh: OMesh, bcs: Sequence[OBC], terms_spec: Sequence[dict], x: Tensor):
+    """terms_spec: one dict per operator of the equation, in the order the DSL registered them:
+    {"kind": "laplacian" | "grad", "sign": +-1.0, "coeff": float | Tensor | None} or
+    {"kind": "div", "sign": +-1.0, "u": float | Tensor, "limiter": "none" | "upwind"}.
+    -> (terms, adjs): the OTerm list of ``Aop`` and, per term, the tensor its ``adjust_rhs`` returns.  The
+    adjustment does not see the term's sign (ops.py:63-77 adds every operator's adjustment as it is)."""
+    terms, adjs = [], []
+    for s in terms_spec:
+        kind, sign = s["kind"], float(s.get("sign", 1.0))
+        if kind == "laplacian":
+            terms.append(OTerm("laplacian", laplacian_tables(x, mesh, bcs), s.get("coeff"), sign))
+            adjs.append(laplacian_rhs_adjust(x, mesh, bcs))
+        elif kind == "grad":
+            terms.append(OTerm("grad", grad_tables(x, mesh, bcs), s.get("coeff"), sign))
+            adjs.append(grad_rhs_adjust(x, mesh, bcs))
+        elif kind == "div":
+            lim = s.get("limiter", "none")
+            terms.append(OTerm("div", div_tables(s["u"], x, mesh, bcs, lim), None, sign))
+            adjs.append(div_rhs_adjust(s["u"], x, mesh, bcs, lim))
+        else:
+            raise ValueError(kind)
+    return terms, adjs
+
+
+def solve_equation(mesh: OMesh, bc_cfg: Sequence[dict], terms_spec: Sequence[dict], rhs: Tensor,
+                   x0: Tensor | None = None, method: str = "bicgstab", tol: float = 1e-6, max_it: int = 1000):
+    """``Solver.set_eq(eq == rhs)`` + ``Solver.solve()`` of the reference for the equation ``terms_spec``
+    describes (``equation_terms``).  The caller's ``rhs`` is modified in place: every term's adjustment is
+    added to it in term order, unsigned (ops.py:63-77), so afterwards it is the reference's ``solver.rhs``.
+    Central Div with a neumann / symmetry face raises IndexError, like the reference (fdc.py:543-609)."""
+    bcs = make_bcs(mesh, bc_cfg)
+    x = torch.zeros(1, *mesh.nx, dtype=mesh.dtype) if x0 is None else x0
+    terms, adjs = equation_terms(mesh, bcs, terms_spec, x)
+    for a in adjs:
+        rhs += a
+    fn = {"cg": cg, "bicgstab": bicgstab}[method.lower()]
+    return fn(x, rhs, terms, mesh, bcs, tol, max_it)
+
+
+# Neumann values per NODE, callables of (grid, mask) that vary along both directions of their face (products and
+# sums only, so a CPU and a GPU evaluation give the same bits).  One face on each axis of a 3-D mesh; the same
+# functions drive the reference (tests/golden/make_golden.py), this oracle and the product.
+def _pn_x(grid, mask, *_):
+    return 0.5 + 0.3 * grid[1][mask] - 0.2 * grid[2][mask] * grid[1][mask]
+
+
+def _pn_y(grid, mask, *_):
+    return -0.25 + 0.4 * grid[0][mask] * grid[2][mask] + 0.1 * grid[2][mask]
+
+
+def _pn_z(grid, mask, *_):
+    return 0.3 - 0.5 * grid[0][mask] + 0.7 * grid[1][mask] * grid[0][mask]
+
+
+def pernode_cfg() -> list[dict]:
+    """xl D(0), xu N(f(y, z)), yl N(f(x, z)), yu D(0.2), zl N(f(x, y)), zu D(1.0)"""
+    vals = [("dirichlet", 0.0), ("neumann", _pn_x), ("neumann", _pn_y), ("dirichlet", 0.2),
+            ("neumann", _pn_z), ("dirichlet", 1.0)]
+    return [{"bc_face": FACES[i], "bc_type": t, "bc_val": v} for i, (t, v) in enumerate(vals)]

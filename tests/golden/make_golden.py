@@ -17,7 +17,7 @@ For every case this script
      descriptor (``cases.json``).
 Fixtures are data only: inputs and expected outputs.
 
-usage:  python tests/golden/make_golden.py
+usage:  python tests/golden/make_golden.py [name prefix ...]    (prefixes: regenerate only those cases)
 """
 from __future__ import annotations
 
@@ -283,6 +283,72 @@ def run_solve(case):
              rtol=1e-13 if case["dtype"] == "double" else 1e-6)
         assert abs(ro["tol"] - rep["tol"]) <= 1e-9 * max(abs(rep["tol"]), 1e-300) + 1e-20 or case["dtype"] != "double", (ro, rep)
         print(f"   {case['name']} K={K}: itr={rep['itr']} tol={rep['tol']:.16e} conv={rep['converge']}")
+    out["_reports"] = np.frombuffer(json.dumps(reports).encode(), dtype=np.uint8)
+    return out
+
+
+def run_eqn(case):
+    """Multi-term equations through Solver.set_eq / Aop / solve: Div +- Laplacian (central / literal upwind, number or
+    tensor speed), Grad - Laplacian in 1-D, one operator object used twice.  Stores the reference's solver.rhs after
+    set_eq, its Aop on the BC-filled x0 and its iterates; asserts the oracle's solve_equation (adjustments added in
+    term order, unsigned) reproduces them, and that the reference ALGORITHM with its dot products summed in another
+    order stays within a tenth of the bar the GPU tests assert (BiCGSTAB amplifies summation order)."""
+    from helpers import eqn_build, eqn_cfg, eqn_spec, eqn_tensor, rel_err, sum_order
+    mr, mo = ref_mesh(case), orc_mesh(case)
+    nd = mr.dim
+    f = mr.dtype.float
+    co = eqn_cfg(case)
+    cr = [dict(c, bc_val_opt=None) for c in co]
+    x0 = rand_field(case, mr)
+    rhs0 = torch.zeros_like(x0) + case["rhs_float"] if "rhs_float" in case else rhs_of(case, mr)
+    ut = eqn_tensor(case, (1, *mr.nx), f)
+    out = {"x0": npy(x0), "rhs0": npy(rhs0), "u_tensor": npy(ut)}
+    bcs_o = O.make_bcs(mo, co)
+    if case.get("tensor", "randn") == "randn" and any(p == "tensor" for _, _, p in case["terms"]):
+        for bc in bcs_o:   # the speed takes both signs on every Neumann layer: both branches of the upwind adjustment
+            if bc.type == "neumann":
+                assert ut[0][bc.prev].min() < 0 < ut[0][bc.prev].max(), (case["name"], bc.face)
+    fcfg = {"div": {"limiter": case["limiter"], "edge": False}} if "limiter" in case else None
+    spec = eqn_spec(case, ut)
+    rtol = 1e-13 if case["dtype"] == "double" else 1e-6
+    gpu_bar = 1e-10 if case["dtype"] == "double" else 1e-5
+    reports = {}
+    for K in case["max_its"]:
+        var = Field("p", 1, mr, {"domain": cr, "obstacle": None})
+        var.set_var_tensor(x0.clone())
+        rhs_r = rhs0.clone()
+        solver = Solver({"fdm": {"method": case["method"], "tol": case["tol"], "max_it": K, "report": False}})
+        eq = eqn_build(FDM(fcfg), var, case, ut)
+        solver.set_eq(eq == (case["rhs_float"] if "rhs_float" in case else rhs_r))
+        if "rhs_set_eq" not in out:
+            out["rhs_set_eq"] = npy(solver.rhs).copy()
+            filled = Field("q", 1, mr, {"domain": cr, "obstacle": None})
+            filled.set_var_tensor(x0.clone())
+            for bc in filled.bcs:
+                bc.apply(filled(), mr.grid, 0)
+            out["aop"] = npy(solver.Aop(filled))
+            xf = x0.clone()
+            O.bc_fill(xf, bcs_o)
+            terms, adjs = O.equation_terms(mo, bcs_o, spec, xf)
+            same(O.Aop(xf, terms, nd), out["aop"], f"{case['name']} aop")
+        rep = solver.solve()
+        out[f"x_K{K}"] = npy(var())
+        reports[str(K)] = {"itr": int(rep["itr"]), "tol": float(rep["tol"]), "converge": bool(rep["converge"])}
+
+        rhs_o = rhs0.clone()
+        xo, ro = O.solve_equation(mo, co, spec, rhs_o, x0.clone(), case["method"], case["tol"], K)
+        same(rhs_o, out["rhs_set_eq"], f"{case['name']} rhs_set_eq")
+        assert ro["itr"] == rep["itr"] and ro["converge"] == rep["converge"], (case["name"], K, ro, rep)
+        same(xo, out[f"x_K{K}"], f"{case['name']} x_K{K}", exact=False, rtol=rtol)
+        dev = 0.0
+        for v in (1, 2, 3, 4):
+            with sum_order(v):
+                xv, rv = O.solve_equation(mo, co, spec, rhs0.clone(), x0.clone(), case["method"], case["tol"], K)
+            assert rv["itr"] == rep["itr"]
+            dev = max(dev, rel_err(xv, out[f"x_K{K}"]))
+        assert dev <= 0.1 * gpu_bar, (case["name"], K, dev)
+        print(f"   {case['name']} K={K}: itr={rep['itr']} tol={rep['tol']:.16e} conv={rep['converge']} "
+              f"oracle {rel_err(xo, out[f'x_K{K}']):.1e} other summation orders {dev:.1e}")
     out["_reports"] = np.frombuffer(json.dumps(reports).encode(), dtype=np.uint8)
     return out
 
@@ -613,6 +679,50 @@ CASES += [mk("rfp_rz_32x64_f64", "rfp", 2, [32, 64], "double", [], coord="rz",
              box=([0.0, -5.0], [5.0, 5.0]))]    # mesh of the reference's tests/test_ops.py::test_fp
 
 
+# multi-term solver equations (kind "eqn"): every case a random x0, tol 1e-30 and short fixed iteration counts
+def _eqn(name, nd, spacing, dtype, bcs, terms, **kw):
+    kw.setdefault("method", "bicgstab")
+    # fp32 BiCGSTAB stops at 2 iterations: at 4 the reference algorithm alone, its dot products summed in another order,
+    # moves by 1e-6 .. 3e-5 on these operators (run_eqn requires a tenth of the 1e-5 the GPU tests assert)
+    kw.setdefault("max_its", [1, 4] if dtype == "double" or kw["method"] != "bicgstab" else [1, 2])
+    return mk(name, "eqn", nd, spacing, dtype, bcs, terms=terms, rhs="randn", tol=1e-30, **kw)
+
+
+BOX3 = ([0.0, 0.0, 0.0], [1.0, 1.1, 1.2])
+MIX3 = [D(0.0), N(0.5), SY, D(0.2), N(-0.25), D(1.0)]
+for dt in ("double", "single"):
+    s_ = "f64" if dt == "double" else "f32"
+    for tag, u in (("up", 0.8), ("um", -0.8), ("ut", "tensor")):
+        CASES.append(_eqn(f"eqn2d_mix_{tag}_{s_}", 2, [13, 18], dt, [D(0.3), N(0.5), SY, D(-0.2)],
+                          [["div", 1.0, u], ["laplacian", -1.0, 0.05]], limiter="upwind"))
+    for tag, u in (("u", 0.8), ("ut", "tensor")):
+        # Laplacian first, Div negated: the adjustments are still added, in this order
+        CASES.append(_eqn(f"eqn3d_mix_{tag}_{s_}", 3, [9, 10, 12], dt, MIX3,
+                          [["laplacian", -1.0, 0.05], ["div", -1.0, u]], limiter="upwind", box=BOX3))
+        CASES.append(_eqn(f"eqn3d_pernode_{tag}_{s_}", 3, [9, 10, 12], dt, "pernode3d",
+                          [["laplacian", -1.0, 0.05], ["div", -1.0, u]], limiter="upwind", box=BOX3))
+        CASES.append(_eqn(f"eqn3d_zper_central_{tag}_{s_}", 3, [9, 10, 12], dt,
+                          [D(0.5), D(0.1), D(0.0), D(0.2), PE, PE],
+                          [["div", 1.0, u], ["laplacian", -1.0, 0.05]], limiter="none",
+                          **({"seed": 1} if (tag, dt) == ("u", "single") else {})))   # seed 0: 1.8e-6 at 2 iterations
+    CASES += [
+        _eqn(f"eqn1d_grad_nd_{s_}", 1, [33], dt, [N(0.4), D(0.2)], [["grad", 1.0, None], ["laplacian", -1.0, 0.1]],
+             rhs_float=1.0),
+        _eqn(f"eqn1d_grad_dn_{s_}", 1, [33], dt, [D(0.3), N(-0.7)], [["grad", 1.0, None], ["laplacian", -1.0, 0.1]],
+             rhs_float=1.0),
+    ]
+    # ONE Laplacian object used twice: -fdm.laplacian(0.3, phi) - fdm.laplacian(gamma, phi) solves two gamma terms
+    # (the second call replaces the shared object's state; pinned, SURVEY Q8 covers only separate FDM instances)
+    for m, its in (("cg", [0, 5]), ("bicgstab", None)):
+        CASES.append(_eqn(f"eqn3d_lap_twice_{m}_{s_}", 3, [9, 10, 12], dt, MIX3,
+                          [["laplacian", -1.0, "tensor"], ["laplacian", -1.0, "tensor"]],
+                          dsl=[["laplacian", -1.0, 0.3], ["laplacian", -1.0, "tensor"]], tensor="gamma",
+                          method=m, box=BOX3, **({"max_its": its} if its else {})))
+CASES.append(_eqn("eqn_rz_mix_f64", 2, [12, 15], "double", [N(0.0), D(1.0), D(0.0), N(0.5)],
+                  [["div", 1.0, 0.7], ["laplacian", -1.0, 0.05]], limiter="upwind", coord="rz",
+                  box=([0.0, 0.0], [1.0, 1.5])))
+
+
 def main():
     torch.set_num_threads(8)
     only = tuple(sys.argv[1:]) or None   # name prefixes: regenerate just those cases
@@ -624,15 +734,16 @@ def main():
             continue
         print(f"[golden] {case['name']}")
         out = {"ops": run_ops, "solve": run_solve, "spatial": run_spatial, "rfp": run_rfp,
-               "euler": run_euler}[case["kind"]](case)
+               "euler": run_euler, "eqn": run_eqn}[case["kind"]](case)
         path = os.path.join(HERE, case["name"] + ".npz")
         np.savez_compressed(path, **out)
         total += os.path.getsize(path)
         index.append(case)
-    # the reference's own golden file for test_heat_conduction_2d_mixed (data, 11 lines)
-    import pandas as pd
-    ref = pd.read_csv("/root/reference/tests/data/laplace_equation/sol_ref_10_by_10.csv", index_col=0).to_numpy()
-    np.savez_compressed(os.path.join(HERE, "ref_heat_10x10.npz"), sol=ref)
+    if only is None:
+        # the reference's own golden file for test_heat_conduction_2d_mixed (data, 11 lines)
+        import pandas as pd
+        ref = pd.read_csv("/root/reference/tests/data/laplace_equation/sol_ref_10_by_10.csv", index_col=0).to_numpy()
+        np.savez_compressed(os.path.join(HERE, "ref_heat_10x10.npz"), sol=ref)
     with open(os.path.join(HERE, "cases.json"), "w") as f:
         json.dump(index, f, indent=1)
     print(f"[golden] wrote {len(index)} cases, {total/1e6:.2f} MB")

@@ -207,12 +207,10 @@ def scalar_history(method, sums):
     return np.array(rows, dtype=np.float64).reshape(-1, 3)
 
 
-def oracle_solve(case, rhs0, K, variant=0, tap=None):
-    """The oracle on a golden case.  variant > 0 evaluates every torch.sum in a different, equally
-    valid order (reversed along all / the first / the last summed axis, or as two half sums):
-    same algorithm, same inputs, same arithmetic otherwise."""
-    import warnings
-    mesh = oracle_mesh(case)
+@contextlib.contextmanager
+def sum_order(variant):
+    """While active, every ``torch.sum`` is evaluated in a different, equally valid order (variant 1 / 2 / 3:
+    reversed along all / the first / the last summed axis; 4: as two half sums; 0: torch's own)."""
     orig = torch.sum
 
     def fsum(t, dim=None, **kw):
@@ -232,14 +230,127 @@ def oracle_solve(case, rhs0, K, variant=0, tap=None):
     if variant:
         torch.sum = fsum
     try:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            with (tap if tap is not None else contextlib.nullcontext()):
-                return O.solve_poisson(mesh, oracle_cfg(case), torch.as_tensor(rhs0).clone(), method=case["method"],
-                                       tol=case["tol"], max_it=K, coeff=case.get("coeff", 1.0),
-                                       sign=case.get("sign", 1.0))
+        yield
     finally:
         torch.sum = orig
+
+
+# ---- multi-term equations (golden kind "eqn", tests/test_gpu_equations.py) ----
+def eqn_tensor(case, shape, dtype):
+    """The tensor parameter of an equation case: a Div speed (randn, both signs) or a Laplacian coefficient (> 0)."""
+    g = torch.Generator().manual_seed(case.get("seed", 0) + 7)
+    t = torch.randn(shape, generator=g, dtype=torch.float64)
+    if case.get("tensor", "randn") == "gamma":
+        t = 0.2 + 0.1 * t.abs()
+    return t.to(dtype)
+
+
+def eqn_cfg(case):
+    """Oracle BC list of an equation case: [type, value] pairs in face order, or a named set of callables."""
+    if case["bcs"] == "pernode3d":
+        return O.pernode_cfg()
+    faces = case_faces(case)
+    return [{"bc_face": faces[i], "bc_type": t, "bc_val": v} for i, (t, v) in enumerate(case["bcs"])]
+
+
+def eqn_spec(case, tensor):
+    """``O.equation_terms`` spec of ``case["terms"]`` = [kind, sign, parameter] per operator (parameter: a number, None,
+    or "tensor" for the case's tensor) -- the equation that is SOLVED, which for an operator object used twice
+    is not the one written (``case["dsl"]``)."""
+    spec = []
+    for kind, sign, p in case["terms"]:
+        p = tensor if p == "tensor" else p
+        if kind == "div":
+            spec.append({"kind": "div", "sign": sign, "u": p, "limiter": case["limiter"]})
+        else:
+            spec.append({"kind": kind, "sign": sign, "coeff": p})
+    return spec
+
+
+def eqn_build(fdm, var, case, tensor):
+    """The DSL expression of ``case["dsl"]`` (default: ``case["terms"]``), operator by operator in Python's evaluation
+    order of ``[-]A +- B +- ...``, on the reference's FDM or the product's (same DSL).  ``tensor`` on var's device."""
+    expr = None
+    for kind, sign, p in case.get("dsl", case["terms"]):
+        p = tensor if p == "tensor" else p
+        op = getattr(fdm, kind)
+        term = op(var) if p is None else op(p, var)
+        if expr is None:
+            expr = -term if sign < 0 else term
+        else:
+            expr = expr - term if sign < 0 else expr + term
+    return expr
+
+
+def eqn_inputs(case):
+    """(x0, rhs0, tensor) of an equation case that has no fixture: the seeded recipe of tests/golden/make_golden.py"""
+    dt = torch.float64 if case["dtype"] == "double" else torch.float32
+    shape = (1, *case["spacing"])
+    g = torch.Generator().manual_seed(case.get("seed", 0))
+    rhs0 = torch.randn(shape, generator=g, dtype=torch.float64).to(dt)
+    g = torch.Generator().manual_seed(case.get("seed", 0) + 100)
+    x0 = torch.randn(shape, generator=g, dtype=torch.float64).to(dt)
+    return x0, rhs0, eqn_tensor(case, shape, dt)
+
+
+def eqn_oracle(case, x0, rhs0, tensor, K, variant=0):
+    """The oracle on an equation case -> (rhs after set_eq, A x on the BC-filled x0, iterate, report); variant as in
+    ``sum_order``."""
+    import warnings
+    mesh, cfg, spec = oracle_mesh(case), eqn_cfg(case), eqn_spec(case, tensor)
+    bcs = O.make_bcs(mesh, cfg)
+    xf = x0.clone()
+    O.bc_fill(xf, bcs)
+    ax = O.Aop(xf, O.equation_terms(mesh, bcs, spec, xf)[0], mesh.dim)
+    rhs = rhs0.clone()
+    with sum_order(variant), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        x, rep = O.solve_equation(mesh, cfg, spec, rhs, x0.clone(), case["method"], case["tol"], K)
+    return rhs, ax, x, rep
+
+
+# The two-term tiling of the 3-D / 2-D kernels needs whole rows and more than one k tile: meshes too large for
+# fixtures, graded against the oracle (which the "eqn" goldens pin to the reference).  Shapes and face sets of
+# tests/test_gpu_tiled_advdiff.py; BiCGSTAB, 3 iterations from a random x0.
+_D, _N = (lambda v=0.0: ["dirichlet", v]), (lambda v=0.0: ["neumann", v])
+_SY, _PE = ["symmetry", None], ["periodic", None]
+TILED_EQN_BCS = {"mix": [_D(0.0), _N(0.5), _SY, _D(0.0), _D(1.0), _N(-0.25)],
+                 "zper": [_D(0.5), _D(0.1), _D(0.0), _D(0.0), _PE, _PE]}
+TILED_EQN_SHAPES = [((20, 18, 132), "double"), ((9, 17, 129), "double"), ((40, 132), "double"), ((16, 20, 136), "single")]
+TILED_EQN_K = 3
+
+
+def tiled_eqn_cases():
+    """face set x scheme (literal upwind on both sets, central where no face is neumann / symmetry) x speed (+-0.8,
+    and a tensor on the first shape) x both term orders / signs of the Div"""
+    cases = []
+    for n, dtype in TILED_EQN_SHAPES:
+        nd = len(n)
+        for bc, lim in (("mix", "upwind"), ("zper", "upwind"), ("zper", "none")):
+            for utag, u in (("up", 0.8), ("um", -0.8), ("ut", "tensor")):
+                if u == "tensor" and n != TILED_EQN_SHAPES[0][0]:
+                    continue
+                for order, terms in (("div_first", [["div", 1.0, u], ["laplacian", -1.0, 0.05]]),
+                                     ("lap_first", [["laplacian", -1.0, 0.05], ["div", -1.0, u]])):
+                    name = "x".join(map(str, n)) + f"{dtype[0]}_{bc}_{lim}_{utag}_{order}"
+                    cases.append(dict(name=name, kind="eqn", lower=[0.0] * nd, upper=[1.0] * nd, spacing=list(n),
+                                      dtype=dtype, bcs=TILED_EQN_BCS[bc][:2 * nd], terms=terms, limiter=lim,
+                                      method="bicgstab", tol=1e-30, max_its=[TILED_EQN_K]))
+    return cases
+
+
+def oracle_solve(case, rhs0, K, variant=0, tap=None):
+    """The oracle on a golden case.  variant > 0 evaluates every torch.sum in a different, equally
+    valid order (reversed along all / the first / the last summed axis, or as two half sums):
+    same algorithm, same inputs, same arithmetic otherwise."""
+    import warnings
+    mesh = oracle_mesh(case)
+    with sum_order(variant), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        with (tap if tap is not None else contextlib.nullcontext()):
+            return O.solve_poisson(mesh, oracle_cfg(case), torch.as_tensor(rhs0).clone(), method=case["method"],
+                                   tol=case["tol"], max_it=K, coeff=case.get("coeff", 1.0),
+                                   sign=case.get("sign", 1.0))
 
 
 def summation_band(case, rhs0, K):

@@ -80,19 +80,21 @@ def test_tiled_equals_generic(shape, bc, scheme, monkeypatch):
 
 def test_advection_diffusion_solve_vs_oracle(monkeypatch):
     """3-D steady advection-diffusion, upwind (literal reference scheme), to convergence through the tiled
-    BiCGSTAB: same answer as the oracle's BiCGSTAB to solver accuracy"""
+    BiCGSTAB: same answer as the oracle's BiCGSTAB to solver accuracy.  The inflow face is an inhomogeneous Neumann
+    one, so the Div and the Laplacian rhs adjustments are both non-zero; the oracle adds them as the reference does
+    (O.solve_equation: every term's adjustment, whatever the term's sign)."""
     n = (17, 19, 33)
     om = O.OMesh([0.0] * 3, [1.0] * 3, list(n), "double")
-    cfg = [{"bc_face": O.FACES[i], "bc_type": "dirichlet", "bc_val": v} for i, v in enumerate([0.0, 0.5, 0.0, 0.0, 1.0, 0.0])]
-    bcs = O.make_bcs(om, cfg)
-    x0 = torch.zeros(1, *n, dtype=torch.float64)
+    faces = [("neumann", 0.5), ("dirichlet", 0.5), ("dirichlet", 0.0), ("dirichlet", 0.0), ("dirichlet", 1.0), ("dirichlet", 0.0)]
+    cfg = [{"bc_face": O.FACES[i], "bc_type": t, "bc_val": v} for i, (t, v) in enumerate(faces)]
     rhs = torch.ones(1, *n, dtype=torch.float64)
-    terms = [O.OTerm("div", O.div_tables(0.8, x0, om, bcs, "upwind"), None, 1.0),
-             O.OTerm("laplacian", O.laplacian_tables(x0, om, bcs), 0.05, -1.0)]
+    spec = [{"kind": "div", "sign": 1.0, "u": 0.8, "limiter": "upwind"}, {"kind": "laplacian", "sign": -1.0, "coeff": 0.05}]
+    rhs_o = rhs.clone()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        xo, ro = O.bicgstab(x0.clone(), rhs.clone() + O.div_rhs_adjust(0.8, x0, om, bcs, "upwind") * 1.0
-                            - O.laplacian_rhs_adjust(x0, om, bcs), terms, om, bcs, 1e-10, 2000)
+        xo, ro = O.solve_equation(om, cfg, spec, rhs_o, None, "bicgstab", 1e-10, 2000)
+    lap_only = rhs + O.laplacian_rhs_adjust(xo, om, O.make_bcs(om, cfg))
+    assert not torch.equal(rhs_o, rhs) and not torch.equal(rhs_o, lap_only)   # both adjustments took part
     monkeypatch.setenv("PYAPES_HIP_FASTPATH", "1")
     mesh = Mesh(Box([0.0] * 3, [1.0] * 3), None, list(n), "cuda", "double")
     var = Field("p", 1, mesh, {"domain": [dict(c, bc_val_opt=None) for c in cfg], "obstacle": None})
@@ -102,5 +104,6 @@ def test_advection_diffusion_solve_vs_oracle(monkeypatch):
         warnings.simplefilter("ignore")
         s.set_eq(fdm.div(0.8, var) - fdm.laplacian(0.05, var) == rhs.cuda())
         rep = s.solve()
+    assert torch.equal(s.rhs.cpu(), rhs_o)
     assert rep["converge"] and ro["converge"]
     assert rel_err(var().cpu(), xo) < 1e-7

@@ -84,6 +84,55 @@ def test_oracle_solve(case):
         assert err <= rtol, (case["name"], K, err)
 
 
+@pytest.mark.parametrize("case", golden_cases("eqn"), ids=lambda c: c["name"])
+def test_oracle_equation(case):
+    """Multi-term equations (Div +- Laplacian, Grad - Laplacian, one operator object used twice): the rhs after
+    set_eq -- every term's adjustment added in term order, unsigned -- and A x bit for bit, iterates <= 1e-13
+    (fp32: 1e-6) with the reference's counts."""
+    from helpers import eqn_oracle, rel_err
+    g = golden_load(case["name"])
+    x0, rhs0, ut = (torch.from_numpy(g[k]) for k in ("x0", "rhs0", "u_tensor"))
+    rtol = 1e-13 if case["dtype"] == "double" else 1e-6
+    for K in case["max_its"]:
+        rhs, ax, x, rep = eqn_oracle(case, x0, rhs0, ut, K)
+        _eq(rhs, g["rhs_set_eq"], "rhs_set_eq")
+        _eq(ax, g["aop"], "aop")
+        rep_ref = g["_reports"][str(K)]
+        assert rep["itr"] == rep_ref["itr"] and rep["converge"] == rep_ref["converge"]
+        assert rel_err(x, g[f"x_K{K}"]) <= rtol, (case["name"], K, rel_err(x, g[f"x_K{K}"]))
+
+
+def test_equation_fixture_sees_term_order():
+    """the adjustments added in the REVERSE term order round differently on the 3-D mixed-BC mesh: the fixture pins
+    the order, not only the sum"""
+    from helpers import eqn_cfg, eqn_spec
+    case = [c for c in golden_cases("eqn") if c["name"] == "eqn3d_mix_ut_f64"][0]
+    g = golden_load(case["name"])
+    want = torch.from_numpy(g["rhs_set_eq"])
+    assert not torch.equal(want, torch.from_numpy(g["rhs0"]))
+    mesh = _mesh(case)
+    bcs = O.make_bcs(mesh, eqn_cfg(case))
+    _, adjs = O.equation_terms(mesh, bcs, eqn_spec(case, torch.from_numpy(g["u_tensor"])), torch.from_numpy(g["x0"]))
+    rhs = torch.from_numpy(g["rhs0"]).clone()
+    for a in reversed(adjs):
+        rhs += a
+    assert not torch.equal(rhs, want)
+    assert torch.allclose(rhs, want, rtol=1e-14, atol=1e-14)
+
+
+def test_tiled_equation_inputs_are_summation_order_stable():
+    """tests/test_gpu_equations.py grades the tiled two-term kernels against the oracle at 1e-9 (fp32: 5e-5) on meshes
+    too large for fixtures.  BiCGSTAB amplifies summation order, so the inputs must leave the reference ALGORITHM
+    itself, its dot products summed in another order, within a tenth of that bar."""
+    from helpers import TILED_EQN_K, eqn_inputs, eqn_oracle, rel_err, tiled_eqn_cases
+    for case in tiled_eqn_cases():
+        x0, rhs0, ut = eqn_inputs(case)
+        _, _, x, rep = eqn_oracle(case, x0, rhs0, ut, TILED_EQN_K)
+        _, _, xv, repv = eqn_oracle(case, x0, rhs0, ut, TILED_EQN_K, variant=1)
+        assert rep["itr"] == repv["itr"] == TILED_EQN_K
+        assert rel_err(xv, x) <= 0.1 * (1e-9 if case["dtype"] == "double" else 5e-5), (case["name"], rel_err(xv, x))
+
+
 @pytest.mark.parametrize("case", golden_cases("euler"), ids=lambda c: c["name"])
 def test_oracle_euler_pieces(case):
     """Explicit Euler steps composed of reference operators (make_golden.run_euler): the oracle's pieces in
