@@ -130,62 +130,25 @@ __global__ void __launch_bounds__(PA_BLOCK) k_bicg_x(DevGeom G, const SolverScal
   T beta_n = (T)0;
   const double rho_cur = sc->rho;
   if (pre_n > 0) {
-    // folded k_bicg_post stage 12 (rows {|s|^2, t.s, t.t, r0.t} of the fused s / t kernel): stop test 1,
-    // then omega and rho_next -- every block on its own, same summation order; block 0 stores
+    // folded stop test 1, then omega and rho' (pa_step_bicg_mid on the rows {|s|^2, t.s, t.t, r0.t} of the fused s / t
+    // kernel) -- every block on its own, same summation order; block 0 stores
+    // (Both launch sites pass sc_w == sc, so a late block may read the early flag, omega and rho' block 0 has already
+    // stored.  All three only pass THROUGH the step: the early flag comes back as it went in on the non-finite path alone,
+    // where block 0 stored it unchanged and every block returns; omega and rho' when stop test 1 ended the solve, where
+    // the look-ahead beta formed from them goes unused (`pn` is false).  Whatever a block uses, it computed from the sums.)
     __shared__ double pre_sm[24];
-    const int done_in = sc->done;
-    const double tol_lim = sc->tolerance, omega_in = sc->omega;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = threadIdx.x; b < pre_n; b += PA_BLOCK) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] += pre_part[4 * (int64_t)b + q];
-    }
-    if (done_in) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off, 64);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) pre_sm[4 * (threadIdx.x >> 6) + q] = v[q];
-    }
-    __syncthreads();
+    const int done_in = sc->done, early_in = sc->finished_early;
+    const double tol_lim = sc->tolerance, omega_in = sc->omega, rho_next_in = sc->rho_next;
+    double t4[4];
+    if (!pa_fold_sums<4, 0>(pre_part, pre_n, 4, 0, nullptr, 0, done_in, pre_sm, t4)) return;
     if (threadIdx.x == 0) {
-      double t4[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int w = 0; w < PA_BLOCK / 64; ++w) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) t4[q] += pre_sm[4 * w + q];
-      }
-      const T tol = (T)sqrt(t4[0]);
-      const bool bad = isnan(tol) || isinf(tol);
-      const int fe = (!bad && (double)tol <= tol_lim) ? 1 : 0;
-      T om = (T)omega_in;
-      if (!bad && !fe) om = (T)pa_nan_to_num<T>((T)t4[1] / (T)t4[2]);
-      pre_sm[16] = (double)om;
-      pre_sm[17] = fe ? 1.0 : 0.0;
-      pre_sm[18] = bad ? 1.0 : 0.0;
-      {   // the next beta, as the stage that closes the iteration forms it (k_bicg_post stage 3 / phase 5 prologue)
-        T rn = -om;
-        rn = rn * (T)t4[3];
-        T bq = (T)(double)rn / (T)rho_cur;
-        bq = bq * alpha;
-        bq = bq / om;
-        pre_sm[19] = (double)bq;
-      }
-      if (blockIdx.x == 0) {
-        sc_w->tol = (double)tol;
-        if (bad) {
-          sc_w->err = 1;
-          sc_w->done = 1;
-        } else {
-          sc_w->finished_early = fe;
-          if (!fe) {
-            sc_w->omega = (double)om;
-            T rn = -om;
-            rn = rn * (T)t4[3];
-            sc_w->rho_next = (double)rn;
-          }
-        }
-      }
+      const PaBicgMid m = pa_step_bicg_mid<T>(t4[0], t4[1], t4[2], t4[3], tol_lim, early_in, omega_in, rho_next_in);
+      pre_sm[16] = m.om.omega;
+      pre_sm[17] = m.stop.early ? 1.0 : 0.0;
+      pre_sm[18] = m.stop.err ? 1.0 : 0.0;
+      // the next beta, as the step that closes the iteration forms it
+      pre_sm[19] = (double)pa_step_bicg_beta<T>((T)m.om.rho_next, (T)rho_cur, alpha, (T)m.om.omega);
+      if (blockIdx.x == 0) pa_put(sc_w, m);
     }
     __syncthreads();
     if (pre_sm[18] != 0.0) return;
@@ -196,10 +159,7 @@ __global__ void __launch_bounds__(PA_BLOCK) k_bicg_x(DevGeom G, const SolverScal
     if (sc->done) return;
     omega = (T)sc->omega;
     early = sc->finished_early;
-    T bq = (T)sc->rho_next / (T)rho_cur;
-    bq = bq * alpha;
-    bq = bq / omega;
-    beta_n = bq;
+    beta_n = pa_step_bicg_beta<T>((T)sc->rho_next, (T)rho_cur, alpha, omega);
   }
   const bool pn = p_next != nullptr && !early;
   double s[1] = {0.0};
@@ -301,76 +261,36 @@ __global__ void __launch_bounds__(PA_BLOCK) k_bicg_x(DevGeom G, const SolverScal
   pa_block_reduce_store<1>(s, partials);
 }
 
-// stage: 0 after pv (alpha), 1 after s (tol check 1), 2 after t (omega, rho_next), 3 after x (tol check 2)
+// The single-block scalar steps (pa_scalar_steps.h).  step 0: alpha, after p / v; 1: stop test 1, after s; 2: omega and
+// rho', after t; 12: both, after the fused s / t kernel (rows {|s|^2, t.s, t.t, r0.t}); 3: the close, after x / r;
+// 10: the start of a slab solve (rho' = r0.r0, the first beta).  partials non-null: the step's sums are reduced from
+// nblk partial rows first; null (slabs): they are the all-reduced entries of `sums` (layout: the slab section below).
 template <typename T>
 __global__ void __launch_bounds__(PA_BLOCK) k_bicg_post(SolverScalars* sc, const double* partials, int nblk,
-                                                         int stage) {
+                                                         const double* sums, int step) {
   __shared__ double sm[PA_BLOCK / 64];
-  if (sc->done) return;
-  if (stage == 0) {
-    double v = pa_reduce_partials(partials, nblk, 1, 0, sm);
+  if (step == 10) {
     if (threadIdx.x == 0) {
-      sc->itr += 1;
-      T r0v = (T)v;
-      T rho = (T)sc->rho;
-      sc->alpha = pa_nan_to_num<T>(rho / r0v);
+      pa_logic_bicg_start<T>(sc, sums[1]);
+      sc->done = 0;   // `while not finished`: at least one iteration
     }
-  } else if (stage == 1) {
-    double v = pa_reduce_partials(partials, nblk, 1, 0, sm);
-    if (threadIdx.x == 0) {
-      T tol = (T)sqrt(v);
-      sc->tol = (double)tol;
-      if (isnan(tol) || isinf(tol)) { sc->err = 1; sc->done = 1; return; }
-      sc->finished_early = (sc->tol <= sc->tolerance) ? 1 : 0;
-    }
-  } else if (stage == 2) {
-    if (sc->finished_early) return;
-    double ts = pa_reduce_partials(partials, nblk, 3, 0, sm);
-    double tt = pa_reduce_partials(partials, nblk, 3, 1, sm);
-    double r0t = pa_reduce_partials(partials, nblk, 3, 2, sm);
-    if (threadIdx.x == 0) {
-      T om = (T)pa_nan_to_num<T>((T)ts / (T)tt);
-      sc->omega = (double)om;
-      T rn = -om;
-      rn = rn * (T)r0t;
-      sc->rho_next = (double)rn;
-    }
-  } else if (stage == 12) {
-    // fused s / t kernel: partial rows are {|s|^2, t.s, t.t, r0.t}: stop test 1, then omega, rho_next
-    double ss = pa_reduce_partials(partials, nblk, 4, 0, sm);
-    double ts = pa_reduce_partials(partials, nblk, 4, 1, sm);
-    double tt = pa_reduce_partials(partials, nblk, 4, 2, sm);
-    double r0t = pa_reduce_partials(partials, nblk, 4, 3, sm);
-    if (threadIdx.x == 0) {
-      T tol = (T)sqrt(ss);
-      sc->tol = (double)tol;
-      if (isnan(tol) || isinf(tol)) { sc->err = 1; sc->done = 1; return; }
-      sc->finished_early = (sc->tol <= sc->tolerance) ? 1 : 0;
-      if (!sc->finished_early) {
-        T om = (T)pa_nan_to_num<T>((T)ts / (T)tt);
-        sc->omega = (double)om;
-        T rn = -om;
-        rn = rn * (T)r0t;
-        sc->rho_next = (double)rn;
-      }
-    }
-  } else {
-    double v = pa_reduce_partials(partials, nblk, 1, 0, sm);
-    if (threadIdx.x == 0) {
-      if (sc->finished_early) { sc->done = 1; return; }
-      T tol = (T)sqrt(v);
-      sc->tol = (double)tol;
-      if (isnan(tol) || isinf(tol)) { sc->err = 1; sc->done = 1; return; }
-      if (sc->tol <= sc->tolerance) sc->done = 1;
-      if (sc->itr >= sc->max_it) sc->done = 1;
-      // next iteration's beta = rho_next / rho * alpha / omega ; rho = rho_next (linalg.py:212-214)
-      T b = (T)sc->rho_next / (T)sc->rho;
-      b = b * (T)sc->alpha;
-      b = b / (T)sc->omega;
-      sc->beta = (double)b;
-      sc->rho = sc->rho_next;
-    }
+    return;
   }
+  if (sc->done) return;
+  const int ncol = step == 2 ? 3 : (step == 12 ? 4 : 1), off = step == 0 ? 0 : (step == 3 ? 5 : (step == 2 ? 2 : 1));
+  double v[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    if (q >= ncol) continue;
+    if (partials) v[q] = pa_reduce_partials(partials, nblk, ncol, q, sm);
+    else if (threadIdx.x == 0) v[q] = sums[off + q];
+  }
+  if (threadIdx.x != 0) return;
+  if (step == 0) pa_logic_bicg_alpha<T>(sc, v[0]);
+  else if (step == 1) pa_logic_bicg_stop1<T>(sc, v[0]);
+  else if (step == 2) pa_logic_bicg_omega<T>(sc, v[0], v[1], v[2]);
+  else if (step == 12) pa_logic_bicg_mid<T>(sc, v[0], v[1], v[2], v[3]);
+  else pa_logic_bicg_close<T>(sc, v[0]);
 }
 
 template <typename T>
@@ -414,7 +334,7 @@ static int bicg_run_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_it,
   };
   if (c->cg_pitch) {
     // A x (tiled kernel, contiguous) into t, then r0 = r = b - A x scattered into the pitched rows with the loop and
-    // partial sums of the contiguous form (k_cg_init_ax_pitch); pad cells of every array zero for the whole solve
+    // partial sums of the contiguous form (k_cg_init, PITCH); pad cells of every array zero for the whole solve
     if ((rc = cg_residual_init_pitch<T>(c, E, xv, rhs, t, r0, r, part))) return rc;
   }
   // the tiled phases do not visit the last boundary row / column of non-periodic axes (launch_cg3d): p, v, s, t are 0
@@ -428,13 +348,7 @@ static int bicg_run_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_it,
   if ((rc = read_scalars(c))) return rc;
   {
     SolverScalars h = *c->h_sc;
-    h.rho_next = h.rr;
-    h.tol = (double)(T)sqrt((T)h.rr);
-    T b = (T)h.rho_next / (T)1.0;
-    b = b * (T)1.0;
-    b = b / (T)1.0;
-    h.beta = (double)b;
-    h.rho = h.rho_next;
+    pa_logic_bicg_start<T>(&h, h.rr);   // (on the host: the square root of tol0 is the host's)
     h.done = 0;  // `while not finished`: at least one iteration
     *c->h_sc = h;
     PA_HIP(c, hipMemcpyAsync(c->sc, c->h_sc, sizeof(h), hipMemcpyHostToDevice, c->stream));
@@ -474,7 +388,7 @@ static int bicg_run_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_it,
   }
   if (c->cg_pitch && c->coord == PA_COORD_RZ && !pgiven) { pa_set_err(c, "pitched BiCGSTAB on an axisymmetric mesh needs the marching v phase"); return PA_E_STATE; }
   auto flush3 = [&]() {
-    if (pend3 > 0) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg2, pend3, 3);
+    if (pend3 > 0) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg2, pend3, (const double*)nullptr, 3);
     pend3 = 0;
     c->fold_b_n = 0;
   };
@@ -512,7 +426,7 @@ static int bicg_run_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_it,
     }
     copy_x_old<T>(c, x);   // after the p / v phase: its prologue has decided whether this iteration still runs
     int pend0 = (fold && used <= PA_MAX_GRID) ? used : 0;
-    if (!pend0) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg0, used, 0);
+    if (!pend0) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg0, used, (const double*)nullptr, 0);
     Vec<T> vnv = vec_of(v[cur ^ 1]);
     c->fold_a_n = pend0;          // phase 6 computes alpha itself
     // (option "bicg_srv", default on: the tiled phase stores t alone and k_bicg_x re-forms s from r and v')
@@ -524,15 +438,15 @@ static int bicg_run_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_it,
     int pend12 = 0;
     if (used2 > 0) {
       pend12 = (fold && used2 <= PA_MAX_GRID) ? used2 : 0;
-      if (!pend12) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg1, used2, 12);
+      if (!pend12) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg1, used2, (const double*)nullptr, 12);
     } else {
-      if (pend0) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg0, pend0, 0);
+      if (pend0) hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg0, pend0, (const double*)nullptr, 0);
       hipLaunchKernelGGL(k_bicg_s<T>, dim3(nblk), dim3(PA_BLOCK), 0, c->stream, G, c->sc, (const T*)r,
                          (const T*)v[cur ^ 1], s, reg1);
-      hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg1, nblk, 1);
+      hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg1, nblk, (const double*)nullptr, 1);
       Vec<T> sv = pa_vec_self<T>(c, s);
       hipLaunchKernelGGL(k_bicg_t<T>, dim3(nblk), dim3(PA_BLOCK), 0, c->stream, G, E, c->sc, sv, (const T*)r0, t, reg1);
-      hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg1, nblk, 2);
+      hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg1, nblk, (const double*)nullptr, 2);
     }
     {
       constexpr int XV = 16 / (int)sizeof(T);
@@ -558,7 +472,7 @@ static int bicg_run_t(pa_ctx* c, T* x, const T* rhs, double tol, int64_t max_it,
     if (fold && nblk <= PA_MAX_GRID)
       pend3 = nblk;
     else
-      hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg2, nblk, 3);
+      hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(PA_BLOCK), 0, c->stream, c->sc, reg2, nblk, (const double*)nullptr, 3);
     cur ^= 1;
     ++enq;
    }
@@ -605,56 +519,6 @@ __global__ void __launch_bounds__(PA_BLOCK) k_rows_to_sums(const SolverScalars* 
   for (int q = 0; q < ncol; ++q) {
     const double v = pa_reduce_partials(partials, nblk, ncol, q, sm);
     if (threadIdx.x == 0) sums[off + q] = v;
-  }
-}
-
-// the scalar steps of k_bicg_post, from all-reduced sums instead of partial rows.  stage 10: start (rho' = r0.r0,
-// first beta); 0: alpha; 12: stop test 1, omega, rho'; 3: stop test 2, next beta
-template <typename T>
-__global__ void k_bicg_logic(SolverScalars* sc, const double* __restrict__ sums, int stage) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  if (stage == 10) {
-    sc->rr = (double)(T)sums[1];
-    sc->rho_next = sc->rr;
-    sc->tol = (double)(T)sqrt((T)sc->rr);
-    T b = (T)sc->rho_next / (T)1.0;
-    b = b * (T)1.0;
-    b = b / (T)1.0;
-    sc->beta = (double)b;
-    sc->rho = sc->rho_next;
-    sc->done = 0;   // `while not finished`: at least one iteration
-    return;
-  }
-  if (sc->done) return;
-  if (stage == 0) {
-    sc->itr += 1;
-    T r0v = (T)sums[0];
-    T rho = (T)sc->rho;
-    sc->alpha = pa_nan_to_num<T>(rho / r0v);
-  } else if (stage == 12) {
-    T tol = (T)sqrt(sums[1]);
-    sc->tol = (double)tol;
-    if (isnan(tol) || isinf(tol)) { sc->err = 1; sc->done = 1; return; }
-    sc->finished_early = (sc->tol <= sc->tolerance) ? 1 : 0;
-    if (!sc->finished_early) {
-      T om = (T)pa_nan_to_num<T>((T)sums[2] / (T)sums[3]);
-      sc->omega = (double)om;
-      T rn = -om;
-      rn = rn * (T)sums[4];
-      sc->rho_next = (double)rn;
-    }
-  } else {
-    if (sc->finished_early) { sc->done = 1; return; }
-    T tol = (T)sqrt(sums[5]);
-    sc->tol = (double)tol;
-    if (isnan(tol) || isinf(tol)) { sc->err = 1; sc->done = 1; return; }
-    if (sc->tol <= sc->tolerance) sc->done = 1;
-    if (sc->itr >= sc->max_it) sc->done = 1;
-    T b = (T)sc->rho_next / (T)sc->rho;
-    b = b * (T)sc->alpha;
-    b = b / (T)sc->omega;
-    sc->beta = (double)b;
-    sc->rho = sc->rho_next;
   }
 }
 
@@ -780,7 +644,7 @@ int bicg_slab_st_t(pa_ctx* c) {
   T* sg_lo = g + 4 * pl;
   T* sg_hi = g + 5 * pl;
   double* part = (double*)c->scr[SCR_PART] + (size_t)PA_MAX_PARTIALS;
-  hipLaunchKernelGGL(k_bicg_logic<T>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)pa_sums(c), 0);   // alpha, itr
+  hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)nullptr, 0, (const double*)pa_sums(c), 0);   // alpha, itr
   Vec<T> rv = slab_vec<T>(c, r, c->r_recv_lo, c->r_recv_hi);
   Vec<T> vv = slab_vec<T>(c, vn, c->v_recv_lo, c->v_recv_hi);
   c->fold_a_n = 0;
@@ -818,7 +682,7 @@ int bicg_slab_x_t(pa_ctx* c) {
   T* s = (T*)c->scr[SCR_S];
   T* t = (T*)c->scr[SCR_TT];
   double* part = (double*)c->scr[SCR_PART] + 5 * (size_t)PA_MAX_PARTIALS;
-  hipLaunchKernelGGL(k_bicg_logic<T>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)pa_sums(c), 12);   // stop test 1, omega, rho'
+  hipLaunchKernelGGL(k_bicg_post<T>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)nullptr, 0, (const double*)pa_sums(c), 12);   // stop test 1, omega, rho'
   constexpr int XV = 16 / (int)sizeof(T);
   const bool vec = G.ncell % XV == 0 && ((((uintptr_t)x | (uintptr_t)pn | (uintptr_t)s | (uintptr_t)t | (uintptr_t)r) & 15) == 0);
   const T* vn = (const T*)c->scr[c->cur ? SCR_V0 : SCR_V1];   // v' of this iteration (s = r - alpha v' when s was not stored)
@@ -873,8 +737,8 @@ int pa_bicg_begin(pa_ctx* c, void* x, const void* rhs, double tol, int64_t max_i
 
 int pa_bicg_start(pa_ctx* c) {   // after the all-reduce of sums[1] = r0.r0
   if (int rc = pa_require_solve(c, PA_SOLVE_BICG, "pa_bicg_start")) return rc;
-  if (c->dtype == PA_F64) hipLaunchKernelGGL(k_bicg_logic<double>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)pa_sums(c), 10);
-  else hipLaunchKernelGGL(k_bicg_logic<float>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)pa_sums(c), 10);
+  if (c->dtype == PA_F64) hipLaunchKernelGGL(k_bicg_post<double>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)nullptr, 0, (const double*)pa_sums(c), 10);
+  else hipLaunchKernelGGL(k_bicg_post<float>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)nullptr, 0, (const double*)pa_sums(c), 10);
   PA_HIP(c, hipGetLastError());
   return PA_OK;
 }
@@ -901,8 +765,8 @@ int pa_bicg_bc(pa_ctx* c) {
 
 int pa_bicg_finish(pa_ctx* c) {
   if (int rc = pa_require_solve(c, PA_SOLVE_BICG, "pa_bicg_finish")) return rc;
-  if (c->dtype == PA_F64) hipLaunchKernelGGL(k_bicg_logic<double>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)pa_sums(c), 3);
-  else hipLaunchKernelGGL(k_bicg_logic<float>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)pa_sums(c), 3);
+  if (c->dtype == PA_F64) hipLaunchKernelGGL(k_bicg_post<double>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)nullptr, 0, (const double*)pa_sums(c), 3);
+  else hipLaunchKernelGGL(k_bicg_post<float>, dim3(1), dim3(1), 0, c->stream, c->sc, (const double*)nullptr, 0, (const double*)pa_sums(c), 3);
   c->cur ^= 1;
   PA_HIP(c, hipGetLastError());
   return PA_OK;

@@ -164,23 +164,14 @@ __global__ void __launch_bounds__(PA_BLOCK) k_slab_mid(DevGeom G, SolverScalars*
   const int done_in = sc->done;
   const double rr_in = sc->rr;
   const T beta = (T)sc->beta;
-  double v0 = 0.0;
-  for (int b = threadIdx.x; b < nrows; b += PA_BLOCK) v0 += rows[b];
-  if (done_in) return;
-  for (int off = 32; off > 0; off >>= 1) v0 += __shfl_down(v0, off, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v0;
-  __syncthreads();
+  double v[1];
+  if (!pa_fold_sums<1, 0>(rows, nrows, 1, 0, nullptr, 0, done_in, sm, v)) return;
   if (threadIdx.x == 0) {
-    double v = 0.0;
-    for (int w = 0; w < PA_BLOCK / 64; ++w) v += sm[w];
-    const T dAd = (T)v;                      // linalg.py:118-120
-    const T a = (T)rr_in / dAd;
-    const double al = (isnan(a) || isinf(a)) ? 0.0 : (double)a;
-    sm[4] = al;
+    const PaCgAlpha s = pa_step_cg_alpha<T>(v[0], rr_in);
+    sm[4] = s.alpha;
     if (blockIdx.x == 0) {
-      sc->dAd = (double)dAd;
-      sc->alpha = al;
-      sums[0] = v;
+      pa_put(sc, s);
+      sums[0] = v[0];
     }
   }
   __syncthreads();

@@ -55,167 +55,12 @@ __global__ void __launch_bounds__(256) k_cg2d(Cg3dArgs<T> A) {
 
   // ---- the scalar step folded into this kernel's prologue (k_cg3d, same code: every block reduces the partial
   //      rows the previous kernel left, in the same fixed order -> the same bits in every block) -----------------
-  T beta = (T)0, alpha = (T)0;
-  if ((PH == 0 || PH == 4) && A.pre_n > 0) {
-    __shared__ double pre_sm[16];
-    const SolverScalars* si = A.sc;
-    const int done_in = si->done;
-    const double rr_in = si->rr, beta_in = si->beta, tol_lim = si->tolerance;
-    const long long itr_in = si->itr, max_it = si->max_it;
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) {
-      if (PH == 0) v0 += A.pre_part[2 * (int64_t)b];
-      v1 += A.pre_part[2 * (int64_t)b + 1];
-    }
-    for (int b = threadIdx.x; b < A.pre_nsh; b += 256) v2 += A.pre_shell[b];
-    if (done_in) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) *A.sc_w = *si;
-      return;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      v0 += __shfl_down(v0, off, 64);
-      v1 += __shfl_down(v1, off, 64);
-      v2 += __shfl_down(v2, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      const int w = threadIdx.x >> 6;
-      pre_sm[3 * w] = v0;
-      pre_sm[3 * w + 1] = v1;
-      pre_sm[3 * w + 2] = v2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double rr = 0.0, dx2 = 0.0, sh = 0.0;
-      for (int w = 0; w < 4; ++w) { rr += pre_sm[3 * w]; dx2 += pre_sm[3 * w + 1]; sh += pre_sm[3 * w + 2]; }
-      const T rr_new = (T)rr;
-      const T tolv = (T)sqrt(dx2 + sh);
-      const bool bad = isnan(tolv) || isinf(tolv);   // linalg.py:334-336 raises before beta / itr
-      const T rr_old = (T)rr_in;
-      const double bq = bad ? beta_in : (double)(rr_new / rr_old);
-      const long long itr = itr_in + (bad ? 0 : 1);
-      const int done = (bad || itr > max_it || !((double)tolv > tol_lim)) ? 1 : 0;
-      pre_sm[12] = bq;
-      pre_sm[13] = done ? 1.0 : 0.0;
-      if (blockIdx.x == 0) {
-        SolverScalars* so = A.sc_w;
-        *so = *si;
-        so->tol = (double)tolv;
-        so->done = done;
-        if (bad) {
-          so->err = 1;
-        } else {
-          if (PH == 0) {
-            so->rr_old = (double)rr_old;
-            so->beta = bq;
-            so->rr = (double)rr_new;
-          }
-          so->itr = itr;
-        }
-        if (PH == 0) A.pre_sums[1] = rr;
-        A.pre_sums[2] = dx2 + sh;
-      }
-    }
-    __syncthreads();
-    if (pre_sm[13] != 0.0) return;
-    beta = (T)pre_sm[12];
-  } else if (PH == 1 && A.pre_n > 0) {
-    __shared__ double pre_sm[8];
-    const int done_in = A.sc->done;
-    const double rr_in = A.sc->rr;
-    double v0 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) v0 += A.pre_part[b];
-    if (done_in) return;
-    for (int off = 32; off > 0; off >>= 1) v0 += __shfl_down(v0, off, 64);
-    if ((threadIdx.x & 63) == 0) pre_sm[threadIdx.x >> 6] = v0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = 0.0;
-      for (int w = 0; w < 4; ++w) v += pre_sm[w];
-      const T dAd = (T)v;
-      const T a = (T)rr_in / dAd;
-      const double al = (isnan(a) || isinf(a)) ? 0.0 : (double)a;
-      pre_sm[4] = al;
-      if (blockIdx.x == 0) {
-        A.sc_w->dAd = (double)dAd;
-        A.sc_w->alpha = al;
-        A.pre_sums[0] = v;
-      }
-    }
-    __syncthreads();
-    alpha = (T)pre_sm[4];
-  } else if (PH == 8 && A.pre_n > 0) {
-    // BiCGSTAB: the step that closes the PREVIOUS iteration (k_cg3d phase 5 / 8 prologue, k_bicg_post stage 3)
-    __shared__ double pre_sm[8];
-    const SolverScalars* si = A.sc;
-    const int done_in = si->done, fe = si->finished_early;
-    const double tol_lim = si->tolerance, rho_next = si->rho_next, rho_in = si->rho, alpha_in = si->alpha,
-                 omega_in = si->omega;
-    const long long itr_in = si->itr, max_it = si->max_it;
-    double v0 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) v0 += A.pre_part[b];
-    if (done_in) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) *A.sc_w = *si;
-      return;
-    }
-    for (int off = 32; off > 0; off >>= 1) v0 += __shfl_down(v0, off, 64);
-    if ((threadIdx.x & 63) == 0) pre_sm[threadIdx.x >> 6] = v0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = 0.0;
-      for (int w = 0; w < 4; ++w) v += pre_sm[w];
-      const T tolv = (T)sqrt(v);
-      const bool bad = !fe && (isnan(tolv) || isinf(tolv));
-      int done = (fe || bad) ? 1 : 0;
-      T bq = (T)0;
-      if (!fe && !bad) {
-        if ((double)tolv <= tol_lim) done = 1;
-        if (itr_in >= max_it) done = 1;
-        bq = (T)rho_next / (T)rho_in;
-        bq = bq * (T)alpha_in;
-        bq = bq / (T)omega_in;
-      }
-      pre_sm[5] = done ? 1.0 : 0.0;
-      if (blockIdx.x == 0) {
-        SolverScalars* so = A.sc_w;
-        *so = *si;
-        so->done = done;
-        if (!fe) {
-          so->tol = (double)tolv;
-          if (bad) {
-            so->err = 1;
-          } else {
-            so->beta = (double)bq;
-            so->rho = rho_next;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (pre_sm[5] != 0.0) return;
-  } else if (PH == 6 && A.pre_n > 0) {
-    // BiCGSTAB: alpha = rho / (r0 . v) of THIS iteration, iteration count (k_bicg_post stage 0)
-    __shared__ double pre_sm[8];
-    const int done_in = A.sc->done;
-    const double rho_in = A.sc->rho;
-    double v0 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) v0 += A.pre_part[b];
-    if (done_in) return;
-    for (int off = 32; off > 0; off >>= 1) v0 += __shfl_down(v0, off, 64);
-    if ((threadIdx.x & 63) == 0) pre_sm[threadIdx.x >> 6] = v0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = 0.0;
-      for (int w = 0; w < 4; ++w) v += pre_sm[w];
-      const T q = (T)rho_in / (T)v;
-      const double al = (isnan(q) || isinf(q)) ? 0.0 : (double)q;  // linalg.py:302-305
-      pre_sm[4] = al;
-      if (blockIdx.x == 0) {
-        A.sc_w->itr += 1;   // no other block of this launch reads itr
-        A.sc_w->alpha = al;
-      }
-    }
-    __syncthreads();
-    alpha = (T)pre_sm[4];
+  T beta = (T)0, alpha = (T)0, omega = (T)0;   // (omega: no phase of this kernel uses it)
+  constexpr int FOLD = PH == 0 ? PA_FOLD_CG_CLOSE : PH == 4 ? PA_FOLD_JACOBI_CLOSE : PH == 1 ? PA_FOLD_CG_ALPHA
+                     : PH == 8 ? PA_FOLD_BICG_CLOSE : PA_FOLD_BICG_ALPHA;
+  if (A.pre_n > 0) {
+    __shared__ double pre_sm[(PH == 0 || PH == 4) ? 16 : 8];
+    if (pa_fold_prologue<T, FOLD>(A, pre_sm, alpha, beta, omega)) return;
   } else {
     if (A.sc->done) return;
     if (PH == 0) beta = (T)A.sc->beta;

@@ -30,6 +30,7 @@
 // The grid is exactly one resident wave of workgroups: chunks = capacity / tiles, so every
 // CU carries the same number of identical work items and nothing queues behind a tail.
 #include "pa_host.h"
+#include "pa_scalar_steps.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -329,178 +330,20 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
   issue(plane_of(0), wc, true);
   if (act0) issue(plane_of(1), w, CI > 1);
 
-  if ((PH == 0 || PH == 4) && A.pre_n > 0) {
-    // the scalar step that closes the PREVIOUS iteration (CG: linalg.py:128-141, 321-338; the Jacobi
-    // sweep has the stop test and the iteration count only).  Every load of
-    // the prologue is issued before the first wait -- one memory round trip (~1-2 us right after a
-    // kernel boundary), not one per reduction.  Summation order = pa_reduce_partials, column by column.
-    __shared__ double pre_sm[16];
-    const SolverScalars* si = A.sc;
-    const int done_in = si->done;
-    const double rr_in = si->rr, beta_in = si->beta, tol_lim = si->tolerance;
-    const long long itr_in = si->itr, max_it = si->max_it;
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) {
-      if (PH == 0) v0 += A.pre_part[2 * (int64_t)b];
-      v1 += A.pre_part[2 * (int64_t)b + 1];
+  // The scalar step folded into this kernel (pa_fold_prologue, pa_scalar_steps.h): phase A and the Jacobi sweep close
+  // the PREVIOUS iteration, phase B forms alpha of THIS one; BiCGSTAB: phases 5 / 8 close the previous iteration, phase
+  // 6 forms alpha.  Its loads -- the flag, the scalars, the partial rows -- go out behind the planes above, and all of
+  // them are waited for once.
+  constexpr int FOLD = PH == 0 ? PA_FOLD_CG_CLOSE : PH == 4 ? PA_FOLD_JACOBI_CLOSE : PH == 1 ? PA_FOLD_CG_ALPHA
+                     : (PH == 5 || PH == 8) ? PA_FOLD_BICG_CLOSE : PH == 6 ? PA_FOLD_BICG_ALPHA : -1;
+  const bool folded = FOLD >= 0 && A.pre_n > 0;
+  if constexpr (FOLD >= 0) {
+    if (folded) {
+      __shared__ double pre_sm[(PH == 0 || PH == 4) ? 16 : 8];
+      if (pa_fold_prologue<T, FOLD>(A, pre_sm, alpha, beta, omega)) return;
     }
-    for (int b = threadIdx.x; b < A.pre_nsh; b += 256) v2 += A.pre_shell[b];
-    if (done_in) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) *A.sc_w = *si;
-      return;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      v0 += __shfl_down(v0, off, 64);
-      v1 += __shfl_down(v1, off, 64);
-      v2 += __shfl_down(v2, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      const int w = threadIdx.x >> 6;
-      pre_sm[3 * w] = v0;
-      pre_sm[3 * w + 1] = v1;
-      pre_sm[3 * w + 2] = v2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double rr = 0.0, dx2 = 0.0, sh = 0.0;
-      for (int w = 0; w < 4; ++w) { rr += pre_sm[3 * w]; dx2 += pre_sm[3 * w + 1]; sh += pre_sm[3 * w + 2]; }
-      // pa_logic_b on registers: a local SolverScalars puts the kernel on scratch memory, and a kernel
-      // with a private segment costs ~10 us more to dispatch (measured)
-      const T rr_new = (T)rr;
-      const T tolv = (T)sqrt(dx2 + sh);
-      const bool bad = isnan(tolv) || isinf(tolv);   // linalg.py:334-336 raises before beta / itr
-      const T rr_old = (T)rr_in;
-      const double bq = bad ? beta_in : (double)(rr_new / rr_old);
-      const long long itr = itr_in + (bad ? 0 : 1);
-      const int done = (bad || itr > max_it || !((double)tolv > tol_lim)) ? 1 : 0;
-      pre_sm[12] = bq;
-      pre_sm[13] = done ? 1.0 : 0.0;
-      if (blockIdx.x == 0) {
-        SolverScalars* so = A.sc_w;
-        *so = *si;
-        so->tol = (double)tolv;
-        so->done = done;
-        if (bad) {
-          so->err = 1;
-        } else {
-          if (PH == 0) {
-            so->rr_old = (double)rr_old;
-            so->beta = bq;
-            so->rr = (double)rr_new;
-          }
-          so->itr = itr;
-        }
-        if (PH == 0) A.pre_sums[1] = rr;
-        A.pre_sums[2] = dx2 + sh;
-      }
-    }
-    __syncthreads();
-    if (pre_sm[13] != 0.0) return;
-    beta = (T)pre_sm[12];
-  } else if (PH == 1 && A.pre_n > 0) {
-    // alpha = r.r / d.Ad of THIS iteration (linalg.py:118-120); loads first, as above
-    __shared__ double pre_sm[8];
-    const int done_in = A.sc->done;
-    const double rr_in = A.sc->rr;
-    double v0 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) v0 += A.pre_part[b];
-    if (done_in) return;
-    for (int off = 32; off > 0; off >>= 1) v0 += __shfl_down(v0, off, 64);
-    if ((threadIdx.x & 63) == 0) pre_sm[threadIdx.x >> 6] = v0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = 0.0;
-      for (int w = 0; w < 4; ++w) v += pre_sm[w];
-      const T dAd = (T)v;
-      const T a = (T)rr_in / dAd;
-      const double al = (isnan(a) || isinf(a)) ? 0.0 : (double)a;
-      pre_sm[4] = al;
-      if (blockIdx.x == 0) {
-        A.sc_w->dAd = (double)dAd;
-        A.sc_w->alpha = al;
-        A.pre_sums[0] = v;
-      }
-    }
-    __syncthreads();
-    alpha = (T)pre_sm[4];
-  } else if ((PH == 5 || PH == 8) && A.pre_n > 0) {
-    // BiCGSTAB: the step that closes the PREVIOUS iteration (k_bicg_post stage 3; linalg.py:212-214,
-    // 236-262): early exit, stop test 2, next beta, rho <- rho_next.  Next state -> the other slot.
-    __shared__ double pre_sm[8];
-    const SolverScalars* si = A.sc;
-    const int done_in = si->done, fe = si->finished_early;
-    const double tol_lim = si->tolerance, rho_next = si->rho_next, rho_in = si->rho, alpha_in = si->alpha,
-                 omega_in = si->omega;
-    const long long itr_in = si->itr, max_it = si->max_it;
-    double v0 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) v0 += A.pre_part[b];
-    if (done_in) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) *A.sc_w = *si;
-      return;
-    }
-    for (int off = 32; off > 0; off >>= 1) v0 += __shfl_down(v0, off, 64);
-    if ((threadIdx.x & 63) == 0) pre_sm[threadIdx.x >> 6] = v0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = 0.0;
-      for (int w = 0; w < 4; ++w) v += pre_sm[w];
-      const T tolv = (T)sqrt(v);
-      const bool bad = !fe && (isnan(tolv) || isinf(tolv));
-      int done = (fe || bad) ? 1 : 0;
-      T bq = (T)0;
-      if (!fe && !bad) {
-        if ((double)tolv <= tol_lim) done = 1;
-        if (itr_in >= max_it) done = 1;
-        bq = (T)rho_next / (T)rho_in;
-        bq = bq * (T)alpha_in;
-        bq = bq / (T)omega_in;
-      }
-      pre_sm[4] = (double)bq;
-      pre_sm[5] = done ? 1.0 : 0.0;
-      if (blockIdx.x == 0) {
-        SolverScalars* so = A.sc_w;
-        *so = *si;
-        so->done = done;
-        if (!fe) {
-          so->tol = (double)tolv;
-          if (bad) {
-            so->err = 1;
-          } else {
-            so->beta = (double)bq;
-            so->rho = rho_next;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (pre_sm[5] != 0.0) return;
-    beta = (T)pre_sm[4];
-    omega = (T)omega_in;
-  } else if (PH == 6 && A.pre_n > 0) {
-    // BiCGSTAB: alpha = rho / (r0 . v) of THIS iteration, iteration count (k_bicg_post stage 0)
-    __shared__ double pre_sm[8];
-    const int done_in = A.sc->done;
-    const double rho_in = A.sc->rho;
-    double v0 = 0.0;
-    for (int b = threadIdx.x; b < A.pre_n; b += 256) v0 += A.pre_part[b];
-    if (done_in) return;
-    for (int off = 32; off > 0; off >>= 1) v0 += __shfl_down(v0, off, 64);
-    if ((threadIdx.x & 63) == 0) pre_sm[threadIdx.x >> 6] = v0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double v = 0.0;
-      for (int w = 0; w < 4; ++w) v += pre_sm[w];
-      const T q = (T)rho_in / (T)v;
-      const double al = (isnan(q) || isinf(q)) ? 0.0 : (double)q;  // linalg.py:302-305
-      pre_sm[4] = al;
-      if (blockIdx.x == 0) {
-        A.sc_w->itr += 1;   // no other block of this launch reads itr
-        A.sc_w->alpha = al;
-      }
-    }
-    __syncthreads();
-    alpha = (T)pre_sm[4];
-  } else {
+  }
+  if (!folded) {
     if (PH != 2 && PH != 3 && PH != 7 && A.sc->done) return;
     if (PH == 0) beta = (T)A.sc->beta;
     if (PH == 1) alpha = (T)A.sc->alpha;
@@ -1109,6 +952,7 @@ struct TileKernel {
   int* dbg;
   void (*label)(char* s, size_t n, const void* args);   // "k_sf phase 3 kind 5 RJ 2 (source)": called for a debug line only
   bool with_cus;      // the line ends in " x <CUs> CUs"
+  int bpc_max;        // > 0: the grid is sized for at most this many blocks / CU, whatever the occupancy query says
 };
 
 // Everything after "which kernel, which extents": tiles, chunks = capacity / tiles clamped to [1, n0] and capped by option
@@ -1119,6 +963,7 @@ static int launch_tiled(pa_ctx* c, const TileKernel& K, int64_t n1e, int64_t n2e
   if (!*K.bpc) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K.fn, 256, 0) != hipSuccess || n <= 0) n = K.bpc_fallback;
+    if (K.bpc_max > 0 && n > K.bpc_max) n = K.bpc_max;
     *K.bpc = n;
   }
   const int TJ = 4 * K.rj, TK = 64 * K.vec;
@@ -1162,11 +1007,16 @@ static int launch_cg3d(pa_ctx* c, Cg3dArgs<T>& A) {
     if (G.bct[3] != PA_BC_PERIODIC && n1e > 2) n1e -= 1;
     if (G.bct[5] != PA_BC_PERIODIC && n2e > 2) n2e -= 1;
   }
+  // The chunks of a launch -- and with them the grouping of its partial sums, i.e. the bits of tol -- follow the blocks / CU
+  // the occupancy query reports, which follows the register count.  One instantiation is held at the value its results
+  // were recorded with: the Jacobi sweep with a coefficient field, fp32, one cell per lane, one row per thread stood at 75
+  // VGPRs (6 blocks / CU) while its prologue still formed a beta no sweep uses; with the shared prologue it needs 71 (7).
+  constexpr int BPC_MAX = (sizeof(T) == 4 && RJ == 1 && (PHASE == 4 || PHASE == 9) && CF && LAY == 1) ? 6 : 0;
   static int bpc = 0, dbg = -1;
   static const TileKernel K = {(const void*)k_cg3d<T, RJ, PHASE, CF, KIND, LAY, STG>, RJ, LAY == 1 ? 1 : VecOf<T>::N, 2, &bpc, &dbg,
     [](char* s, size_t n, const void*) {
       snprintf(s, n, "k_cg3d phase %c%s%s", (char)('A' + PHASE), LAY == 1 ? " (narrow)" : (LAY == 2 ? " (pitched)" : ""), STG ? " (RK stage)" : "");
-    }, true};
+    }, true, BPC_MAX};
   return launch_tiled(c, K, n1e, n2e, &A, &A.tiles_j, true);
 }
 

@@ -670,16 +670,8 @@ __global__ void __launch_bounds__(NT) k_resident(DevGeom G, DevEq<T> E, ResArgs<
     if (!res_allreduce(S, A.parts, v1, red)) { timed_out = true; break; }
     receive(Hp);
     if (tid == 0) {
-      sc.rr = (double)(T)red[0];                 // k_cg_post_init
-      if (SOLVER == 2) {                         // linalg.py:201-212: rho' = r0.r0, tol0, the first beta = rho' / 1 * 1 / 1
-        sc.rho_next = sc.rr;
-        sc.tol = (double)(T)sqrt((T)sc.rr);
-        T b = (T)sc.rho_next / (T)1.0;
-        b = b * (T)1.0;
-        b = b / (T)1.0;
-        sc.beta = (double)b;
-        sc.rho = sc.rho_next;
-      }
+      if (SOLVER == 2) pa_logic_bicg_start<T>(&sc, red[0]);
+      else sc.rr = (double)(T)red[0];            // k_cg_post_init
     }
     __syncthreads();
   } while (0);
@@ -823,12 +815,7 @@ __global__ void __launch_bounds__(NT) k_resident(DevGeom G, DevEq<T> E, ResArgs<
       __syncthreads();
       publish(H3p);
       if (!res_allreduce(S, A.parts, v1, red)) { timed_out = true; break; }
-      if (tid == 0) {
-        sc.itr += 1;
-        T r0v = (T)red[0];
-        T rho = (T)sc.rho;
-        sc.alpha = pa_nan_to_num<T>(rho / r0v);
-      }
+      if (tid == 0) pa_logic_bicg_alpha<T>(&sc, red[0]);
       receive(H3p);
       __syncthreads();
       // s = r - alpha v' on every cell, own and halo, in place of r ; |s|^2
@@ -868,23 +855,7 @@ __global__ void __launch_bounds__(NT) k_resident(DevGeom G, DevEq<T> E, ResArgs<
         P3p[RES_M_P(m)] = tv;
       }
       if (!res_allreduce(S, A.parts, v4, red)) { timed_out = true; break; }
-      if (tid == 0) {
-        T tol = (T)sqrt(red[0]);
-        sc.tol = (double)tol;
-        if (isnan(tol) || isinf(tol)) {
-          sc.err = 1;
-          sc.done = 1;
-        } else {
-          sc.finished_early = (sc.tol <= sc.tolerance) ? 1 : 0;
-          if (!sc.finished_early) {
-            T om = (T)pa_nan_to_num<T>((T)red[1] / (T)red[2]);
-            sc.omega = (double)om;
-            T rn = -om;
-            rn = rn * (T)red[3];
-            sc.rho_next = (double)rn;
-          }
-        }
-      }
+      if (tid == 0) pa_logic_bicg_mid<T>(&sc, red[0], red[1], red[2], red[3]);
       __syncthreads();
       if (sc.err) break;
       // x += alpha p' (+ s omega) ; r = s - omega t ; |r|^2 ; BC fill (k_bicg_x, linalg.py:236-262)
@@ -917,26 +888,7 @@ __global__ void __launch_bounds__(NT) k_resident(DevGeom G, DevEq<T> E, ResArgs<
       }
       publish(Hp);
       if (!res_allreduce(S, A.parts, v1, red)) { timed_out = true; break; }
-      if (tid == 0) {   // k_bicg_post stage 3
-        if (sc.finished_early) {
-          sc.done = 1;
-        } else {
-          T tol = (T)sqrt(red[0]);
-          sc.tol = (double)tol;
-          if (isnan(tol) || isinf(tol)) {
-            sc.err = 1;
-            sc.done = 1;
-          } else {
-            if (sc.tol <= sc.tolerance) sc.done = 1;
-            if (sc.itr >= sc.max_it) sc.done = 1;
-            T b = (T)sc.rho_next / (T)sc.rho;
-            b = b * (T)sc.alpha;
-            b = b / (T)sc.omega;
-            sc.beta = (double)b;
-            sc.rho = sc.rho_next;
-          }
-        }
-      }
+      if (tid == 0) pa_logic_bicg_close<T>(&sc, red[0]);
       __syncthreads();
       if (sc.done) break;
       receive(Hp);

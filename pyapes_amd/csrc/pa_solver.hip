@@ -3,93 +3,17 @@
 // one-shot drivers' resident attempt and timed tail, the solve-state guard, and the method-neutral entry points.
 #include "pa_solver.h"
 
-// ---- CG: r = (b - A x) on S, d = r, partial sum r.r (linalg.py:98-107) ---------------
-template <typename T>
-__global__ void __launch_bounds__(PA_BLOCK) k_cg_init(DevGeom G, DevEq<T> E, Vec<T> xv,
-                                                       const T* __restrict__ rhs, T* __restrict__ r,
+// ---- the first residual: r = (b - A x) on S (0 elsewhere), d = r, partial sum r.r (linalg.py:98-107) ---------------
+// One loop, grid and partial sum; two choices.
+//   TERMS  A x from the generic term evaluation on xv; else from the array `ax`, where a tiled kernel left it (zero
+//          outside S; `ax` may be r itself) -- r, d and the sum r.r come out bit-identical either way.
+//   PITCH  r and d leave with a row pitch of ps1 cells, pad cells zero (the PITCH layout of the tiled phases,
+//          pa_cg3d_kernel.h: odd row lengths); else contiguous, d optional, with the send planes of a slab.
+template <typename T, bool TERMS, bool PITCH>
+__global__ void __launch_bounds__(PA_BLOCK) k_cg_init(DevGeom G, DevEq<T> E, Vec<T> xv, const T* rhs,
+                                                       const T* ax, T* r,   // (rhs and ax may be r)
                                                        T* __restrict__ d, T* __restrict__ send_lo,
-                                                       T* __restrict__ send_hi, double* __restrict__ partials) {
-  FieldAcc<T> acc{xv};
-  double s[1] = {0.0};
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < G.ncell;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    int64_t i, j, k;
-    pa_decode(G, idx, i, j, k);
-    T rv = (T)0;
-    if (pa_in_S(G, i, j, k)) {
-      T ax = pa_apply_terms<T>(G, E, acc, i, j, k, xv.p[idx]);
-      rv = rhs[idx] - ax;
-      T p = rv * rv;
-      s[0] += (double)p;
-    }
-    r[idx] = rv;
-    if (d) d[idx] = rv;
-    if (send_lo && i == 0) send_lo[j * G.s1 + k] = rv;
-    if (send_hi && i == G.n0 - 1) send_hi[j * G.s1 + k] = rv;
-  }
-  pa_block_reduce_store<1>(s, partials);
-}
-
-// the same, from A x already computed by the tiled kernel (zero outside S) and sitting in `r`: same
-// loop, same grid, same partial sums -- r, d and the sum r.r come out bit-identical to k_cg_init
-template <typename T>
-__global__ void __launch_bounds__(PA_BLOCK) k_cg_init_ax(DevGeom G, const T* __restrict__ rhs, T* __restrict__ r,
-                                                          T* __restrict__ d, T* __restrict__ send_lo,
-                                                          T* __restrict__ send_hi, double* __restrict__ partials) {
-  double s[1] = {0.0};
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < G.ncell;
-       idx += (int64_t)gridDim.x * blockDim.x) {
-    int64_t i, j, k;
-    pa_decode(G, idx, i, j, k);
-    T rv = (T)0;
-    if (pa_in_S(G, i, j, k)) {
-      rv = rhs[idx] - r[idx];
-      T p = rv * rv;
-      s[0] += (double)p;
-    }
-    r[idx] = rv;
-    if (d) d[idx] = rv;
-    if (send_lo && i == 0) send_lo[j * G.s1 + k] = rv;
-    if (send_hi && i == G.n0 - 1) send_hi[j * G.s1 + k] = rv;
-  }
-  pa_block_reduce_store<1>(s, partials);
-}
-
-// the same for the PITCH layout of the tiled CG phases (pa_cg3d_kernel.h, odd row lengths): A x arrives in a
-// contiguous scratch, r and d leave with a row pitch of ps1 cells, pad cells zero.  Same loop, grid and partial sums.
-template <typename T>
-__global__ void __launch_bounds__(PA_BLOCK) k_cg_init_ax_pitch(DevGeom G, const T* __restrict__ rhs, const T* __restrict__ ax,
-                                                                T* __restrict__ r, T* __restrict__ d, int64_t ps1,
-                                                                double* __restrict__ partials) {
-  double s[1] = {0.0};
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t idx = t0; idx < G.ncell; idx += stride) {
-    int64_t i, j, k;
-    pa_decode(G, idx, i, j, k);
-    T rv = (T)0;
-    if (pa_in_S(G, i, j, k)) {
-      rv = rhs[idx] - ax[idx];
-      T p = rv * rv;
-      s[0] += (double)p;
-    }
-    const int64_t o = (i * G.n1 + j) * ps1 + k;
-    r[o] = rv;
-    d[o] = rv;
-  }
-  const int64_t rows = G.n0 * G.n1, pw = ps1 - G.n2;
-  for (int64_t q = t0; q < rows * pw; q += stride) {
-    const int64_t o = (q / pw) * ps1 + G.n2 + q % pw;
-    r[o] = (T)0;
-    d[o] = (T)0;
-  }
-  pa_block_reduce_store<1>(s, partials);
-}
-
-// ... and with A x from the GENERIC term evaluation (axisymmetric meshes: no tiled A x), r / d (or r0 / r) pitched
-template <typename T>
-__global__ void __launch_bounds__(PA_BLOCK) k_cg_init_pitch(DevGeom G, DevEq<T> E, Vec<T> xv, const T* __restrict__ rhs,
-                                                             T* __restrict__ r, T* __restrict__ d, int64_t ps1,
-                                                             double* __restrict__ partials) {
+                                                       T* __restrict__ send_hi, int64_t ps1, double* __restrict__ partials) {
   FieldAcc<T> acc{xv};
   double s[1] = {0.0};
   const int64_t stride = (int64_t)gridDim.x * blockDim.x, t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -98,20 +22,31 @@ __global__ void __launch_bounds__(PA_BLOCK) k_cg_init_pitch(DevGeom G, DevEq<T> 
     pa_decode(G, idx, i, j, k);
     T rv = (T)0;
     if (pa_in_S(G, i, j, k)) {
-      T ax = pa_apply_terms<T>(G, E, acc, i, j, k, xv.p[idx]);
-      rv = rhs[idx] - ax;
+      T axv;
+      if constexpr (TERMS) axv = pa_apply_terms<T>(G, E, acc, i, j, k, xv.p[idx]);
+      else axv = ax[idx];
+      rv = rhs[idx] - axv;
       T p = rv * rv;
       s[0] += (double)p;
     }
-    const int64_t o = (i * G.n1 + j) * ps1 + k;
-    r[o] = rv;
-    d[o] = rv;
+    if constexpr (PITCH) {
+      const int64_t o = (i * G.n1 + j) * ps1 + k;
+      r[o] = rv;
+      d[o] = rv;
+    } else {
+      r[idx] = rv;
+      if (d) d[idx] = rv;
+      if (send_lo && i == 0) send_lo[j * G.s1 + k] = rv;
+      if (send_hi && i == G.n0 - 1) send_hi[j * G.s1 + k] = rv;
+    }
   }
-  const int64_t rows = G.n0 * G.n1, pw = ps1 - G.n2;
-  for (int64_t q = t0; q < rows * pw; q += stride) {
-    const int64_t o = (q / pw) * ps1 + G.n2 + q % pw;
-    r[o] = (T)0;
-    d[o] = (T)0;
+  if constexpr (PITCH) {
+    const int64_t rows = G.n0 * G.n1, pw = ps1 - G.n2;
+    for (int64_t q = t0; q < rows * pw; q += stride) {
+      const int64_t o = (q / pw) * ps1 + G.n2 + q % pw;
+      r[o] = (T)0;
+      d[o] = (T)0;
+    }
   }
   pa_block_reduce_store<1>(s, partials);
 }
@@ -258,12 +193,12 @@ int cg_residual_init(pa_ctx* c, const DevEq<T>& E, Vec<T> xv, const T* rhs, T* r
   if (!xt.ghi) xt.ghi = xt.p + (c->G.n0 - 1) * c->G.s0;
   int fr = (rhs != r && (const T*)xv.p != r) ? pa_tile3d_aop<T>(c, E, xt, r, 1) : 0;
   if (fr < 0) return fr;
-  if (fr > 0)
-    hipLaunchKernelGGL(k_cg_init_ax<T>, dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, rhs, r, d, send_lo, send_hi,
-                       part);
+  if (fr > 0)   // (A x sits in r)
+    hipLaunchKernelGGL((k_cg_init<T, false, false>), dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, rhs, (const T*)r,
+                       r, d, send_lo, send_hi, (int64_t)0, part);
   else
-    hipLaunchKernelGGL(k_cg_init<T>, dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, rhs, r, d, send_lo,
-                       send_hi, part);
+    hipLaunchKernelGGL((k_cg_init<T, true, false>), dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, rhs,
+                       (const T*)nullptr, r, d, send_lo, send_hi, (int64_t)0, part);
   return PA_OK;
 }
 
@@ -273,10 +208,11 @@ int cg_residual_init_pitch(pa_ctx* c, const DevEq<T>& E, Vec<T> xv, const T* rhs
   const int fr = pa_tile3d_aop<T>(c, E, xv, ax, 1);
   if (fr < 0) return fr;
   if (fr > 0) {
-    hipLaunchKernelGGL(k_cg_init_ax_pitch<T>, dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, rhs, (const T*)ax, r, d,
-                       c->cg_ps1, part);
+    hipLaunchKernelGGL((k_cg_init<T, false, true>), dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, rhs, (const T*)ax,
+                       r, d, (T*)nullptr, (T*)nullptr, c->cg_ps1, part);
   } else if (c->coord == PA_COORD_RZ) {   // no tiled A x with r rows: the generic term evaluation, once per solve
-    hipLaunchKernelGGL(k_cg_init_pitch<T>, dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, rhs, r, d, c->cg_ps1, part);
+    hipLaunchKernelGGL((k_cg_init<T, true, true>), dim3(nblk), dim3(PA_BLOCK), 0, c->stream, c->G, E, xv, rhs,
+                       (const T*)nullptr, r, d, (T*)nullptr, (T*)nullptr, c->cg_ps1, part);
   } else {   // the tiled A x declined: contiguous layout (the buffers are merely larger)
     c->cg_pitch = 0, c->cg_ps1 = 0;
   }

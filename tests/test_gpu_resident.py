@@ -132,6 +132,38 @@ def test_resident_matches_launch_per_phase(monkeypatch, method):
     assert taken >= ncases // 2
 
 
+def test_resident_bicgstab_beta_restated(monkeypatch):
+    """the last beta of a resident BiCGSTAB solve, restated from the scalars it was formed from in the mesh's precision and
+    the reference's order (linalg.py:212: rho' / rho * alpha / omega, rho = the rho one iteration earlier): the resident
+    loop applies the same step functions as the launch-per-phase kernels, and this pins the one they share"""
+    for n, dtype in (([12, 9, 17], "double"), ([16, 33], "single")):
+        bcs = [("dirichlet", 0.25), ("neumann", 0.1), ("dirichlet", -0.5), ("dirichlet", 0.0), ("neumann", -0.2), ("dirichlet", 1.0)][:2 * len(n)]
+        rhs, x0 = _fields(n, dtype, 4242)
+        f = np.float64 if dtype == "double" else np.float32
+        sp = None
+        for max_it in range(2, 9):   # (one beta may round alike in another order; seven in two precisions do not)
+            monkeypatch.setenv("PYAPES_HIP_RESIDENT", "1")
+            nd = len(n)
+            mesh = Mesh(Box([0.0] * nd, [1.0 + 0.1 * a for a in range(nd)]), None, list(n), "cuda", dtype)
+            cfg = [{"bc_face": FACES[i], "bc_type": t, "bc_val": v, "bc_val_opt": None} for i, (t, v) in enumerate(bcs)]
+            var = Field("p", 1, mesh, {"domain": cfg, "obstacle": None})
+            var.set_var_tensor(x0.cuda().clone())
+            s = Solver({"fdm": {"method": "bicgstab", "tol": -1.0, "max_it": max_it, "report": False}})
+            s.set_eq(-FDM().laplacian(0.8, var) == rhs.cuda().clone())
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                rep = s.solve()
+            ctx = context_for(mesh)
+            assert ctx.resident_used() > 0 and rep["itr"] == max_it, (n, dtype, rep)
+            sk = ctx.scalars()
+            if sp is not None:
+                beta = f(sk["rho_next"]) / f(sp["rho"])
+                beta = beta * f(sk["alpha"])
+                beta = beta / f(sk["omega"])
+                assert sk["beta"] == float(beta) and sk["rho"] == sk["rho_next"] and sk["beta"] != 0.0, (n, dtype, max_it, sk, sp)
+            sp = sk
+
+
 def test_resident_plan_and_layouts(monkeypatch):
     """box layouts: one workgroup, cuts along one / two / three axes, uneven boxes, the largest mesh the plan takes
     (64^3: boxes of 16 x 16 x 13 with a one-cell halo), and just above it (launch-per-phase loops)"""

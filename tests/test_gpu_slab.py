@@ -73,7 +73,8 @@ def _worker(rank, world, port, jobs, out):
                 rep = drv.solve(1e-30, K, poll=3)
             parts = [None] * world
             dist.all_gather_object(parts, var().cpu())
-            res[key] = {"x": torch.cat(parts, dim=1), "itr": int(rep.itr), "tol": float(rep.tol), "errors": errors}
+            res[key] = {"x": torch.cat(parts, dim=1), "itr": int(rep.itr), "tol": float(rep.tol), "errors": errors,
+                        "scalars": dict(drv.be.scalars())}
         if rank == 0:
             torch.save(res, out)
     finally:
@@ -93,6 +94,8 @@ def two_slabs(tmp_path_factory):
         # the per-axis BC pair kernels (what a large slab uses) / one launch per face instead of the fused fill
         jobs += [(f"{name}-pair", name, (24, 20, 132), K_IT, "double", {"bc_path": 1}),
                  (f"{name}-faces", name, (24, 20, 132), K_IT, "double", {"bc_path": 3})]
+    # BiCGSTAB on the stepwise driver (scalar steps from all-reduced sums), 1 .. K_IT iterations: the restated beta below
+    jobs += [(f"bicg-{k}", "mix", (12, 9, 11), k, "double", {}, "bicgstab", False) for k in range(1, K_IT + 1)]
     out = str(tmp_path_factory.mktemp("two_slabs") / "res.pt")
     spawn_ranks(_worker, lambda port: (2, port, jobs, out), 2)
     return torch.load(out)
@@ -139,6 +142,20 @@ def test_two_slabs_pair_bc_kernels(name, two_slabs):
     _check_against_oracle(plain, name, (24, 20, 132), "double")
     assert torch.equal(paired["x"], plain["x"])
     assert abs(paired["tol"] - plain["tol"]) <= 1e-12 * abs(plain["tol"])
+
+
+def test_two_slabs_bicgstab_beta_restated(two_slabs):
+    """the last beta of a two-slab BiCGSTAB solve, restated from the scalars it was formed from in the reference's order
+    (linalg.py:212: rho' / rho * alpha / omega, rho = the rho one iteration earlier): the slab steps form their state from
+    all-reduced sums through the same step functions as every other path, and this pins the one they share"""
+    for k in range(2, K_IT + 1):   # (one beta may round alike in another order; five do not)
+        last, prev = two_slabs[f"bicg-{k}"], two_slabs[f"bicg-{k - 1}"]
+        assert last["itr"] == k and prev["itr"] == k - 1
+        sk, sp = last["scalars"], prev["scalars"]
+        beta = sk["rho_next"] / sp["rho"]     # (fp64 mesh: Python floats round as the mesh does)
+        beta = beta * sk["alpha"]
+        beta = beta / sk["omega"]
+        assert sk["beta"] == beta and sk["rho"] == sk["rho_next"] and sk["beta"] != 0.0, (k, sk, sp)
 
 
 @pytest.mark.parametrize("method,kind", [("bicgstab", "BiCGSTAB"), ("jacobi", "Jacobi")])
