@@ -73,9 +73,36 @@ def test_cg2d_vs_one_plane_tiling_and_oracle(name, n, dtype, faces, K):
 
 
 def test_cg2d_is_the_default_on_large_meshes_and_deterministic():
-    """2048 x 1024 (2 M cells) takes the marching kernel by default; two runs give the same bits, and the converged
-    solution of the reference's 2-D Poisson problem (poisson_bcs(2), tests/test_solver.py:34) is the exact one"""
-    from pyapes_amd.testing.poisson import poisson_bcs, poisson_exact_nd, poisson_rhs_nd
+    """2048 x 1024 (2 M cells) takes the marching kernel by default.  On the reference's 2-D Poisson problem (poisson_bcs(2),
+    tests/test_solver.py:34): two runs of 61 iterations give the same bits and a finite result; a run of 4 iterations
+    (max_it 3) equals the oracle's to 1e-10, with its iteration count, and the one-plane tiling of k_cg3d (cg2d_mincells -1)
+    to 1e-12, the bound of test_cg2d_vs_one_plane_tiling_and_oracle"""
+    from pyapes_amd.testing.poisson import poisson_bcs, poisson_rhs_nd
+    short = {}
+    for mincells in (None, -1):
+        mesh = Mesh(Box([0.0, 0.0], [1.0, 1.0]), None, [2048, 1024], "cuda", "double")
+        ctx = context_for(mesh)
+        if mincells is not None:
+            ctx.set_option("cg2d_mincells", mincells)
+            ctx.set_option("resident", False)
+        var = Field("p", 1, mesh, {"domain": poisson_bcs(2), "obstacle": None})
+        rhs = poisson_rhs_nd(mesh, var)
+        rhs0 = rhs.cpu().clone()
+        s = Solver({"fdm": {"method": "cg", "tol": 1e-30, "max_it": 3, "report": False}})
+        s.set_eq(FDM().laplacian(1.0, var) == rhs)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            rep = s.solve()
+        short[mincells] = (var().cpu(), rep, ctx.scalars())
+    om = O.OMesh([0.0, 0.0], [1.0, 1.0], [2048, 1024], "double")
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        xo, ro = O.solve_poisson(om, O.poisson_cfg(2), rhs0.clone(), method="cg", tol=1e-30, max_it=3)
+    assert short[None][1]["itr"] == short[-1][1]["itr"] == ro["itr"] == 4
+    assert rel_err(short[None][0], xo) < 1e-10, rel_err(short[None][0], xo)
+    assert rel_err(short[None][0], short[-1][0]) < 1e-12, rel_err(short[None][0], short[-1][0])
+    for key in ("alpha", "beta", "tol"):
+        assert abs(short[None][2][key] - short[-1][2][key]) <= 1e-10 * abs(short[-1][2][key]), key
     out = []
     for _ in range(2):
         mesh = Mesh(Box([0.0, 0.0], [1.0, 1.0]), None, [2048, 1024], "cuda", "double")
