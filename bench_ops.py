@@ -5,7 +5,8 @@ adv-diff Euler march (BASELINE config 4), the SSP Runge-Kutta march beside its u
 march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step composition, the marches with a source term
 (--sections source) beside the three-launch workaround and the generic kernel, the marches in a velocity field (--sections
 velocity) beside the one-speed marches and the generic kernel, the momentum march of a vector field (--sections momentum)
-beside three scalar marches in three frozen fields, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+beside three scalar marches in three frozen fields, the Euler step with a diffusivity field (--sections nu) beside the
+constant-nu step and its torch composition, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -68,7 +69,9 @@ def main():
                          "and speed-tensor marches; not in the default list; velocity_baseline: the no-velocity rows alone, which a "
                          "library without the velocity entry points can run), momentum (momentum_march orders 1 and 3: the default, "
                          "vself 0, fastpath 0; not in the default list; momentum_baseline: the yardstick alone, three scalar rk_march "
-                         "calls in three velocity fields, which a library without pa_momentum_march can run), small (the reference's "
+                         "calls in three velocity fields, which a library without pa_momentum_march can run), nu (the Euler step with a diffusivity field at 256^3 and "
+                         "512^3 fp32: tiled, generic, the constant-nu step and the torch composition; not in the default list), "
+                         "small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
     sections = set(args.sections.split(","))
@@ -126,7 +129,72 @@ def main():
         velocity_rows(q, emit, with_velocity="velocity" in sections)
     if sections & {"momentum", "momentum_baseline"}:
         momentum_rows(q, emit, with_momentum="momentum" in sections)
+    if "nu" in sections:
+        nu_rows(q, emit)
     solver_rows(q, emit, sections)
+
+
+def nu_rows(q, emit):
+    """The Euler step with a diffusivity FIELD, div(nu grad phi) - upwind div(u phi), u = 0.7, all-dirichlet faces, fp32, on a
+    pre-allocated output (step kernel + BC fill per call): the tiled k_sfn, the generic k_euler (option sf 0), the constant-nu step
+    on k_sf on the same mesh (one array fewer: a floor) and the torch composition of the same term -- rolls and elementwise
+    operations plus apply_bcs, what a caller has to write without the feature.  Every variant is timed three times in
+    alternation; ms is the median, ms_all the three."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip import lib as L
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import homogeneous_bcs
+    for n in ((128,) if q else (256, 512)):
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", "single")
+        phi = Field("phi", 1, mesh, {"domain": homogeneous_bcs(3, 0.0, "dirichlet"), "obstacle": None})
+        phi.set_var_tensor(torch.exp(-((mesh.X - 0.5) ** 2 + (mesh.Y - 0.5) ** 2 + (mesh.Z - 0.5) ** 2) / 0.02)
+                           .unsqueeze(0).contiguous())
+        phi.apply_bcs()
+        ctx = context_for(mesh)
+        ctx.bind_bcs(phi(), phi.bcs, 0)
+        g = torch.Generator(device="cuda").manual_seed(0)
+        nu = (1e-3 * (0.5 + torch.rand((n, n, n), generator=g, device="cuda", dtype=torch.float32))).contiguous()
+        dx = float(mesh.dx_list[0])
+        dt, u = 0.2 * min(dx * dx / (6 * 1.5e-3), dx / 1.0), 0.7
+        x, out = phi()[0], torch.empty_like(phi()[0])
+        w, ih = 0.5 / (dx * dx), 1.0 / dx
+        scratch = Field("t", 1, mesh, {"domain": homogeneous_bcs(3, 0.0, "dirichlet"), "obstacle": None})
+
+        def torch_step():
+            d = torch.zeros_like(x)
+            adv = torch.zeros_like(x)
+            for a in range(3):
+                fp = torch.roll(x, -1, a) - x
+                fm = x - torch.roll(x, 1, a)
+                d = d + ((torch.roll(nu, -1, a) + nu) * fp - (nu + torch.roll(nu, 1, a)) * fm) * w
+                adv = adv + (u * fm) * ih
+            scratch.set_var_tensor((x + dt * (d - adv)).unsqueeze(0))
+            scratch.apply_bcs()
+
+        def tiled():
+            ctx.step_nu(x, None, out, 0.0, 0.0, L.OP_DIV_UPWIND, u, nu, dt)
+
+        def generic():
+            ctx.set_option("sf", 0)
+            ctx.step_nu(x, None, out, 0.0, 0.0, L.OP_DIV_UPWIND, u, nu, dt)
+            ctx.set_option("sf", 1)
+
+        def constant():
+            ctx.euler_step(x, out, L.OP_DIV_UPWIND, u, 1e-3, dt)
+
+        rows = [("nu-field step, tiled k_sfn", tiled, 3, 100), ("nu-field step, generic k_euler (sf 0)", generic, 3, 100),
+                ("constant-nu step, k_sf (yardstick: one array fewer)", constant, 2, 100),
+                ("torch composition of the nu-field step (rolls + elementwise + apply_bcs)", torch_step, 3, 10)]
+        ms = {name: [] for name, *_ in rows}
+        for _ in range(3):
+            for name, fn, _, iters in rows:
+                ms[name].append(timed(fn, iters if n <= 256 else max(iters // 4, 5)))
+        for name, _, passes, _ in rows:
+            emit(f"{name} {n}^3 f32 upwind u 0.7, dirichlet", n ** 3, sorted(ms[name])[1], passes, 4, {"ms_all": ms[name]})
+        assert bool(torch.isfinite(out).all())
+        del phi, scratch, mesh, ctx, nu, x, out
 
 
 def euler_rows(q, emit):

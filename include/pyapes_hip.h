@@ -366,6 +366,49 @@ int pa_momentum_march(pa_ctx* ctx, void* U, void* w1, void* w2, int ncomp, int o
                       const pa_velocity* frozen, double nu, double dt, int64_t nsteps, int* final, const pa_source* src,
                       const pa_bc_values* bcv);
 
+/* ---- diffusivity field: div(nu grad phi) with nu per node in the place of nu lap(phi) (new, defined by this library; the
+ * reference has no counterpart).  Conservative form, the diffusivity averaged onto the faces.  Per active mesh axis a, every
+ * operation rounded on its own in the grid dtype, no FMA:
+ *     ih = fl(1/dx_a);  w = ih*ih;  w = 0.5*w                                   (formed once)
+ *     nup = nu[+1]_a + nu;   num = nu + nu[-1]_a;   fp = x[+1]_a - x;   fm = x - x[-1]_a
+ *     t = nup*fp;  s = num*fm;  t = t - s;  t = t*w;  d = d + t                 (d starts at +0, axes ascending)
+ * and on the interior set   a = d - adv;  [a = a + s;]  a = dt*a;  v = phi + a,   then the ordered BC fill; a stage is
+ * B( c0*phi0 + c1*E(phi_s) ) as everywhere.  Neighbours wrap around on every axis.  The step reads the BC-filled face values of
+ * its input -- not the Neumann 2/3 rows of the Laplacian -- and nu at every node the stencil touches, boundary nodes included:
+ * nu has no BCs of its own.  nu is FROZEN for the call.  A march with a diffusivity field fills the BCs after every step and
+ * stage (no BC-on-load form); with a periodic face a stage is step, combination, fill.
+ * Three entry points carry it, each the union of its siblings' arguments plus a trailing diffusivity:
+ *   pa_step_nu            the Euler step (phi0 == NULL; c0, c1 not read) or the stage out = B( c0*phi0 + c1*E(phi) ), with one
+ *                         speed u / u_field (vel == NULL; u_field == phi: self-advection) or a velocity (u, u_field not read)
+ *   pa_march_nu           nsteps steps of order 1 | 2 | 3 over phi, w1, w2 (order 1: w2 may be NULL); *final names the buffer
+ *                         with the result.  vel != NULL: a frozen velocity; else self != 0: the field advects itself, every
+ *                         launch by its own input; else the frozen speed u / u_field
+ *   pa_momentum_march_nu  pa_momentum_march with one diffusivity field for every component
+ * dif == NULL or has == 0 IS the sibling -- pa_euler_step_src / pa_rk_stage_src / pa_euler_step_vel / pa_rk_stage_vel,
+ * pa_rk_march_src (order 1 without w2: pa_euler_march_src) / pa_rk_march_self_src / pa_rk_march_vel, pa_momentum_march: the
+ * same checks, kernel instantiations and bits.  With a field the scalar `nu` is NOT read, and
+ *     PA_E_ARG    field == NULL; a field equal to or overlapping a buffer of the call (input, output, w1, w2, phi0);
+ *                 PA_OP_DIV_UPWIND_COMPAT; an axisymmetric mesh; plus the refusals of the source and the velocity
+ *     PA_E_STATE  slab mode
+ * and the context stays usable after either.  Kernels: the upwind step and stage with ONE SCALAR speed (u == 0: pure
+ * heterogeneous diffusion) on a 3-D mesh with whole 16-byte rows, aligned operands, more than 4 rows and a BC on every face run
+ * tiled on k_sfn (pa_sfn_kernel.h: two marching fields, two rows per wave), bit-identical to the generic kernel; option "sf" 0
+ * sends them to it.  Everything else -- a speed field, a velocity, self-advection, QUICK, minmod, mc, central, a source, 1-D /
+ * 2-D, odd rows, unaligned operands -- runs the NU instantiations of the generic k_euler. */
+typedef struct {
+  int32_t has;        /* 0: no diffusivity field (the scalar nu is used: the sibling call) */
+  const void* field;  /* nu per node: a field of the grid's shape and dtype */
+} pa_diffusivity;
+int pa_step_nu(pa_ctx* ctx, const void* phi, const void* phi0, void* out, double c0, double c1, int div_kind, double u,
+               const void* u_field, const pa_velocity* vel, double nu, double dt, const pa_source* src,
+               const pa_diffusivity* dif);
+int pa_march_nu(pa_ctx* ctx, void* phi, void* w1, void* w2, int order, int div_kind, double u, const void* u_field,
+                const pa_velocity* vel, int self, double nu, double dt, int64_t nsteps, int* final, const pa_source* src,
+                const pa_diffusivity* dif);
+int pa_momentum_march_nu(pa_ctx* ctx, void* U, void* w1, void* w2, int ncomp, int order, int div_kind,
+                         const pa_velocity* frozen, double nu, double dt, int64_t nsteps, int* final, const pa_source* src,
+                         const pa_bc_values* bcv, const pa_diffusivity* dif);
+
 /* ---- vector steps for a host-stepped solver loop (pyapes_amd/solver/host_stepped.py: BC callables that read the iterate
  * make the reference's loop come back to Python for every face of every fill, bcs.py:200-253; the loop's AXPYs and dot
  * products between those fills are these).  Fields of the grid's shape and dtype.

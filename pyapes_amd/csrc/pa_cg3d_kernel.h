@@ -108,6 +108,10 @@ struct Cg3dArgs {
   T vel_v[3];
   // VEL 3 (pa_sf_vself.hip): the internal axis whose speed field IS the field `d` -- its speed is the centre operand
   int vel_own;
+  // diffusivity field of the Euler step (k_sfn, pa_sfn_kernel.h): nu per node, a second field with stencil reach, and
+  // w_a = 0.5 * (ih_a * ih_a) per INTERNAL axis; behind everything else for the same reason
+  const T* nu_f;
+  T nu_w[3];
 };
 
 __device__ __forceinline__ int pa_xcd_remap(int b, int nb) {

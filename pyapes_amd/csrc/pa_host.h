@@ -351,7 +351,7 @@ struct StepAdv {
 template <typename T>
 struct StepStage { const T* phi0; double c0, c1; };
 // one Euler step / stage as step_t (pa_march.hip) asks the tiled layer for it.  src: the source term (pa_*_src) or null;
-// bcl: the "BC on load" form (pa_sf_kernel.h)
+// bcl: the "BC on load" form (pa_sf_kernel.h); nu_field: the diffusivity field (pa_*_nu; nu is then not read) or null
 template <typename T>
 struct StepRequest {
   StepAdv adv;
@@ -359,6 +359,7 @@ struct StepRequest {
   StepStage<T> stage;
   const pa_source* src;
   bool bcl;
+  const void* nu_field;
 };
 // The step on a tiled kernel (pa_sf.hip): k_sfq for the kinds with a reach of 2 (QUICK, minmod, mc), k_sf with a velocity,
 // else k_sf or k_cg3d's Euler phase.  Blocks launched; 0 when no tiled kernel takes the launch (the generic k_euler then

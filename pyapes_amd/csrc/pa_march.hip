@@ -1,6 +1,7 @@
 // pa_march.hip -- the explicit march: the generic Euler step / Runge-Kutta stage kernel, ONE step routine (step_t) that
 // every entry point goes through, ONE buffer rotation (march_t) that every march is a callable of, and the pa_euler_* /
-// pa_rk_* / pa_momentum_march entry points.  The tiled kernels (pa_sf*.hip, pa_sfq*.hip) take over where they apply.
+// pa_rk_* / pa_momentum_march entry points and their forms with a diffusivity field (pa_step_nu, pa_march_nu,
+// pa_momentum_march_nu).  The tiled kernels (pa_sf*.hip, pa_sfq*.hip, pa_sfn.hip) take over where they apply.
 #include "pa_host.h"
 
 #include <stdlib.h>
@@ -24,6 +25,42 @@ template <typename T> struct EulerSrc<T, true> { const T* f; T val; };
 // read; the instantiations without it are the code they were
 template <typename T, bool VEL> struct EulerVel {};
 template <typename T> struct EulerVel<T, true> { const T* f[3]; T val[3]; int kind; };
+
+// NU: a diffusivity field (pa_*_nu) -- the conservative term div(nu grad phi) of pa_nu_term below stands where nu * lap stood,
+// Elap's rows and the scalar nu are not read; the instantiations without it are the code they were
+template <typename T, bool NU> struct EulerNu {};
+template <typename T> struct EulerNu<T, true> { const T* f; T w[3]; };
+
+// d = (+0) + t_0 + t_1 + t_2 over the active axes, nu averaged onto the two faces of axis a (the 1/2 sits in w_a):
+//   nup = nu[+1] + nu;  num = nu + nu[-1];  fp = x[+1] - x;  fm = x - x[-1];  t = nup*fp;  s = num*fm;  t = t - s;  t = t * w_a
+// with w_a = 0.5 * (ih_a * ih_a), ih_a = fl(1 / dx_a), formed on the host in T.  Neighbours wrap around on every axis; nu is read
+// at every node the stencil touches, boundary nodes included, and x through the BC-filled face values (no Neumann 2/3 rows).
+template <typename T>
+__device__ __forceinline__ T pa_nu_term(const DevGeom& G, const EulerNu<T, true>& D, const FieldAcc<T>& acc, int64_t i, int64_t j,
+                                        int64_t k, T xc) {
+  const T nc = D.f[i * G.s0 + j * G.s1 + k];
+  T d = (T)0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (!G.act[a]) continue;
+    T xp, xm;
+    pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
+    int64_t ii = i, jj = j, kk = k, i2 = i, j2 = j, k2 = k;
+    if (a == 0) { ii = pa_wrap(i + 1, G.n0); i2 = pa_wrap(i - 1, G.n0); }
+    if (a == 1) { jj = pa_wrap(j + 1, G.n1); j2 = pa_wrap(j - 1, G.n1); }
+    if (a == 2) { kk = pa_wrap(k + 1, G.n2); k2 = pa_wrap(k - 1, G.n2); }
+    T nup = D.f[ii * G.s0 + jj * G.s1 + kk] + nc;
+    T num = nc + D.f[i2 * G.s0 + j2 * G.s1 + k2];
+    T fp = xp - xc;
+    T fm = xc - xm;
+    T t = nup * fp;
+    T s = num * fm;
+    t = t - s;
+    t = t * D.w[a];
+    d = d + t;
+  }
+  return d;
+}
 
 // adv = (+0) + t_0 + t_1 + t_2 over the active axes: the per-axis term of pa_apply_terms' scheme `kind` (central, QUICK,
 // minmod / mc, upwind), operation for operation, with axis a's own speed W.f[a] / W.val[a] in the place of the one speed
@@ -119,10 +156,10 @@ __device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd
 
 // TVD: the advection term is a slope-limited scheme, PA_OP_DIV_MINMOD / _MC (pa_device.h pa_tvd_halves) -- instantiations of
 // their own, so that the kernels of every other scheme are the code they were
-template <typename T, bool STG = false, bool SRC = false, bool VEL = false, bool TVD = false>
+template <typename T, bool STG = false, bool SRC = false, bool VEL = false, bool TVD = false, bool NU = false>
 __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, DevEq<T> Eadv, Vec<T> pv,
                                                      T* __restrict__ out, T nu, T dt, EulerStage<T, STG> S = {},
-                                                     EulerSrc<T, SRC> Q = {}, EulerVel<T, VEL> W = {}) {
+                                                     EulerSrc<T, SRC> Q = {}, EulerVel<T, VEL> W = {}, EulerNu<T, NU> D = {}) {
   FieldAcc<T> acc{pv};
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < G.ncell;
        idx += (int64_t)gridDim.x * blockDim.x) {
@@ -131,11 +168,15 @@ __global__ void __launch_bounds__(PA_BLOCK) k_euler(DevGeom G, DevEq<T> Elap, De
     T pc = pv.p[idx];
     T v = pc;
     if (pa_in_S(G, i, j, k)) {
-      T lap = pa_apply_terms<T>(G, Elap, acc, i, j, k, pc);
+      T lap;
+      if constexpr (NU) lap = pa_nu_term<T>(G, D, acc, i, j, k, pc);
+      else lap = pa_apply_terms<T>(G, Elap, acc, i, j, k, pc);
       T adv;
       if constexpr (VEL) adv = pa_adv_vel<T, TVD>(G, Elap.grd, W, acc, i, j, k, pc);
       else adv = pa_apply_terms<T, TVD>(G, Eadv, acc, i, j, k, pc);
-      T a = nu * lap;
+      T a;
+      if constexpr (NU) a = lap;   // the diffusivity is inside the term
+      else a = nu * lap;
       a = a - adv;
       if constexpr (SRC) {
         const T s = Q.f ? Q.f[idx] : Q.val;
@@ -178,10 +219,11 @@ static bool step_dbg(int* left, int budget) {
 // The Euler step or the fused stage, in -> out, on the path that takes it: a tiled kernel (pa_tile3d_step: k_sfq, k_sf, k_cg3d),
 // else the generic k_euler; then the ordered BC fill.  bcl: the "BC on load" form of a march
 // (pa_sf_kernel.h) -- the step kernel alone, no fill behind it, the boundary nodes of `out` stay whatever they were; the answer is
-// PA_STEP_DECLINED when that form does not apply here.
+// PA_STEP_DECLINED when that form does not apply here.  nuf: the diffusivity field (pa_*_nu) -- div(nu grad phi) in the place of
+// nu * lap, `nu` is not read; never with bcl.
 template <typename T>
 static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu, double dt, const StepStage<T>& stage,
-                  const pa_source* src, bool bcl = false) {
+                  const pa_source* src, bool bcl = false, const void* nuf = nullptr) {
   const T* phi0 = stage.phi0;
   const pa_velocity* vel = adv.vel;
   if (phi0 && !bcl) {
@@ -194,9 +236,9 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
     bool periodic = false;
     for (int f = 0; f < 6; ++f) periodic = periodic || (c->G.act[f >> 1] && c->bc[f].type == PA_BC_PERIODIC);
     if (periodic) {
-      if (int rc = step_t<T>(c, in, out, adv, nu, dt, {nullptr, 0.0, 0.0}, src)) return rc;   // the source enters in the step only
+      if (int rc = step_t<T>(c, in, out, adv, nu, dt, {nullptr, 0.0, 0.0}, src, false, nuf)) return rc;   // the source enters in the step only
       static int dbg = -1;
-      if (!vel && step_dbg(&dbg, 8))
+      if (!vel && !nuf && step_dbg(&dbg, 8))
         fprintf(stderr, "[pyapes_hip] k_rk_combine (RK stage, periodic face): Euler step, then %lld cells in place\n", (long long)c->G.ncell);
       if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);
       hipLaunchKernelGGL(k_rk_combine<T>, dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, out, phi0, (T)stage.c0,
@@ -217,13 +259,18 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
   if (c->profile) (void)hipEventRecord(c->pev[0], c->stream);   // slot 0: the step kernel (without its BC fill)
   // the tiled layer first: k_sfq (QUICK, minmod, mc), k_sf, k_cg3d's Euler phase; 0: none of them takes the launch
   // (a source: the SRC instantiations of k_sf / k_sfq or the generic kernel -- k_cg3d's Euler phase takes none)
-  const int fr = pa_tile3d_step<T>(c, pv, out, StepRequest<T>{adv, nu, dt, stage, src, bcl});
+  const int fr = pa_tile3d_step<T>(c, pv, out, StepRequest<T>{adv, nu, dt, stage, src, bcl, nuf});
   if (fr < 0) return fr;
   if (fr == 0 && bcl) return PA_STEP_DECLINED;
   if (fr == 0) {
     static int dbg_vel = -1, dbg_src = -1, dbg_stg = -1;   // (source, velocity: one budget for every mesh and both forms, larger than an instantiation's 8)
     const long long nc = (long long)c->G.ncell;
-    if (vel) {
+    static int dbg_nu = -1;
+    if (nuf) {
+      if (step_dbg(&dbg_nu, 64))
+        fprintf(stderr, "[pyapes_hip] k_euler%s%s%s (diffusivity field): generic kernel, %lld cells\n", phi0 ? " (RK stage)" : "", src ? " (source)" : "",
+                vel ? " (velocity)" : "", nc);
+    } else if (vel) {
       if (step_dbg(&dbg_vel, 64)) fprintf(stderr, "[pyapes_hip] k_euler%s%s (velocity): generic kernel, %lld cells\n", phi0 ? " (RK stage)" : "", src ? " (source)" : "", nc);
     } else if (src) {
       if (step_dbg(&dbg_src, 64)) fprintf(stderr, "[pyapes_hip] k_euler%s (source): generic kernel, %lld cells\n", phi0 ? " (RK stage)" : "", nc);
@@ -242,10 +289,21 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
       with_bool(src != nullptr, [&](auto sc) {
         with_bool(vel != nullptr, [&](auto vl) {
          with_bool(adv.kind == PA_OP_DIV_MINMOD || adv.kind == PA_OP_DIV_MC, [&](auto tv) {
+          with_bool(nuf != nullptr, [&](auto nf) {
           constexpr bool STG = decltype(stg)::value, SRC = decltype(sc)::value, VEL = decltype(vl)::value, TVD = decltype(tv)::value;
+          constexpr bool NU = decltype(nf)::value;
           EulerStage<T, STG> S;
           EulerSrc<T, SRC> Q;
           EulerVel<T, VEL> W;
+          EulerNu<T, NU> D;
+          if constexpr (NU) {   // w_a = 0.5 * (ih_a * ih_a), each operation rounded in T
+            D.f = (const T*)nuf;
+            for (int a = 0; a < 3; ++a) {
+              T w = El.grd.ih[a] * El.grd.ih[a];
+              w = (T)0.5 * w;
+              D.w[a] = w;
+            }
+          }
           if constexpr (STG) S = {phi0, (T)stage.c0, (T)stage.c1};
           if constexpr (SRC) Q = {(const T*)src->field, (T)src->value};
           if constexpr (VEL) {
@@ -253,8 +311,9 @@ static int step_t(pa_ctx* c, const T* in, T* out, const StepAdv& adv, double nu,
             W.kind = adv.kind;
           }
           // (with a velocity El stands in for Eadv: unread)
-          hipLaunchKernelGGL((k_euler<T, STG, SRC, VEL, TVD>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G,
-                             El, VEL ? El : Ea, pv, out, (T)nu, (T)dt, S, Q, W);
+          hipLaunchKernelGGL((k_euler<T, STG, SRC, VEL, TVD, NU>), dim3(pa_grid_blocks(c->G.ncell)), dim3(PA_BLOCK), 0, c->stream, c->G,
+                             El, VEL ? El : Ea, pv, out, (T)nu, (T)dt, S, Q, W, D);
+          });
          });
         });
       });
@@ -349,13 +408,25 @@ static int march_vel_t(pa_ctx* c, void* const b[3], int order, int kind, const p
   });
 }
 
+// pa_march_nu with a diffusivity field: step_t directly, a BC fill behind every step and stage (there is no BC-on-load form of
+// the term).  vel null: one speed, u / u_field, or -- self -- every launch takes its own input buffer as the speed field
+template <typename T>
+static int march_nu_t(pa_ctx* c, void* const b[3], int order, int kind, double u, const void* u_field, bool self,
+                      const pa_velocity* vel, double dt, int64_t nsteps, int* final, const pa_source* src, const void* nuf) {
+  T* const buf[3] = {(T*)b[0], (T*)b[1], (T*)b[2]};
+  return march_t<T>(buf, order, nsteps, final, [&](T* in, T* out, const T* phi0, double c0, double c1) {
+    return step_t<T>(c, in, out, StepAdv{kind, u, self ? (const void*)in : u_field, vel, -1}, 0.0, dt, {phi0, c0, c1}, src, false, nuf);
+  });
+}
+
 // pa_momentum_march: the rotation over (ncomp, ncell) buffers.  A stage computes every component from the SAME input vector:
 // component q of `in` goes to component q of `out` with component q's BC values in the bound list (types, order and dxf stay),
 // advected by the frozen velocity `fz` or, fz null, by the input vector itself -- internal axis ia carries component
-// ia - (3 - ndim).  The bound list's values are restored on every way out.
+// ia - (3 - ndim).  The bound list's values are restored on every way out.  nuf: one diffusivity field for every component.
 template <typename T>
 static int march_momentum_t(pa_ctx* c, void* const b[3], int ncomp, int order, int kind, const pa_velocity* fz, double nu,
-                            double dt, int64_t nsteps, int* final, const pa_source* src, const pa_bc_values* bcv) {
+                            double dt, int64_t nsteps, int* final, const pa_source* src, const pa_bc_values* bcv,
+                            const void* nuf = nullptr) {
   T* const buf[3] = {(T*)b[0], (T*)b[1], (T*)b[2]};
   const int64_t nc = c->G.ncell;
   const int sh = 3 - c->ndim;
@@ -373,7 +444,7 @@ static int march_momentum_t(pa_ctx* c, void* const b[3], int ncomp, int order, i
       for (int f = 0; f < 2 * c->ndim; ++f) { c->bc[f + 2 * sh].value = bcv[q].value[f]; c->bc[f + 2 * sh].vals = bcv[q].vals[f]; }
       const pa_source* sq = (src && src[q].has) ? &src[q] : nullptr;
       if (int rc = step_t<T>(c, in + q * nc, out + q * nc, StepAdv{kind, 0.0, nullptr, &vi, fz ? -1 : q + sh}, nu, dt,
-                             {phi0 ? phi0 + q * nc : nullptr, c0, c1}, sq))
+                             {phi0 ? phi0 + q * nc : nullptr, c0, c1}, sq, false, nuf))
         return rc;
     }
     return PA_OK;
@@ -435,6 +506,25 @@ static int check_velocity(pa_ctx* c, const pa_velocity* vel, pa_velocity* vi, in
   return PA_OK;
 }
 
+// The diffusivity of a pa_*_nu call.  NULL or has == 0: *nuf stays null and the call is its sibling.  Else the refusals of the
+// header: a null field, the literal upwind kind, an axisymmetric mesh, a field that overlaps one of the call's buffers, each
+// `bbytes` long (PA_E_ARG); slab mode (PA_E_STATE).
+static int check_diffusivity(pa_ctx* c, const pa_diffusivity* dif, const void** nuf, int kind, const char* who,
+                             std::initializer_list<const void*> bufs, size_t bbytes) {
+  *nuf = nullptr;
+  if (!dif || !dif->has) return PA_OK;
+  if (!dif->field) { pa_set_err(c, "%s: a diffusivity with has != 0 needs its field", who); return PA_E_ARG; }
+  if (kind == PA_OP_DIV_UPWIND_COMPAT) { pa_set_err(c, "%s: the literal upwind form takes no diffusivity field", who); return PA_E_ARG; }
+  if (on_slab(c)) { pa_set_err(c, "%s: a diffusivity field is single GPU only (no slabs)", who); return PA_E_STATE; }
+  if (c->coord != PA_COORD_XYZ) { pa_set_err(c, "%s: a diffusivity field is for xyz meshes (no axisymmetric rows)", who); return PA_E_ARG; }
+  if (overlaps(dif->field, field_bytes(c), bufs, bbytes)) {
+    pa_set_err(c, "%s: the diffusivity field must not be one of the call's buffers", who);
+    return PA_E_ARG;
+  }
+  *nuf = dif->field;
+  return PA_OK;
+}
+
 // what an entry point asks of check_march_call beyond the common rules
 enum {
   MC_W2_ALWAYS = 1,   // three buffers at every order (pa_rk_march); else order 1 does not look at w2, and *w2 becomes null
@@ -472,10 +562,10 @@ static int check_march_call(pa_ctx* c, const char* who, int order, int kind, con
 
 // one step or stage (phi0 non-null) in the context's dtype: the single-launch entry points
 static int step_any(pa_ctx* c, const void* in, void* out, const StepAdv& adv, double nu, double dt, const void* phi0, double c0,
-                    double c1, const pa_source* src) {
+                    double c1, const pa_source* src, const void* nuf = nullptr) {
   PA_HIP(c, hipSetDevice(c->device));
-  return c->dtype == PA_F64 ? step_t<double>(c, (const double*)in, (double*)out, adv, nu, dt, {(const double*)phi0, c0, c1}, src)
-                            : step_t<float>(c, (const float*)in, (float*)out, adv, nu, dt, {(const float*)phi0, c0, c1}, src);
+  return c->dtype == PA_F64 ? step_t<double>(c, (const double*)in, (double*)out, adv, nu, dt, {(const double*)phi0, c0, c1}, src, false, nuf)
+                            : step_t<float>(c, (const float*)in, (float*)out, adv, nu, dt, {(const float*)phi0, c0, c1}, src, false, nuf);
 }
 
 extern "C" {
@@ -523,7 +613,13 @@ int pa_rk_march_vel(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kin
 
 int pa_momentum_march(pa_ctx* c, void* U, void* w1, void* w2, int ncomp, int order, int kind, const pa_velocity* frozen, double nu,
                       double dt, int64_t nsteps, int* final, const pa_source* src, const pa_bc_values* bcv) {
-  const char* who = "pa_momentum_march";
+  return pa_momentum_march_nu(c, U, w1, w2, ncomp, order, kind, frozen, nu, dt, nsteps, final, src, bcv, nullptr);
+}
+
+int pa_momentum_march_nu(pa_ctx* c, void* U, void* w1, void* w2, int ncomp, int order, int kind, const pa_velocity* frozen, double nu,
+                         double dt, int64_t nsteps, int* final, const pa_source* src, const pa_bc_values* bcv,
+                         const pa_diffusivity* dif) {
+  const char* who = (dif && dif->has) ? "pa_momentum_march_nu" : "pa_momentum_march";
   int rc = check_march_call(c, who, order, kind, U, w1, &w2, nsteps, bcv ? final : nullptr,
                             "buffers (two for order 1, else three), a place for the result index, BC values and nsteps >= 0 are needed",
                             0, ncomp);
@@ -550,10 +646,68 @@ int pa_momentum_march(pa_ctx* c, void* U, void* w1, void* w2, int ncomp, int ord
         pa_set_err(c, "%s: a BC face array must not overlap a buffer of the call", who);
         return PA_E_ARG;
       }
+  const void* nuf;
+  if ((rc = check_diffusivity(c, dif, &nuf, kind, who, {U, w1, w2}, vbytes))) return rc;
   PaRange range_("pyapes momentum march");
   PA_HIP(c, hipSetDevice(c->device));
   void* const b[3] = {U, w1, w2};
-  return PA_BY_DTYPE(c, march_momentum_t, c, b, ncomp, order, kind, frozen ? &vi : nullptr, nu, dt, nsteps, final, src, bcv);
+  return PA_BY_DTYPE(c, march_momentum_t, c, b, ncomp, order, kind, frozen ? &vi : nullptr, nu, dt, nsteps, final, src, bcv, nuf);
+}
+
+int pa_step_nu(pa_ctx* c, const void* phi, const void* phi0, void* out, double c0, double c1, int kind, double u, const void* u_field,
+               const pa_velocity* vel, double nu, double dt, const pa_source* src, const pa_diffusivity* dif) {
+  if (!dif || !dif->has) {   // the sibling itself
+    if (vel) return phi0 ? pa_rk_stage_vel(c, phi, phi0, out, c0, c1, kind, vel, nu, dt, src) : pa_euler_step_vel(c, phi, out, kind, vel, nu, dt, src);
+    return phi0 ? pa_rk_stage_src(c, phi, phi0, out, c0, c1, kind, u, u_field, nu, dt, src) : pa_euler_step_src(c, phi, out, kind, u, u_field, nu, dt, src);
+  }
+  const char* who = "pa_step_nu";
+  if (!c || !c->grid_set) return PA_E_STATE;
+  int rc = pa_check_div_kind(c, kind, who);
+  if (rc) return rc;
+  if (!phi || !out || out == phi || out == phi0) {
+    pa_set_err(c, "%s: out must be a buffer of its own (not phi, not phi0)", who);
+    return PA_E_ARG;
+  }
+  if ((rc = check_source(c, &src, who, {phi, phi0, out, vel ? nullptr : u_field}))) return rc;
+  pa_velocity vi;
+  if (vel && (rc = check_velocity(c, vel, &vi, kind, src, who, {phi, phi0, out}))) return rc;
+  const void* nuf;
+  if ((rc = check_diffusivity(c, dif, &nuf, kind, who, {phi, phi0, out}, field_bytes(c)))) return rc;
+  return step_any(c, phi, out, vel ? StepAdv{kind, 0.0, nullptr, &vi, -1} : StepAdv{kind, u, u_field, nullptr, -1}, 0.0, dt, phi0, c0, c1,
+                  src, nuf);
+}
+
+int pa_march_nu(pa_ctx* c, void* phi, void* w1, void* w2, int order, int kind, double u, const void* u_field, const pa_velocity* vel,
+                int self, double nu, double dt, int64_t nsteps, int* final, const pa_source* src, const pa_diffusivity* dif) {
+  if (!dif || !dif->has) {   // the sibling itself
+    if (vel) return pa_rk_march_vel(c, phi, w1, w2, order, kind, vel, nu, dt, nsteps, final, src);
+    if (self) return pa_rk_march_self_src(c, phi, w1, w2, order, kind, nu, dt, nsteps, final, src);
+    if (order == 1 && !w2) {
+      const int rc = pa_euler_march_src(c, phi, w1, kind, u, u_field, nu, dt, nsteps, src);
+      if (!rc && final) *final = (int)(nsteps & 1);
+      return rc;
+    }
+    return pa_rk_march_src(c, phi, w1, w2, order, kind, u, u_field, nu, dt, nsteps, final, src);
+  }
+  const char* who = "pa_march_nu";
+  int rc = check_march_call(c, who, order, kind, phi, w1, &w2, nsteps, final,
+                            "distinct buffers (two for order 1, else three), a place for the result index and nsteps >= 0 are needed", 0);
+  if (rc) return rc;
+  const bool one = !vel && !self;
+  if ((rc = check_source(c, &src, who, {phi, w1, w2, one ? u_field : nullptr}))) return rc;
+  pa_velocity vi;
+  if (vel && (rc = check_velocity(c, vel, &vi, kind, src, who, {phi, w1, w2}))) return rc;
+  const void* nuf;
+  if ((rc = check_diffusivity(c, dif, &nuf, kind, who, {phi, w1, w2}, field_bytes(c)))) return rc;
+  if (one && overlaps(u_field, field_bytes(c), {phi, w1, w2}, field_bytes(c))) {
+    pa_set_err(c, "%s: a frozen speed field must not be one of the march's buffers (self != 0 is the field that advects itself)", who);
+    return PA_E_ARG;
+  }
+  PaRange range_("pyapes march with a diffusivity field");
+  PA_HIP(c, hipSetDevice(c->device));
+  void* const b[3] = {phi, w1, w2};
+  return PA_BY_DTYPE(c, march_nu_t, c, b, order, kind, one ? u : 0.0, one ? u_field : nullptr, !vel && self != 0, vel ? &vi : nullptr, dt,
+                     nsteps, final, src, nuf);
 }
 
 int pa_euler_step_src(pa_ctx* c, const void* in, void* out, int kind, double u, const void* u_field, double nu, double dt,

@@ -58,6 +58,10 @@ int pa_tile3d_step(pa_ctx* c, Vec<T> phi, T* out, const StepRequest<T>& rq) {
   const bool reach2 = !vel && (kind == PA_OP_DIV_QUICK || limited);   // k_sfq or nothing
   // the field advects itself: the speed at the cell and at its neighbours are the stencil's own operands (k_sf SELF)
   const bool self = u_field && u_field == (const void*)phi.p;
+  const T* nuf = (const T*)rq.nu_field;
+  if (nuf) {   // a diffusivity field: k_sfn -- upwind, one scalar speed, no source, two rows per wave, one GPU -- or nothing
+    if (vel || u_field || src || rq.bcl || kind != PA_OP_DIV_UPWIND || c->ndim != 3 || G.n1 <= 4 || c->slab || G.n0 != G.g0) return 0;
+  }
   if (vel) {   // k_sf VEL or nothing
     if (kind != PA_OP_DIV_UPWIND || c->ndim != 3) return 0;
     const int nf = (vel->field[0] ? 1 : 0) + (vel->field[1] ? 1 : 0) + (vel->field[2] ? 1 : 0);
@@ -75,7 +79,7 @@ int pa_tile3d_step(pa_ctx* c, Vec<T> phi, T* out, const StepRequest<T>& rq) {
   // (the speed fields, a stage's phi0 and a source field count for the alignment)
   const void* sfield = src ? src->field : nullptr;
   const int mode = vel ? cg3d_mode<T>(c, E, {phi.p, out, phi.glo, phi.ghi, phi0, sfield, vel->field[0], vel->field[1], vel->field[2]})
-                       : cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0, sfield});
+                       : cg3d_mode<T>(c, E, {phi.p, out, u_field, phi.glo, phi.ghi, phi0, sfield, nuf});
   if (!mode || (reach2 && mode != 1)) return 0;   // k_sfq: whole 16-byte vectors, aligned operands
   const bool one_speed = !vel && !reach2;   // k_sf, or k_cg3d's Euler phase where k_sf does not apply
   if (one_speed) {
@@ -96,7 +100,16 @@ int pa_tile3d_step(pa_ctx* c, Vec<T> phi, T* out, const StepRequest<T>& rq) {
   }
   // the kernels write the step's value at EVERY node where the BC fill that follows (step_t) rewrites every face plane that has a BC
   A.out_all = pa_bc_on_every_face(c);
+  if (nuf) {   // w_a as the generic kernel's launch forms it (step_t): each operation rounded in T
+    A.nu_f = nuf;
+    for (int a = 0; a < 3; ++a) {
+      T w = A.ih[a] * A.ih[a];
+      w = (T)0.5 * w;
+      A.nu_w[a] = w;
+    }
+  }
   const bool sf = sf_applies<T, 3>(c, A, mode);
+  if (nuf && !sf) return 0;   // k_cg3d's Euler phase knows no diffusivity field: the generic kernel does
   if (!one_speed && !sf) return 0;
   if (src && !sf) return 0;   // k_cg3d's Euler phase takes no source: the generic kernel does
   // central self off k_sf: k_cg3d reads the speed at the cell only.  On a slab the generic kernel takes u's axis-0

@@ -700,6 +700,7 @@ struct SfVariant {
   int us;     // US: the sign of a scalar speed as a launch-time fact (1: u >= 0, 2: u < 0; 0: not used)
   int vel;    // VEL
   bool hasu, bcl, stg, self, src;
+  bool nu;    // a diffusivity field (A.nu_f): k_sfn, the sibling with two marching fields (pa_sfn_kernel.h)
 };
 
 // A as the caller filled it (kind, aux / u, bcl_type, stg_phi0, vel_f / vel_own).  src: the step has a source term;
@@ -710,6 +711,11 @@ static SfVariant sf_variant(pa_ctx* c, Cg3dArgs<T>& A, bool src = false, bool se
   V.kind = A.kind;
   V.stg = A.stg_phi0 != nullptr;
   V.src = src;
+  if (A.nu_f) {   // k_sfn: upwind with one scalar speed, both halves formed, two rows per wave only (pa_tile3d_step declines the rest)
+    V.nu = true;
+    V.rows = 2;
+    return V;
+  }
   if (A.kind == PA_OP_DIV_QUICK || A.kind == PA_OP_DIV_MINMOD || A.kind == PA_OP_DIV_MC) {   // k_sfq
     // Rows per wave.  Four rows read (4 + 4) / 4 = 2 rows per row computed, two rows (2 + 4) / 2 = 3 -- the halo rows are the
     // neighbour waves' own rows, cache hits.  But the four-row instantiations do not fit the 256-VGPR file (pa_sfq_kernel.h:
@@ -758,10 +764,12 @@ template <typename T> int pa_sf_launch_vself(pa_ctx* c, Cg3dArgs<T>& A, const Sf
 template <typename T> int pa_sfq_launch(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);          // pa_sfq.hip: QUICK
 template <typename T> int pa_sfq_launch_src(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);      // pa_sfq_src.hip: QUICK, SRC
 template <typename T> int pa_sft_launch(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);          // pa_sft.hip: minmod, mc
+template <typename T> int pa_sfn_launch(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V);          // pa_sfn.hip: k_sfn, a diffusivity field
 
 // the unit that holds V's instantiation, asked
 template <typename T>
 static int sf_launch_variant(pa_ctx* c, Cg3dArgs<T>& A, const SfVariant& V) {
+  if (V.nu) return pa_sfn_launch<T>(c, A, V);
   if (V.kind == PA_OP_DIV_MINMOD || V.kind == PA_OP_DIV_MC) return pa_sft_launch<T>(c, A, V);
   if (V.kind == PA_OP_DIV_QUICK) return V.src ? pa_sfq_launch_src<T>(c, A, V) : pa_sfq_launch<T>(c, A, V);
   if (V.vel) return V.vel == 3 ? pa_sf_launch_vself<T>(c, A, V) : pa_sf_launch_vel<T>(c, A, V);

@@ -288,6 +288,46 @@ class HipContext:
                 pv.value[a], pv.field[a] = float(comp), None
         return pv, keep
 
+    def _diffusivity(self, nu: float | Tensor) -> tuple[Any, Tensor | None]:
+        """``pa_diffusivity`` of a call (None: ``nu`` is a number, the sibling entry point runs) and the tensor it points into"""
+        if not isinstance(nu, Tensor):
+            return None, None
+        nf = self._field(nu if nu.dim() == self.mesh.dim else nu[0], "diffusivity field")
+        pd = L.PaDiffusivity()
+        pd.has, pd.field = 1, nf.data_ptr()
+        return pd, nf
+
+    def _ref(self, s: Any) -> Any:
+        return None if s is None else C.byref(s)
+
+    def step_nu(self, phi: Tensor, phi0: Tensor | None, out: Tensor, c0: float, c1: float, kind: int,
+                u: float | Tensor | Sequence[float | Tensor], nu: Tensor, dt: float, source: float | Tensor | None = None) -> None:
+        """the Euler step (``phi0`` None) or the stage ``out = B(c0 phi0 + c1 E(phi))`` with the diffusivity field ``nu``
+        (``pa_step_nu``); ``u``: one speed, or a list / tuple -- a velocity"""
+        phi, out = self._field(phi, "step_nu"), self._field(out, "step_nu")
+        phi0 = None if phi0 is None else self._field(phi0, "step_nu")
+        pv, _kv = self._velocity(u, "step_nu") if isinstance(u, (list, tuple)) else (None, None)
+        us, uf = (0.0, None) if pv is not None else self._speed(u)
+        ps, _ks = self._source(source, "step_nu")
+        pd, _kd = self._diffusivity(nu)
+        self._rc(self.lib.pa_step_nu(self.h, self._ptr(phi), self._ptr(phi0), self._ptr(out), float(c0), float(c1), kind, us,
+                                     self._ptr(uf), self._ref(pv), 0.0, float(dt), self._ref(ps), self._ref(pd)))
+
+    def march_nu(self, phi: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int,
+                 u: float | Tensor | Sequence[float | Tensor] | None, nu: Tensor, dt: float, nsteps: int,
+                 source: float | Tensor | None = None) -> Tensor:
+        """``nsteps`` steps of ``order`` with the diffusivity field ``nu``, frozen for the call (``pa_march_nu``).  ``u``: one
+        frozen speed, a list / tuple -- a frozen velocity -- or None: the field advects itself.  Returns the tensor that holds
+        the final state."""
+        bufs = [self._field(t, "march_nu") for t in (phi, w1, w2) if t is not None]
+        pv, _kv = self._velocity(u, "march_nu") if isinstance(u, (list, tuple)) else (None, None)
+        us, uf = (0.0, None) if (pv is not None or u is None) else self._speed(u)
+        ps, _ks = self._source(source, "march_nu")
+        pd, _kd = self._diffusivity(nu)
+        return self._rotate(bufs, lambda ptrs, final: self._rc(self.lib.pa_march_nu(
+            self.h, *ptrs, int(order), kind, us, self._ptr(uf), self._ref(pv), 1 if u is None else 0, 0.0, float(dt), int(nsteps),
+            final, self._ref(ps), self._ref(pd))))
+
     def euler_step_vel(self, phi: Tensor, out: Tensor, kind: int, vel: Sequence[float | Tensor], nu: float, dt: float,
                        source: float | Tensor | None = None) -> None:
         """``euler_step`` in a velocity field: one advection speed per mesh axis (``pa_euler_step_vel``)"""
@@ -335,7 +375,7 @@ class HipContext:
         return bv, keep
 
     def momentum_march(self, U: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int,
-                       vel: Sequence[float | Tensor] | None, nu: float, dt: float, nsteps: int,
+                       vel: Sequence[float | Tensor] | None, nu: float | Tensor, dt: float, nsteps: int,
                        sources: Sequence[float | Tensor | None] | None, bcs: Sequence[Any]) -> Tensor:
         """``pa_momentum_march``: the SSP Runge-Kutta march of the vector ``U`` ((dim, *nx), contiguous) advected by itself
         (``vel`` None) or by a frozen velocity; ``sources``: None or one entry per component.  The BC list must be bound
@@ -363,7 +403,12 @@ class HipContext:
             one, kept = self.bc_values(U, bcs, q)
             bv[q] = one
             _kb.append(kept)
-        self._keep["momentum"] = (_kv, _ks, _kb)   # what the enqueued launches still read
+        pd, _kd = self._diffusivity(nu)
+        self._keep["momentum"] = (_kv, _ks, _kb, _kd)   # what the enqueued launches still read
+        if pd is not None:   # a diffusivity field: the scalar nu is not read
+            return self._rotate(bufs, lambda ptrs, final: self._rc(self.lib.pa_momentum_march_nu(
+                self.h, *ptrs, nd, int(order), kind, None if pv is None else C.byref(pv), 0.0, float(dt), int(nsteps), final,
+                ps, bv, C.byref(pd))))
         return self._rotate(bufs, lambda ptrs, final: self._rc(self.lib.pa_momentum_march(
             self.h, *ptrs, nd, int(order), kind, None if pv is None else C.byref(pv), float(nu), float(dt), int(nsteps), final,
             ps, bv)))

@@ -55,6 +55,11 @@ class PaVelocity(C.Structure):
     _fields_ = [("has", C.c_int32), ("value", C.c_double * 3), ("field", C.c_void_p * 3)]
 
 
+class PaDiffusivity(C.Structure):
+    """``pa_diffusivity``: the diffusivity field of the explicit steps (``has`` 0: none, the scalar ``nu`` is used)"""
+    _fields_ = [("has", C.c_int32), ("field", C.c_void_p)]
+
+
 class PaBcValues(C.Structure):
     """``pa_bc_values``: one component's face values for ``pa_momentum_march``, indexed as ``pa_bc_set``'s ``face``"""
     _fields_ = [("value", C.c_double * 6), ("vals", C.c_void_p * 6)]
@@ -135,6 +140,13 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
                                   C.POINTER(C.c_int), C.POINTER(PaSource)]),
     "pa_momentum_march": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(PaVelocity), C.c_double, C.c_double,
                                     C.c_int64, C.POINTER(C.c_int), C.POINTER(PaSource), C.POINTER(PaBcValues)]),
+    "pa_step_nu": (C.c_int, [_VP, _VP, _VP, _VP, C.c_double, C.c_double, C.c_int, C.c_double, _VP, C.POINTER(PaVelocity), C.c_double,
+                             C.c_double, C.POINTER(PaSource), C.POINTER(PaDiffusivity)]),
+    "pa_march_nu": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_double, _VP, C.POINTER(PaVelocity), C.c_int, C.c_double,
+                              C.c_double, C.c_int64, C.POINTER(C.c_int), C.POINTER(PaSource), C.POINTER(PaDiffusivity)]),
+    "pa_momentum_march_nu": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.POINTER(PaVelocity), C.c_double, C.c_double,
+                                       C.c_int64, C.POINTER(C.c_int), C.POINTER(PaSource), C.POINTER(PaBcValues),
+                                       C.POINTER(PaDiffusivity)]),
     "pa_cg_begin": (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_int64]),
     "pa_cg_phase_a": (C.c_int, [_VP]),
     "pa_cg_phase_b": (C.c_int, [_VP]),
@@ -198,11 +210,11 @@ def load_library(path: str | None = None) -> C.CDLL:
             f"pyapes_amd: {p} not found. Build it with pyapes_amd/csrc/build.sh "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(p)
-    # an A/B library named by PYAPES_HIP_LIB (bench_ops.py *_baseline sections) may predate the source term, the velocity or
-    # the momentum march: it runs everything but a call with one of them, which then fails on the missing symbol
+    # an A/B library named by PYAPES_HIP_LIB (bench_ops.py *_baseline sections) may predate the source term, the velocity, the
+    # momentum march or the diffusivity field: it runs everything but a call with one of them, which then fails on the missing symbol
     older = p != LIB_PATH
     for name, (res, args) in SIGNATURES.items():
-        if older and (name.endswith(("_src", "_vel")) or name == "pa_momentum_march") and not hasattr(lib, name):
+        if older and (name.endswith(("_src", "_vel", "_nu")) or name == "pa_momentum_march") and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch: fail loudly
         fn.restype = res

@@ -40,6 +40,15 @@ with component c's face values; every Runge-Kutta stage is advected by its own i
 component's output of the same stage.  ``u=`` a velocity transports every component by that frozen velocity instead (the
 linearised, Oseen form: ``mesh.dim`` scalar marches in one call); ``source=`` has one entry per component.  The four scalar
 entry points keep refusing vector targets.
+
+Diffusivity field: ``nu`` a Tensor shaped like ``phi()`` or like one component, or a scalar Field on the same mesh, on all six
+entry points -- two materials, a conductivity that depends on position, an eddy viscosity under ``momentum_march`` (one field for
+every component).  ``nu lap(phi)`` is then replaced by the conservative ``div(nu grad phi)`` with the diffusivity averaged onto
+the faces (DESIGN.md section 4 "Diffusivity field"): per axis  t = ((nu[+1] + nu) (x[+1] - x) - (nu + nu[-1]) (x - x[-1])) * 0.5/dx^2,
+every operation rounded on its own; the step reads the BC-filled face values of its input and ``nu`` at every node the stencil
+touches (``nu`` has no BCs).  ``nu`` is FROZEN for the call, and it composes with ``source=``, a velocity, self-advection and every
+limiter.  A number is the path it always was, bit for bit.  Not with a diffusivity field: slab and axisymmetric meshes,
+``compat: True``, ``nu`` on ``phi``'s own storage.
 """
 from __future__ import annotations
 
@@ -117,6 +126,40 @@ def _source_of(phi: Field, source: Any, what: str) -> float | Tensor | None:
     return source.contiguous()
 
 
+def _diffusivity_of(phi: Any, nu: Any, config: dict | None, what: str) -> Any:
+    """the checks of a diffusivity FIELD -- made before a device is touched -- and what the Context methods take: a contiguous
+    tensor of one component's shape.  A number is handed back as it came: today's path, untouched."""
+    if not isinstance(nu, (Tensor, Field)):
+        return nu
+    mesh = phi.mesh
+    if getattr(mesh, "slab", None) is not None:
+        raise NotImplementedError(f"pyapes_amd: {what}: a diffusivity field on a slab mesh (single GPU only)")
+    if mesh.coord_sys == "rz":
+        raise NotImplementedError(f"pyapes_amd: {what}: a diffusivity field on an axisymmetric (rz) mesh")
+    if bool(((config or {}).get("div") or {}).get("compat", False)):
+        raise NotImplementedError(f"pyapes_amd: {what}: a diffusivity field with compat: True (the reference's literal upwind form)")
+    if isinstance(nu, Field):
+        if nu.dim != 1:
+            raise NotImplementedError(f"pyapes_amd: {what}: the diffusivity is a scalar field (got {nu.dim} components)")
+        if nu.mesh is not mesh:
+            raise ValueError(f"pyapes_amd: {what}: the diffusivity Field lives on another mesh")
+        nu = nu()
+    p = phi()
+    comp = tuple(p.shape[1:])
+    if tuple(nu.shape) == (1, *comp):
+        nu = nu[0]
+    elif tuple(nu.shape) != comp:
+        raise ValueError(f"pyapes_amd: {what}: nu shape {tuple(nu.shape)}, expected {(1, *comp)} or {comp}")
+    if nu.dtype != p.dtype:
+        raise ValueError(f"pyapes_amd: {what}: nu dtype {nu.dtype} != mesh dtype {p.dtype}")
+    if nu.device != p.device:
+        raise ValueError(f"pyapes_amd: {what}: nu on {nu.device}, the field on {p.device}")
+    if nu.untyped_storage().data_ptr() == p.untyped_storage().data_ptr():
+        raise ValueError(f"pyapes_amd: {what}: nu shares phi's storage (the step kernels read it while they write phi; "
+                         "nu does not depend on phi within a call)")
+    return nu.contiguous()
+
+
 def _velocity_of(phi: Field, u: Any, config: dict | None, what: str) -> list[float | Tensor] | None:
     """``u`` as a velocity -- one entry per mesh axis, all numbers or all contiguous tensors of one component's shape -- or None
     when ``u`` is one speed for every axis (a float, a ``(1, *n)`` Tensor, a scalar Field: the existing path, untouched).  All
@@ -188,7 +231,10 @@ def _run(ctx: Any, phi: Field, bufs: list[Tensor], order: int, kind: int, u: Any
     the result."""
     w1 = bufs[0][0]
     w2 = None if len(bufs) == 1 or order == 1 else bufs[1][0]   # order 1: the ping-pong of two buffers
-    if vel is not None:
+    if isinstance(nu, Tensor):   # a diffusivity field: one entry for every kind of speed (None: the field itself)
+        speed = vel if vel is not None else (None if self_adv else _adv_of(u, phi))
+        final = ctx.march_nu(phi()[0], w1, w2, order, kind, speed, nu, dt, nsteps, source=src)
+    elif vel is not None:
         final = ctx.rk_march_vel(phi()[0], w1, w2, order, kind, vel, nu, dt, nsteps, source=src)
     elif self_adv:   # the speed moves with the field: no single pointer names it
         final = ctx.rk_march_self(phi()[0], w1, w2, order, kind, nu, dt, nsteps, source=src)
@@ -221,13 +267,14 @@ def _march_on_slabs(phi: Field, u: Any, nu: float, dt: float, nsteps: int, kind:
     return phi
 
 
-def euler_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float,
+def euler_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float | Tensor | Field, dt: float,
                config: dict | None = None, *, source: float | Tensor | Field | None = None) -> Field:
     """Advance ``phi`` in place by one explicit Euler step; returns ``phi``.  ``source``: the term S of ``+ S`` (module
     docstring), frozen for the call.  ``u``: one speed for every axis, or a velocity -- one speed per mesh axis (module
     docstring "Velocity"), frozen for the call."""
     vel = _velocity_of(phi, u, config, "euler_step")
     src = _source_of(phi, source, "euler_step")
+    nu = _diffusivity_of(phi, nu, config, "euler_step")
     kind = _kind_of(config, phi.mesh, "euler_step")
     if getattr(phi.mesh, "slab", None) is not None:
         return _march_on_slabs(phi, u, nu, dt, 1, kind)
@@ -237,7 +284,9 @@ def euler_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, 
     ctx = context_for(phi.mesh)
     ctx.bind_bcs(phi(), phi.bcs, 0)
     out = torch.empty_like(phi())
-    if vel is not None:
+    if isinstance(nu, Tensor):
+        ctx.step_nu(phi()[0], None, out[0], 0.0, 0.0, kind, vel if vel is not None else _adv_of(u, phi), nu, dt, source=src)
+    elif vel is not None:
         ctx.euler_step_vel(phi()[0], out[0], kind, vel, nu, dt, source=src)
     else:
         ctx.euler_step(phi()[0], out[0], kind, _adv_of(u, phi), nu, dt, source=src)
@@ -245,7 +294,7 @@ def euler_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, 
     return phi
 
 
-def euler_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float, nsteps: int,
+def euler_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float | Tensor | Field, dt: float, nsteps: int,
                 config: dict | None = None, *, source: float | Tensor | Field | None = None) -> Field:
     """``nsteps`` explicit Euler steps with no host work in between (the whole march is enqueued by one
     C-ABI call: fused step kernel + ordered BC fill per step, ping-pong buffers).  ``source``: the term S of ``+ S``
@@ -255,6 +304,7 @@ def euler_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float,
         raise NotImplementedError("pyapes_amd: euler_march is for scalar fields")
     vel = _velocity_of(phi, u, config, "euler_march")
     src = _source_of(phi, source, "euler_march")
+    nu = _diffusivity_of(phi, nu, config, "euler_march")
     kind = _kind_of(config, phi.mesh, "euler_march")
     self_adv = advects_itself(phi, u)
     if self_adv:
@@ -286,7 +336,7 @@ def _rk_args(phi: Field, config: dict | None, order: int, what: str) -> int:
     return _kind_of(config, phi.mesh, what)
 
 
-def rk_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float, config: dict | None = None,
+def rk_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float | Tensor | Field, dt: float, config: dict | None = None,
             order: int = 3, *, source: float | Tensor | Field | None = None) -> Field:
     """Advance ``phi`` by one SSP Runge-Kutta step of ``order`` (1: the Euler step); returns ``phi``.  ``source``: the term S
     of ``+ S`` (module docstring), the same in every stage of the step; a forcing that depends on time is handed in anew
@@ -294,6 +344,7 @@ def rk_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt:
     vel = _velocity_of(phi, u, config, "rk_step")
     kind = _rk_args(phi, config, order, "rk_step")
     src = _source_of(phi, source, "rk_step")
+    nu = _diffusivity_of(phi, nu, config, "rk_step")
     if order == 1:
         return euler_step(phi, u, nu, dt, config, source=src)   # (a speed on phi's own storage is self-advection at the C ABI)
     self_adv = advects_itself(phi, u)
@@ -306,7 +357,7 @@ def rk_step(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt:
     return phi
 
 
-def rk_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt: float, nsteps: int,
+def rk_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float | Tensor | Field, dt: float, nsteps: int,
              config: dict | None = None, order: int = 3, *, source: float | Tensor | Field | None = None) -> Field:
     """``nsteps`` SSP Runge-Kutta steps of ``order`` with no host work in between (one C-ABI call enqueues the whole
     march: the Euler kernel, then one fused stage kernel per further stage, over three buffers).  Arguments as
@@ -318,6 +369,7 @@ def rk_march(phi: Field, u: float | Tensor | Field | tuple | list, nu: float, dt
     vel = _velocity_of(phi, u, config, "rk_march")
     kind = _rk_args(phi, config, order, "rk_march")
     src = _source_of(phi, source, "rk_march")
+    nu = _diffusivity_of(phi, nu, config, "rk_march")
     self_adv = advects_itself(phi, u)
     require_gpu(phi(), "rk_march")
     ctx = context_for(phi.mesh)
@@ -399,9 +451,10 @@ def _momentum_args(U: Field, config: dict | None, order: int, u: Any, source: An
     return kind, vel, srcs
 
 
-def _momentum(U: Field, nu: float, dt: float, nsteps: int, config: dict | None, order: int, u: Any, source: Any,
+def _momentum(U: Field, nu: float | Tensor | Field, dt: float, nsteps: int, config: dict | None, order: int, u: Any, source: Any,
               what: str) -> Field:
     kind, vel, srcs = _momentum_args(U, config, order, u, source, what)
+    nu = _diffusivity_of(_Component(U), nu, config, what)
     require_gpu(U(), what)
     ctx = context_for(U.mesh)
     if not U().is_contiguous():
@@ -415,7 +468,7 @@ def _momentum(U: Field, nu: float, dt: float, nsteps: int, config: dict | None, 
     return U
 
 
-def momentum_step(U: Field, nu: float, dt: float, config: dict | None = None, order: int = 3, *,
+def momentum_step(U: Field, nu: float | Tensor | Field, dt: float, config: dict | None = None, order: int = 3, *,
                   u: Tensor | Field | tuple | list | None = None, source: Tensor | Field | tuple | list | None = None) -> Field:
     """Advance the vector field ``U`` by one SSP Runge-Kutta step of ``order`` of the momentum equation (module docstring
     "Momentum"); returns ``U``, whose time is not advanced (as ``rk_step``).  ``u`` None: ``U`` transports itself, every stage by
@@ -425,7 +478,7 @@ def momentum_step(U: Field, nu: float, dt: float, config: dict | None = None, or
     return _momentum(U, nu, dt, 1, config, order, u, source, "momentum_step")
 
 
-def momentum_march(U: Field, nu: float, dt: float, nsteps: int, config: dict | None = None, order: int = 3, *,
+def momentum_march(U: Field, nu: float | Tensor | Field, dt: float, nsteps: int, config: dict | None = None, order: int = 3, *,
                    u: Tensor | Field | tuple | list | None = None, source: Tensor | Field | tuple | list | None = None) -> Field:
     """``nsteps`` steps of ``momentum_step`` with no host work in between (one C-ABI call, ``pa_momentum_march``: per stage
     and component one step kernel and its BC fill, over three vector buffers); ``U`` holds the final state and its time
