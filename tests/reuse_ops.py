@@ -529,7 +529,6 @@ def march_op(kind: str, nsteps: int = 2, seed: int = 9) -> Op:
 
     def ref(before: Carried, out: dict, mesh: Any) -> None:
         import march_ref as R
-        import tvd_ref as T
         _, _, om, obcs_s, obcs_v, nu, dt = _march_setup(mesh)
         u_c, s_c = speed_and_source(mesh)
         if kind == "momentum":
@@ -540,7 +539,7 @@ def march_op(kind: str, nsteps: int = 2, seed: int = 9) -> Op:
             if kind == "quick3":
                 want = R.march(phi, u_c, nu, dt, nsteps, om, obcs_s, "quick", 3)
             elif kind == "minmod2":
-                want = T.march(phi, 0.7, nu, dt, nsteps, om, obcs_s, "minmod", 2, s_c)
+                want = R.march(phi, 0.7, nu, dt, nsteps, om, obcs_s, "minmod", 2, s_c)
             elif kind == "euler":
                 want = R.march(phi, 0.7, nu, dt, nsteps + 1, om, obcs_s, "upwind", 1)
             else:

@@ -7,7 +7,7 @@ left it.  The scripts below replay sequences of operations on ONE mesh through t
 same operation on a newly built mesh given the same inputs (the route is the same on both sides, so is the grouping of every
 sum: no tolerance).  After each step the caller-owned inputs of the steps behind are overwritten with NaN, so a kernel that
 reads a pointer of an earlier binding shows NaN.  The fresh run of each distinct operation is also held against the CPU
-references of the suite (oracle/pyapes_oracle.py, tests/march_ref.py, tests/tvd_ref.py) at the suite's bars: bit for bit
+references of the suite (oracle/pyapes_oracle.py, tests/march_ref.py) at the suite's bars: bit for bit
 for single launches and marches, identical ``itr`` and 1e-10 (fp64) / 1e-5 (fp32) for solver iterates.
 
 What a context remembers, and which call resets it: DESIGN.md, "What a context remembers".
@@ -121,7 +121,7 @@ def _cycle():
 def test_time_loop(case):
     """three cycles of momentum_march, rk_march (order 3 quick; order 2 minmod with a source), euler_march (bcl 1),
     rk_march(phi, phi), a CG Poisson solve, FDC.grad and FDC.laplacian, the fields carried from step to step; every step
-    against a fresh mesh given the carried tensors, and against tests/march_ref.py / tvd_ref.py / the oracle"""
+    against a fresh mesh given the carried tensors, and against tests/march_ref.py / the oracle"""
     n, dtype = LOOP[case]
     ops = [start_op()] + _cycle() * 3
     steps = check_gpu_script(ops, box_mesh(n, dtype))

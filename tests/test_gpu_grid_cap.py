@@ -19,7 +19,6 @@ import grid_cap_cases as C
 import march_gpu as G
 import march_ref as R
 import pyapes_oracle as O
-import tvd_ref as T
 from helpers import bit_equal, rel_err
 from pyapes_amd.hip.context import context_for
 from pyapes_amd.solver.fdc import FDC, hessian, jacobian
@@ -264,7 +263,7 @@ EULER = [("upwind", "one_and_a_bit", "double", "mix"), ("upwind", "three_trips",
 @pytest.mark.parametrize("limiter,mid,dtype,bcname", EULER, ids=["-".join(p) for p in EULER])
 def test_generic_euler_step_and_stage_beyond_one_pass(limiter, mid, dtype, bcname):
     """k_euler (fastpath 0): one Euler step and one fused Runge-Kutta stage with a scalar speed of each sign and a speed
-    field, and with source= (a field, on the step and the stage): tests/march_ref.py / tests/tvd_ref.py bit for bit"""
+    field, and with source= (a field, on the step and the stage): tests/march_ref.py bit for bit"""
     n = C.MESHES[mid][0]
     mesh, bc, om, obcs, phis, phi0, ufield, src, nu, dt = G.setup(n, dtype, bcname, 1)
     ctx = context_for(mesh)
@@ -272,14 +271,13 @@ def test_generic_euler_step_and_stage_beyond_one_pass(limiter, mid, dtype, bcnam
     ctx.set_option("fastpath", 0)
     f = G.fresh_field(mesh, bc, phis)
     ctx.bind_bcs(f(), f.bcs, 0)
-    ref = T if limiter in ("minmod", "mc") else R
     c0, c1 = 0.75, 0.25
     phis_d, phi0_d = phis.cuda(), phi0.cuda()
     bad, ran = [], 0
     for tag, u, S in (("pos", 1.3, None), ("neg", -0.8, None), ("field", ufield, None), ("field+source", ufield, src)):
         u_d = u.cuda() if isinstance(u, torch.Tensor) else u
         S_d = None if S is None else S.cuda()[0]
-        e = _quiet(lambda: ref.euler_step(phis.clone(), u, nu, dt, om, obcs, limiter, *(() if S is None else (S,))))
+        e = _quiet(lambda: R.euler_step(phis.clone(), u, nu, dt, om, obcs, limiter, *(() if S is None else (S,))))
         stage = (c0 * phi0) + (c1 * e)
         O.bc_fill(stage, obcs)
         out = torch.full_like(phis_d, float("nan"))

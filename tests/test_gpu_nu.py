@@ -2,7 +2,7 @@
 pyapes_amd/solver/march.py, pa_step_nu / pa_march_nu / pa_momentum_march_nu at the C ABI, the NU instantiations of the generic
 k_euler and the tiled k_sfn (two marching fields).
 
-The yardstick is tests/nu_ref.py, the term div(nu grad phi) and its step restated on the CPU operation for operation, and the
+The yardstick is tests/march_ref.py, the term div(nu grad phi) and its step restated on the CPU operation for operation, and the
 device must give its BITS on every path.  Meshes of the tiled kernel: 14 x 12 x 16 (one partial k tile), 10 x 12 x 132, and
 6 x 7 x 260 fp32 / 6 x 7 x 130 fp64 (two k tiles, the second one vector wide; an odd row count at two rows per wave), each with
 the chunk cap at 1 and 2, all-dirichlet / mixed / periodic-z / periodic-x faces and u in {0, +0.7, -0.7}.
@@ -14,7 +14,6 @@ import torch
 
 import march_gpu as G
 import march_ref as R
-import nu_ref as NR
 import pyapes_oracle as O
 from helpers import bit_equal, guards_intact, offset_view
 from pyapes_amd.geometry import Box, Cylinder
@@ -80,8 +79,8 @@ def launch(mesh, bc, phi_d, phi0_d, stage, kind, u, nu_d, dt, source=None):
 
 def reference(S, stage, u, limiter="upwind", source=None):
     if stage is None:
-        return NR.euler_step(S["phi"], u, S["nu"], S["dt"], S["om"], S["obcs"], limiter, source)
-    return NR.rk_stage(S["phi"], S["phi0"], stage[0], stage[1], u, S["nu"], S["dt"], S["om"], S["obcs"], limiter, source)
+        return R.euler_step(S["phi"], u, S["nu"], S["dt"], S["om"], S["obcs"], limiter, source)
+    return R.rk_stage(S["phi"], S["phi0"], stage[0], stage[1], u, S["nu"], S["dt"], S["om"], S["obcs"], limiter, source)
 
 
 # ---- the step and the fused stage on the generic and on the tiled kernel ------------------------------------------------
@@ -114,7 +113,7 @@ def test_the_field_form_reads_filled_faces_not_the_two_thirds_rows():
     ones = torch.ones_like(S["nu"]).cuda()
     got = launch(S["mesh"], S["bc"], S["phi"].cuda(), None, None, G.kind("upwind"), 0.0, ones, 1e-5)
     const = R.euler_step(S["phi"], 0.0, 1.0, 1e-5, S["om"], S["obcs"], "upwind")
-    assert bit_equal(got, NR.euler_step(S["phi"], 0.0, torch.ones_like(S["nu"]), 1e-5, S["om"], S["obcs"], "upwind"))
+    assert bit_equal(got, R.euler_step(S["phi"], 0.0, torch.ones_like(S["nu"]), 1e-5, S["om"], S["obcs"], "upwind"))
     assert not bit_equal(got, const)
 
 
@@ -235,7 +234,7 @@ def _nu_forms(S):
 @pytest.mark.parametrize("order", [1, 2, 3])
 def test_rk_march_of_three_steps(n, dtype, order):
     S = setup(n, dtype, "mix")
-    want = NR.march(S["phi"], 0.7, S["nu"], S["dt"], 3, S["om"], S["obcs"], "upwind", order)
+    want = R.march(S["phi"], 0.7, S["nu"], S["dt"], 3, S["om"], S["obcs"], "upwind", order)
     for form, nu in _nu_forms(S):
         f = G.fresh_field(S["mesh"], S["bc"], S["phi"], time=True)
         g = rk_march(f, 0.7, nu, S["dt"], 3, G.config("upwind"), order=order)
@@ -243,7 +242,7 @@ def test_rk_march_of_three_steps(n, dtype, order):
         assert bit_equal(f(), want), (form, float((f().cpu() - want).abs().max()))
     f = G.fresh_field(S["mesh"], S["bc"], S["phi"])
     euler_march(f, 0.7, S["nu"].cuda(), S["dt"], 3, G.config("upwind"))
-    assert bit_equal(f(), NR.march(S["phi"], 0.7, S["nu"], S["dt"], 3, S["om"], S["obcs"], "upwind", 1))
+    assert bit_equal(f(), R.march(S["phi"], 0.7, S["nu"], S["dt"], 3, S["om"], S["obcs"], "upwind", 1))
     if order > 1:   # the single steps
         f = G.fresh_field(S["mesh"], S["bc"], S["phi"])
         for _ in range(3):
@@ -287,7 +286,7 @@ def test_march_composes_with_every_speed_source_and_limiter(n, dtype, combo):
     for order in (1, 3):
         f = G.fresh_field(S["mesh"], S["bc"], S["phi"])
         rk_march(f, f if self_adv else u_dev, S["nu"].cuda(), S["dt"], 3, G.config(limiter), order=order, source=s_dev)
-        want = NR.march(S["phi"], u_ref, S["nu"], S["dt"], 3, S["om"], S["obcs"], limiter, order, s_ref, self_adv=self_adv)
+        want = R.march(S["phi"], u_ref, S["nu"], S["dt"], 3, S["om"], S["obcs"], limiter, order, s_ref, self_adv=self_adv)
         assert bit_equal(f(), want), (order, float((f().cpu() - want).abs().max()))
 
 
@@ -308,11 +307,11 @@ def test_momentum_march_of_three_steps(dtype, frozen):
         for order in (1, 3):
             f = G.fresh_field(S["mesh"], S["bc"], U_c)
             momentum_march(f, S["nu"].cuda(), S["dt"], 3, G.config(limiter), order=order, u=u_dev)
-            want = NR.momentum.march(U_c, S["nu"], S["dt"], 3, S["om"], obcs, limiter, order, None, u_ref)
+            want = R.momentum.march(U_c, S["nu"], S["dt"], 3, S["om"], obcs, limiter, order, None, u_ref)
             assert bit_equal(f(), want), (limiter, order, float((f().cpu() - want).abs().max()))
     f = G.fresh_field(S["mesh"], S["bc"], U_c)
     momentum_step(f, S["nu"].cuda().unsqueeze(0), S["dt"], G.config("upwind"), order=2, u=u_dev)
-    assert bit_equal(f(), NR.momentum.march(U_c, S["nu"], S["dt"], 1, S["om"], obcs, "upwind", 2, None, u_ref))
+    assert bit_equal(f(), R.momentum.march(U_c, S["nu"], S["dt"], 1, S["om"], obcs, "upwind", 2, None, u_ref))
 
 
 # ---- the generic NU kernel above one pass of its grid -----------------------------------------------------------------
@@ -352,7 +351,7 @@ def test_constant_field_constant_on_one_mesh_equal_fresh_meshes(n, dtype):
     assert bit_equal(a, run(fresh(), 1e-3)) and bit_equal(c, a)
     assert bit_equal(b, run(fresh(), S["nu"].cuda())) and bit_equal(b2, b)
     assert bit_equal(a, R.march(S["phi"], 0.7, 1e-3, S["dt"], 3, S["om"], S["obcs"], "upwind", 3))
-    assert bit_equal(b, NR.march(S["phi"], 0.7, S["nu"], S["dt"], 3, S["om"], S["obcs"], "upwind", 3))
+    assert bit_equal(b, R.march(S["phi"], 0.7, S["nu"], S["dt"], 3, S["om"], S["obcs"], "upwind", 3))
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------
@@ -433,7 +432,7 @@ def test_errors_leave_the_context_usable():
     def good():
         o = torch.empty_like(phi)
         assert step(_dif(nu), o=o) == 0
-        assert bit_equal(o, NR.euler_step(S["phi"], 0.7, S["nu"], dt, S["om"], S["obcs"], "upwind")[0])   # 123.0 was not read
+        assert bit_equal(o, R.euler_step(S["phi"], 0.7, S["nu"], dt, S["om"], S["obcs"], "upwind")[0])   # 123.0 was not read
 
     good()
     assert step(_dif(None)) == L.PA_E_ARG                       # has != 0 without a field

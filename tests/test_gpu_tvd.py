@@ -2,7 +2,7 @@
 generic kernels through pa_tvd_halves of csrc/pa_device.h, the SCH instantiations of the marching kernel k_sfq in
 csrc/pa_sft.hip).
 
-The yardstick of the BITS is tests/tvd_ref.py, the torch-CPU restatement of the definition: FDC.div at every node, the Euler
+The yardstick of the BITS is tests/march_ref.py, the torch-CPU restatement of the definition: FDC.div at every node, the Euler
 step and two fused Runge-Kutta stages must equal it bit for bit, fp32 and fp64, both limiters, on k_sfq and on the generic
 kernel (option "sfq" 0 included), on the small meshes tests/test_gpu_quick.py uses because they are the smallest that reach
 each code path.  The fields mix random values with values on a grid of quarters, so that flat runs (differences that are
@@ -16,10 +16,10 @@ import pytest
 import torch
 
 import march_gpu as G
+import march_ref as Q
 import pyapes_oracle as O
 import test_gpu_rk as R
 import test_tvd_host as H
-import tvd_ref as T
 from helpers import bit_equal, offset_view
 from march_gpu import XPER
 from pyapes_amd.geometry import Box, Cylinder
@@ -157,8 +157,8 @@ def test_div_step_and_stages_are_the_restatement_bit_for_bit(name, lim):
     mesh, bc, om, ob, phis, phi0, u, nu, dt = _setup(name)
     x, x0 = phis.cpu().clone(), phi0.cpu().clone()
     uc = x if CASE[name][4] == "self" else _ref_speed(u)
-    refs = [T.div_tvd(uc, x, om, ob, lim), T.euler_step(x, uc, nu, dt, om, ob, lim)]
-    refs += [T.rk_stage(x, x0, c0, c1, uc, nu, dt, om, ob, lim) for c0, c1 in STAGES]
+    refs = [Q.div_tvd(uc, x, om, ob, lim), Q.euler_step(x, uc, nu, dt, om, ob, lim)]
+    refs += [Q.rk_stage(x, x0, c0, c1, uc, nu, dt, om, ob, lim) for c0, c1 in STAGES]
     assert all(bool(torch.isfinite(r).all()) for r in refs)
     got = _device_results(name, lim)
     for what, a, b in zip(("div", "euler_step", "stage 3/4 1/4", "stage 1/3 2/3"), got, refs):
@@ -183,7 +183,7 @@ def test_chunks_of_every_length(u, lim):
     assert branches_in_every_row_block(x[0])
     uc = torch.randn((1, *n), generator=g, dtype=torch.float64) if u == "field" else u
     nu, dt = 1e-3, 0.2 * (1.0 / 31) / 1.3
-    refs = [T.euler_step(x, uc, nu, dt, om, ob, lim), T.rk_stage(x, x0, 0.75, 0.25, uc, nu, dt, om, ob, lim)]
+    refs = [Q.euler_step(x, uc, nu, dt, om, ob, lim), Q.rk_stage(x, x0, 0.75, 0.25, uc, nu, dt, om, ob, lim)]
     for chunks in (1, 2, 3, 5):
         mesh = Mesh(Box[0:1, 0:1, 0:1], None, n, "cuda", "double")
         ctx = context_for(mesh)
@@ -276,17 +276,17 @@ def test_source_and_velocity_are_the_restatement(lim):
     for s_ref, s_dev in ((src_c, src_c.cuda()[0]), (0.75, 0.75)):
         out = torch.full_like(phi_d, float("nan"))
         ctx.euler_step(phi_d[0], out[0], KIND[lim], one.cuda(), nu, dt, source=s_dev)
-        assert bit_equal(out, T.euler_step(phi_c, one, nu, dt, om, obcs, lim, s_ref))
+        assert bit_equal(out, Q.euler_step(phi_c, one, nu, dt, om, obcs, lim, s_ref))
         out = torch.full_like(phi_d, float("nan"))
         ctx.rk_stage(phi_d[0], phi0_d[0], out[0], 0.75, 0.25, KIND[lim], -0.7, nu, dt, source=s_dev)
-        assert bit_equal(out, T.rk_stage(phi_c, phi0_c, 0.75, 0.25, -0.7, nu, dt, om, obcs, lim, s_ref))
+        assert bit_equal(out, Q.rk_stage(phi_c, phi0_c, 0.75, 0.25, -0.7, nu, dt, om, obcs, lim, s_ref))
     for v_ref, v_dev in (([0.5, -0.25, 1.0],) * 2, ([speed[a] for a in range(3)], [speed[a].cuda() for a in range(3)])):
         out = torch.full_like(phi_d, float("nan"))
         ctx.euler_step_vel(phi_d[0], out[0], KIND[lim], v_dev, nu, dt)
-        assert bit_equal(out, T.euler_step(phi_c, v_ref, nu, dt, om, obcs, lim))
+        assert bit_equal(out, Q.euler_step(phi_c, v_ref, nu, dt, om, obcs, lim))
         out = torch.full_like(phi_d, float("nan"))
         ctx.rk_stage_vel(phi_d[0], phi0_d[0], out[0], 1.0 / 3.0, 2.0 / 3.0, KIND[lim], v_dev, nu, dt, source=src_c.cuda()[0])
-        assert bit_equal(out, T.rk_stage(phi_c, phi0_c, 1.0 / 3.0, 2.0 / 3.0, v_ref, nu, dt, om, obcs, lim, src_c))
+        assert bit_equal(out, Q.rk_stage(phi_c, phi0_c, 1.0 / 3.0, 2.0 / 3.0, v_ref, nu, dt, om, obcs, lim, src_c))
 
 
 # ---- 3. the marches -------------------------------------------------------------------------------------------------
@@ -319,22 +319,22 @@ def test_marches_equal_the_restatement(lim):
         mesh, bc, om, ob, phis, _, u, nu, dt = _setup(name)
         x = phis.cpu().clone()
         a = rk_march(G.fresh_field(mesh, bc, phis), u, nu, dt, 3, cfg, order=3)()
-        assert bit_equal(a, T.march(x, _ref_speed(u), nu, dt, 3, om, ob, lim, 3)), name
+        assert bit_equal(a, Q.march(x, _ref_speed(u), nu, dt, 3, om, ob, lim, 3)), name
         g = G.fresh_field(mesh, bc, phis)
-        assert bit_equal(rk_march(g, g, nu, dt, 3, cfg, order=3)(), T.march(x, None, nu, dt, 3, om, ob, lim, 3, self_adv=True)), name
+        assert bit_equal(rk_march(g, g, nu, dt, 3, cfg, order=3)(), Q.march(x, None, nu, dt, 3, om, ob, lim, 3, self_adv=True)), name
     mesh, bc, om, obcs, phi_c, _, speed, src_c, nu, dt = G.setup([21, 19, 34], "double", "mix", 3)
     vel_c = [speed[a] for a in range(3)]
     for order in (1, 3):
         got = rk_march(G.fresh_field(mesh, bc, phi_c), [v.cuda() for v in vel_c], nu, dt, 2, cfg, order=order)()
-        assert bit_equal(got, T.march(phi_c, vel_c, nu, dt, 2, om, obcs, lim, order)), order
+        assert bit_equal(got, Q.march(phi_c, vel_c, nu, dt, 2, om, obcs, lim, order)), order
     import test_gpu_momentum as GM
     for n, dtype in (([9, 14, 132], "double"), ([17, 12], "double")):
         mesh, bc, om, obcs, _, U_c, src_c, _, nu, dt = GM._setup(n, dtype, "mix")
         got = momentum_march(G.fresh_field(mesh, bc, U_c), nu, dt, 2, cfg, order=3)()
-        assert bit_equal(got, T.momentum.march(U_c, nu, dt, 2, om, obcs, lim, 3)), n
+        assert bit_equal(got, Q.momentum.march(U_c, nu, dt, 2, om, obcs, lim, 3)), n
         srcs = [src_c[c] for c in range(len(n))]
         got = momentum_march(G.fresh_field(mesh, bc, U_c), nu, dt, 1, cfg, order=2, source=[s.cuda() for s in srcs])()
-        assert bit_equal(got, T.momentum.march(U_c, nu, dt, 1, om, obcs, lim, 2, srcs)), n
+        assert bit_equal(got, Q.momentum.march(U_c, nu, dt, 1, om, obcs, lim, 2, srcs)), n
 
 
 @pytest.mark.parametrize("lim", LIMITERS)
@@ -354,7 +354,7 @@ def test_the_bounded_block_stays_inside_its_bounds(lim):
         print(f"block on the GPU, {lim}, u {'field' if isinstance(u, torch.Tensor) else u}: min {lo:.3e}, max - 1 {hi - 1:.3e}")
         assert lo >= 0.0 and hi <= 1.0, (lo, hi)
         assert float((got.cpu() - phi).abs().max()) > 0.3
-        assert bit_equal(got, T.march(phi, u, 0.0, dt, 40, om, ob, lim, 3))
+        assert bit_equal(got, Q.march(phi, u, 0.0, dt, 40, om, ob, lim, 3))
 
 
 # ---- 4. errors ------------------------------------------------------------------------------------------------------

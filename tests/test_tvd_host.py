@@ -1,4 +1,4 @@
-"""No GPU: the slope-limited (TVD) advection schemes, Div limiters "minmod" and "mc", restated on the CPU in tests/tvd_ref.py, and
+"""No GPU: the slope-limited (TVD) advection schemes, Div limiters "minmod" and "mc", restated on the CPU in tests/march_ref.py, and
 the host-side checks in front of the device.
 
 1. With L == 0 the term is march_ref's first-order upwind term, bit for bit.
@@ -16,7 +16,7 @@ the host-side checks in front of the device.
    sum |x[i+1] - x[i]| does not grow by more than 64 ulp of its value per step, and 0 <= x <= 1 holds exactly, for orders 1 and
    3 at CFL 0.25 and 0.5, order 3 at CFL 0.75, both signs of u, fp64 and fp32 (bounds); QUICK leaves [0, 1] by more than 0.05
    on the same input.
-6. Exact bounds 0 <= phi <= 1 through tvd_ref.march (Laplacian with nu = 0, BC fill with zero dirichlet walls): the
+6. Exact bounds 0 <= phi <= 1 through march_ref.march (Laplacian with nu = 0, BC fill with zero dirichlet walls): the
    12 x 14 x 16 block case and the 33^2 solid-body rotation, fp64 and fp32.
 7. Gaussian exp(-((x - 0.5) / 0.08)^2) once round the ring, order 3, CFL 0.4, 64 / 128 / 256 nodes: the L1 errors fall under
    refinement and mc < minmod < upwind at every size.
@@ -31,7 +31,6 @@ import torch
 
 import march_ref as Q
 import pyapes_oracle as O
-import tvd_ref as T
 
 from pyapes_amd.hip import lib as L
 from pyapes_amd.solver import march as M
@@ -61,10 +60,10 @@ def test_without_a_slope_the_term_is_upwind_bit_for_bit(dtype):
     u = torch.randn((1, 7, 9, 12), generator=g, dtype=torch.float64).to(mesh.dtype)
     vel = [torch.randn((7, 9, 12), generator=g, dtype=torch.float64).to(mesh.dtype) for _ in range(3)]
     for speed in (0.7, -1.3, u):
-        assert torch.equal(T.div_tvd(speed, phi, mesh, bcs, T.no_slope), O.div_upwind_intended(speed, phi, mesh))
-    assert torch.equal(T.adv_tvd(vel, phi, mesh, bcs, T.no_slope), Q.adv_upwind(vel, phi, mesh))
+        assert torch.equal(Q.div_tvd(speed, phi, mesh, bcs, Q.no_slope), O.div_upwind_intended(speed, phi, mesh))
+    assert torch.equal(Q.adv_tvd(vel, phi, mesh, bcs, Q.no_slope), Q.adv_upwind(vel, phi, mesh))
     for lim in LIMITERS:   # and with a slope it is another operator
-        assert not torch.equal(T.div_tvd(u, phi, mesh, bcs, lim), O.div_upwind_intended(u, phi, mesh))
+        assert not torch.equal(Q.div_tvd(u, phi, mesh, bcs, lim), O.div_upwind_intended(u, phi, mesh))
 
 
 @pytest.mark.parametrize("lim", LIMITERS)
@@ -75,7 +74,7 @@ def test_linear_data_is_exact(u, lim):
     x, y, z = mesh.grid
     phi = (1 + 2 * x - y + 3 * z).unsqueeze(0)
     S = (slice(1, -1),) * 3
-    err = float((T.div_tvd(u, phi, mesh, bcs, lim)[0] - u * (2 - 1 + 3))[S].abs().max())
+    err = float((Q.div_tvd(u, phi, mesh, bcs, lim)[0] - u * (2 - 1 + 3))[S].abs().max())
     print(f"linear u={u} {lim}: max error {err:.3e}")
     assert err <= 1e-12
 
@@ -86,8 +85,8 @@ def test_cubic_error_pins_the_fallback():
     x = mesh.grid[0]
     dx = mesh.dx_list[0]
     d2 = dx * dx
-    hi = (T.div_tvd(-1.0, (x ** 3).unsqueeze(0), mesh, bcs, "minmod")[0] - (-3 * x * x)).abs()
-    lo = (T.div_tvd(1.0, ((1 - x) ** 3).unsqueeze(0), mesh, bcs, "minmod")[0] - (-3 * (1 - x) ** 2)).abs()
+    hi = (Q.div_tvd(-1.0, (x ** 3).unsqueeze(0), mesh, bcs, "minmod")[0] - (-3 * x * x)).abs()
+    lo = (Q.div_tvd(1.0, ((1 - x) ** 3).unsqueeze(0), mesh, bcs, "minmod")[0] - (-3 * (1 - x) ** 2)).abs()
     print("cubic, u = -1:", hi.tolist(), " mirrored, u = +1:", lo.tolist())
     for i in range(1, 7):
         assert abs(float(hi[i]) - d2) <= 1e-12, (i, float(hi[i]))
@@ -102,8 +101,8 @@ def test_the_fallback_sits_on_non_periodic_axes_only(lim):
     x = torch.randn((8, 9, 10), generator=g, dtype=torch.float64)
     for a in range(3):
         n = x.shape[a]
-        bq, fq, dm, dp = T.tvd_halves(x, a, False, lim)
-        bqp, fqp, _, _ = T.tvd_halves(x, a, True, lim)
+        bq, fq, dm, dp = Q.tvd_halves(x, a, False, lim)
+        bqp, fqp, _, _ = Q.tvd_halves(x, a, True, lim)
         idx = torch.arange(n).reshape([n if q == a else 1 for q in range(3)]).expand(x.shape)
         assert torch.equal(bq[idx <= 1], dm[idx <= 1]) and torch.equal(fq[idx >= n - 2], dp[idx >= n - 2])
         assert torch.equal(bq[idx > 1], bqp[idx > 1]) and torch.equal(fq[idx < n - 2], fqp[idx < n - 2])
@@ -119,10 +118,10 @@ def test_mc_on_the_golden_pairs():
         if "mc" not in g.files:
             continue
         a, b, want = (torch.as_tensor(g[k]) for k in ("mc_a", "mc_b", "mc"))
-        assert torch.equal(T.mc(a, b), want), f
-        assert torch.equal(T.minmod(2 * T.minmod(a, b), (a + b) / 2), want), f
-        assert torch.equal(T.minmod(a, b), O.minmod(a, b)) and torch.equal(T.mc(a, b), O.mc_limiter(a, b)), f
-        m = T.minmod(a, b)   # the three branches and the zero case all occur
+        assert torch.equal(Q.mc(a, b), want), f
+        assert torch.equal(Q.minmod(2 * Q.minmod(a, b), (a + b) / 2), want), f
+        assert torch.equal(Q.minmod(a, b), O.minmod(a, b)) and torch.equal(Q.mc(a, b), O.mc_limiter(a, b)), f
+        m = Q.minmod(a, b)   # the three branches and the zero case all occur
         assert bool(((a >= 0) & (b >= 0) & (m > 0)).any()) and bool(((a < 0) & (b < 0) & (m < 0)).any()) and bool((a * b <= 0).any())
         seen += 1
     assert seen >= 2
@@ -144,7 +143,7 @@ def _ring_adv(x, u, ring, scheme):
     out = torch.zeros_like(x)
     if scheme == "quick":
         return out + Q.quick_term(x, up, um, 0, True, ring)
-    return out + T.tvd_term(x, up, um, 0, True, ring, T.no_slope if scheme == "upwind" else scheme)
+    return out + Q.tvd_term(x, up, um, 0, True, ring, Q.no_slope if scheme == "upwind" else scheme)
 
 
 def ring_march(x, u, dt, nsteps, scheme, order, each=None):
@@ -253,7 +252,7 @@ def test_exact_bounds_through_the_march(lim, dtype):
             x = phi
             lo, hi = 0.0, 1.0
             for _ in range(nsteps // 10):
-                x = T.march(x, vel, 0.0, dt, 10, mesh, bcs, lim, order)
+                x = Q.march(x, vel, 0.0, dt, 10, mesh, bcs, lim, order)
                 lo, hi = min(lo, float(x.min())), max(hi, float(x.max()))
             print(f"{name} {lim} {dtype} order {order}: {nsteps} steps, min {lo:.3e}, max - 1 {hi - 1:.3e}, moved {float((x - phi).abs().max()):.3f}")
             assert lo >= 0.0 and hi <= 1.0, (name, order, lo, hi)
