@@ -545,16 +545,19 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
           if (rowPLo >> jj & 1) mj = (T)0;
           if (rowPHi >> jj & 1) pj = (T)0;
           V s = gP0 * xpi;
+          s = (V)(T)0 + s;   // every axis is summed into zeros, as k_grad: a sum of -0 products is +0
           V mm = gC0 * xc;
           s = s + mm;
           mm = gM0 * xmi;
           g0r[jj] = s + mm;
           s = pj * dn;
+          s = (V)(T)0 + s;
           mm = cj * xc;
           s = s + mm;
           mm = mj * up;
           g1r[jj] = s + mm;
           s = gPkV * xpk;
+          s = (V)(T)0 + s;
           mm = gCkV * xc;
           s = s + mm;
           mm = gMkV * xmk;
@@ -585,6 +588,8 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
             if (CF) axv = axv * cv[jj]; else axv = axv * cf;
           }
           axv = axv * sgn;
+          // A x: the terms are summed into zeros in the equation's order (ops.py:122-154, pa_apply_terms): 0 + -0 = +0
+          if constexpr (PH == 2 && KIND == 0) axv = (V)(T)0 + axv;
         }
         // Div(u phi) of this row with the scheme KIND (fdc.py:708-772; 4 = upwind as tests/test_fdm.py:239
         // states it): shared by the explicit Euler step and the Laplacian + Div operators
@@ -595,8 +600,8 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
             V upl, umi;
   #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-              upl[v] = uc[v] > (T)0 ? uc[v] : (T)0;
-              umi[v] = uc[v] < (T)0 ? uc[v] : (T)0;
+              upl[v] = uc[v] < (T)0 ? (T)0 : uc[v];
+              umi[v] = uc[v] > (T)0 ? (T)0 : uc[v];
             }
   #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -613,9 +618,9 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
             V cP, cC, cM;
   #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-              cP[v] = (T)2 * (uc[v] < (T)0 ? uc[v] : (T)0);
+              cP[v] = (T)2 * (uc[v] > (T)0 ? (T)0 : uc[v]);
               cC[v] = (T)0 * ((T)2 * uc[v]);
-              cM[v] = (T)2 * (uc[v] > (T)0 ? uc[v] : (T)0);
+              cM[v] = (T)2 * (uc[v] < (T)0 ? (T)0 : uc[v]);
             }
   #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -669,6 +674,9 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
           V dv = div_row((PH == 2 && A.aux) ? xv[jj] : (V)A.u);   // A x: the speed may be a field (upwind)
           dv = dv * A.p0;
           if (A.lap_off) axv = (V)(T)0;   // Div alone: 0 + sign * Div, as the generic kernel's running sum
+          if constexpr (PH == 2) {   // the explicit A x alone: the first term joins zeros, like the generic kernel's running sum
+            if (A.p1 != (T)0) dv = (V)(T)0 + dv; else axv = (V)(T)0 + axv;
+          }
           if (A.p1 != (T)0) axv = dv + axv; else axv = axv + dv;
         }
   #pragma unroll
@@ -720,6 +728,7 @@ __global__ void __launch_bounds__(256) k_cg3d(Cg3dArgs<T> A) {
           ax = ax + s;
           if (CF) ax = ax * cv[jj][v]; else ax = ax * cfe;
           ax = ax * sgn;
+          if (PH == 2) ax = (T)0 + ax;
           if (PH == 4) {
             // Jacobi:  x + omega (b - A x) / diag(A)   (k_jacobi, pa_jacobi.hip)
             T dg = act0 ? cCi : (T)0;

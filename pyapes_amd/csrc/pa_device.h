@@ -341,9 +341,9 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
       }
     } else if (t.kind == 3) {  // PA_OP_DIV_UPWIND_COMPAT (literal fdc.py:746-772)
       T ucen = t.u_f ? t.u_f[o] : t.u;
-      T cP = (T)2 * (ucen < (T)0 ? ucen : (T)0);
+      T cP = (T)2 * (ucen > (T)0 ? (T)0 : ucen);
       T cC0 = (T)0 * ((T)2 * ucen);
-      T cM = (T)2 * (ucen > (T)0 ? ucen : (T)0);
+      T cM = (T)2 * (ucen < (T)0 ? (T)0 : ucen);
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         if (!G.act[a]) continue;
@@ -360,8 +360,8 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
       }
     } else if (t.kind == 5) {  // PA_OP_DIV_QUICK (DESIGN.md "QUICK"): advective form, the speed at the node
       T ucen = t.u_f ? t.u_f[o] : t.u;
-      T upl = ucen > (T)0 ? ucen : (T)0;
-      T umi = ucen < (T)0 ? ucen : (T)0;
+      T upl = ucen < (T)0 ? (T)0 : ucen;
+      T umi = ucen > (T)0 ? (T)0 : ucen;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         if (!G.act[a]) continue;
@@ -394,8 +394,8 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
       }
     } else if (TVD && (t.kind == 6 || t.kind == 7)) {  // PA_OP_DIV_MINMOD / _MC (DESIGN.md "Bounded advection"): as QUICK, limited halves
       T ucen = t.u_f ? t.u_f[o] : t.u;
-      T upl = ucen > (T)0 ? ucen : (T)0;
-      T umi = ucen < (T)0 ? ucen : (T)0;
+      T upl = ucen < (T)0 ? (T)0 : ucen;
+      T umi = ucen > (T)0 ? (T)0 : ucen;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         if (!G.act[a]) continue;
@@ -413,8 +413,8 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
       }
     } else {  // PA_OP_DIV_UPWIND (tests/test_fdm.py:239)
       T ucen = t.u_f ? t.u_f[o] : t.u;
-      T upl = ucen > (T)0 ? ucen : (T)0;
-      T umi = ucen < (T)0 ? ucen : (T)0;
+      T upl = ucen < (T)0 ? (T)0 : ucen;
+      T umi = ucen > (T)0 ? (T)0 : ucen;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         if (!G.act[a]) continue;

@@ -102,8 +102,8 @@ __device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd
       s = s + m;
       ax = ax + s;
     } else {
-      const T upl = ucen > (T)0 ? ucen : (T)0;
-      const T umi = ucen < (T)0 ? ucen : (T)0;
+      const T upl = ucen < (T)0 ? (T)0 : ucen;
+      const T umi = ucen > (T)0 ? (T)0 : ucen;
       if (W.kind == 5) {   // PA_OP_DIV_QUICK
         T xpp, xmm;
         pa_nbrs2<T>(G, acc, a, i, j, k, xpp, xmm);

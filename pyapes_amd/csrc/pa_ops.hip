@@ -53,6 +53,7 @@ __global__ void __launch_bounds__(PA_BLOCK) k_grad(DevGeom G, DevEq<T> E, Vec<T>
       T xp, xm;
       pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
       T s = cP * xp;
+      s = (T)0 + s;   // the reference sums an axis into zeros (fdc.py:80-87): a sum of -0 products is +0
       T m = cC * xc;
       s = s + m;
       m = cM * xm;
@@ -219,7 +220,7 @@ __global__ void __launch_bounds__(PA_BLOCK) k_rhs_adjust(DevGeom G, DevEq<T> E, 
             if (t.kind == 2) gm = (T)2 * ucen;
             else {
               // upwind: lower face uses 2*max(u,0), upper face 2*min(u,0)
-              T mx = ucen > (T)0 ? ucen : (T)0, mn = ucen < (T)0 ? ucen : (T)0;
+              T mx = ucen < (T)0 ? (T)0 : ucen, mn = ucen > (T)0 ? (T)0 : ucen;
               gm = side == 0 ? (T)2 * mx : (T)2 * mn;
             }
             T s = R.c13 * vn;

@@ -86,18 +86,18 @@ __global__ void __launch_bounds__(PA_BLOCK) k_div_general(DevGeom G, DevEq<T> E,
           m = cM * xm;
           disc = s + m;
         } else if (S.kind == PA_OP_DIV_UPWIND_COMPAT) {
-          T cP = (T)2 * (ucen < (T)0 ? ucen : (T)0);
+          T cP = (T)2 * (ucen > (T)0 ? (T)0 : ucen);
           T cC = (T)0 * ((T)2 * ucen);
           if (E.rz && a == PA_RZ_AXIS) cC = E.rz[4 * E.rz_n + ga] * ((T)2 * ucen);
-          T cM = (T)2 * (ucen > (T)0 ? ucen : (T)0);
+          T cM = (T)2 * (ucen < (T)0 ? (T)0 : ucen);
           T s = cP * xp;
           T m = cC * xc;
           s = s + m;
           m = cM * xm;
           disc = s + m;
         } else {
-          T upl = ucen > (T)0 ? ucen : (T)0;
-          T umi = ucen < (T)0 ? ucen : (T)0;
+          T upl = ucen < (T)0 ? (T)0 : ucen;
+          T umi = ucen > (T)0 ? (T)0 : ucen;
           T bwd = xc - xm;
           T fwd = xp - xc;
           T s = upl * bwd;

@@ -91,9 +91,12 @@ template <> struct SfBits<double> {
 // is a signed zero: t = u+ (x - x[-1]) + (+-0) has the value of its first product, and if that is itself +-0 only the sign
 // of a zero can differ -- which the accumulation adv = (+0) + t_0 + t_1 + t_2 absorbs (+0 + -0 = +0, and a sum that starts
 // at +0 never becomes -0).  So the dead half -- one subtraction, one product, one addition per axis, 9 of the ~42 row
-// operations of an Euler step -- is not computed, and every FINITE field gives the same bits (tests/test_gpu_tiled_ops.py
-// against the generic kernels, which form both halves).  Only a non-finite neighbour on the dead side differs: 0 x inf is
-// NaN in the literal form, nothing here.
+// operations of an Euler step -- is not computed, and every field whose DEAD-SIDE DIFFERENCE is finite gives the same bits
+// (tests/test_gpu_tiled_ops.py and tests/test_gpu_edge_values.py against the generic kernels, which form both halves).
+// "Every finite field" would be too strong: two finite neighbours of opposite sign above half the largest number make the
+// difference overflow.  Where the dead-side difference is inf or NaN -- an overflow, a non-finite neighbour on the dead
+// side -- the literal form has 0 x inf = NaN and this kernel a number (DESIGN.md section 4 "Edge values").  The speed halves
+// are u < 0 ? 0 : u and u > 0 ? 0 : u, so a NaN speed stays NaN in both, as under the reference's max(u, 0) / min(u, 0).
 // STG: the stage of an SSP Runge-Kutta step (pa_rk_stage).  The row's Euler value e is in registers when it is stored; the
 // stage stores c0 * phi0 + c1 * e instead (two products, one sum, each rounded).  phi0 is read at the cell only, one
 // 16-byte lane access per row like the field's own rows, issued at the top of the plane IN FRONT of the loads of plane
@@ -269,8 +272,8 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
   V uplC = (V)(T)0, umiC = (V)(T)0;
   if (DIV && !HASU && !SELF) {
     const T u = A.u;
-    uplC = (V)(u > (T)0 ? u : (T)0);
-    umiC = (V)(u < (T)0 ? u : (T)0);
+    uplC = (V)(u < (T)0 ? (T)0 : u);
+    umiC = (V)(u > (T)0 ? (T)0 : u);
   }
 
   // ---- register planes -----------------------------------------------------------------------------
@@ -340,8 +343,8 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         const T u = A.vel_v[a];
-        uplA[a] = (V)(u > (T)0 ? u : (T)0);
-        umiA[a] = (V)(u < (T)0 ? u : (T)0);
+        uplA[a] = (V)(u < (T)0 ? (T)0 : u);
+        umiA[a] = (V)(u > (T)0 ? (T)0 : u);
       }
     }
     V Wv[VEL == 2 ? 3 : (VEL == 3 ? 2 : 1)][VEL >= 2 ? RJ : 1];   // VEL 2: the three speed fields of THIS plane, beside phi0's and the source's
@@ -529,8 +532,8 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
               if constexpr (SELF) uc = xc; else uc = U[HC][jj];
 #pragma unroll
               for (int v = 0; v < VEC; ++v) {
-                upl[v] = uc[v] > (T)0 ? uc[v] : (T)0;
-                umi[v] = uc[v] < (T)0 ? uc[v] : (T)0;
+                upl[v] = uc[v] < (T)0 ? (T)0 : uc[v];
+                umi[v] = uc[v] > (T)0 ? (T)0 : uc[v];
               }
             }
 #pragma unroll
@@ -552,8 +555,8 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
                   } else ua = Wv[a][jj];
 #pragma unroll
                   for (int v = 0; v < VEC; ++v) {
-                    upa[v] = ua[v] > (T)0 ? ua[v] : (T)0;
-                    uma[v] = ua[v] < (T)0 ? ua[v] : (T)0;
+                    upa[v] = ua[v] < (T)0 ? (T)0 : ua[v];
+                    uma[v] = ua[v] > (T)0 ? (T)0 : ua[v];
                   }
                 }
                 V bwd = xc - xm3[a];
@@ -583,9 +586,9 @@ __global__ void __launch_bounds__(256) k_sf(Cg3dArgs<T> A) {
             V cP, cC, cM;
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-              cP[v] = (T)2 * (uc[v] < (T)0 ? uc[v] : (T)0);
+              cP[v] = (T)2 * (uc[v] > (T)0 ? (T)0 : uc[v]);
               cC[v] = (T)0 * ((T)2 * uc[v]);
-              cM[v] = (T)2 * (uc[v] > (T)0 ? uc[v] : (T)0);
+              cM[v] = (T)2 * (uc[v] < (T)0 ? (T)0 : uc[v]);
             }
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -743,6 +746,9 @@ static SfVariant sf_variant(pa_ctx* c, Cg3dArgs<T>& A, bool src = false, bool se
   if (PA_SF_USIGN && A.kind == PA_OP_DIV_UPWIND && !V.hasu && !self) V.us = A.u < (T)0 ? 2 : 1;
   V.rows = sf_rows_per_wave<T>(c);
   V.bcl = (A.bcl_type[0] | A.bcl_type[1] | A.bcl_type[2] | A.bcl_type[3] | A.bcl_type[4] | A.bcl_type[5]) != 0;
+  // the fp64 stage with a speed field, a source and BC on load has no four-row instantiation: with the NaN-propagating
+  // speed halves (a compare and two moves where u > 0 ? u : 0 was one v_max_f64) it spilled two VGPRs (pa_sf_src_bcl.hip)
+  if (sizeof(T) == 8 && V.bcl && V.stg && V.src && V.hasu && V.rows == 4) V.rows = 2;
   // BC on load patches rows n1 - 2, n1 - 1 inside one wave's block: no one-row form, and none where n1 - 1 starts a block
   if (V.bcl && (V.rows < 2 || (c->G.n1 - 1) % V.rows == 0)) V.rows = 0;
   return V;

@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(256) k_sfn(Cg3dArgs<T> A) {
   typedef const char __attribute__((address_space(1))) * gcptr;
   const uintptr_t bx = (uintptr_t)A.d.p, bn = (uintptr_t)A.nu_f;
 
-  const V uplC = (V)(A.u > (T)0 ? A.u : (T)0), umiC = (V)(A.u < (T)0 ? A.u : (T)0);
+  const V uplC = (V)(A.u < (T)0 ? (T)0 : A.u), umiC = (V)(A.u > (T)0 ? (T)0 : A.u);
 
   // ---- register planes of the two fields: slot of chunk-relative plane q is (q + 1) & 3; halo slot q & 3 -----------------
   V P[4][RJ], N[4][RJ];

@@ -23,7 +23,8 @@
 //     x[-1] of plane 0 / x[+1] of plane n0-1 ARE read by the central fallback -- the wrap planes, as the generic kernel.
 // US: sign of a SCALAR speed, known at launch -- 1: u >= 0 (bq only: planes i-2 .. i+1, rows j-2 .. j+1), 2: u < 0 (fq
 // only).  The dead half is a signed zero that the accumulation absorbs: k_sf's argument (pa_sf_kernel.h "US") word for word,
-// every finite field gives the bits of the generic kernel, which forms both halves.  The loads nobody uses (row j+2 / j-2,
+// every field whose dead half (fq for u >= 0, bq for u < 0) is finite gives the bits of the generic kernel, which forms both
+// halves; where it is inf or NaN the generic kernel has 0 x inf = NaN and this one a number.  The loads nobody uses (row j+2 / j-2,
 // the far DPP move) fall away with it.  HASU: the speed is a field read at the node (US 0, both halves); a field that
 // advects itself (u_field == phi) runs as HASU with the field as its own speed stream -- same bits, one more read stream
 // that hits in cache.
@@ -135,8 +136,8 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
   V uplC = (V)(T)0, umiC = (V)(T)0;   // scalar speed: u+ / u- once
   if (!HASU) {
     const T u = A.u;
-    uplC = (V)(u > (T)0 ? u : (T)0);
-    umiC = (V)(u < (T)0 ? u : (T)0);
+    uplC = (V)(u < (T)0 ? (T)0 : u);
+    umiC = (V)(u > (T)0 ? (T)0 : u);
   }
 
   // ---- register planes -----------------------------------------------------------------------------
@@ -272,8 +273,8 @@ __global__ void __launch_bounds__(256) k_sfq(Cg3dArgs<T> A) {
         const V uc = U[HC][jj];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
-          upl[v] = uc[v] > (T)0 ? uc[v] : (T)0;
-          umi[v] = uc[v] < (T)0 ? uc[v] : (T)0;
+          upl[v] = uc[v] < (T)0 ? (T)0 : uc[v];
+          umi[v] = uc[v] > (T)0 ? (T)0 : uc[v];
         }
       }
       V adv = (V)(T)0;

@@ -119,6 +119,47 @@ def bit_equal(a, b):
     return torch.equal(torch.as_tensor(a).cpu(), torch.as_tensor(b).cpu())
 
 
+_BITS = {torch.float32: torch.int32, torch.float64: torch.int64}
+
+
+class _Bits:
+    """the verdict of ``same_bits``: true or false, and on failure its ``why`` names the first cell that differs"""
+
+    def __init__(self, ok, why=""):
+        self.ok, self.why = bool(ok), why
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "same bits" if self.ok else self.why
+
+
+def same_bits(a, b):
+    """``a`` and ``b`` (fp32 or fp64, equal dtypes and shapes) hold the same BITS: the NaN masks are equal -- a NaN is a
+    class, its sign and payload are not compared -- and every other element has the same integer view (int32 / int64), so
+    -0 is not +0 and a subnormal is not 0.  False comes with the first differing index and both bit patterns (``.why``,
+    which is also its repr: ``assert same_bits(a, b)`` reports it)."""
+    a, b = torch.as_tensor(a).cpu().contiguous(), torch.as_tensor(b).cpu().contiguous()
+    if a.dtype != b.dtype or a.dtype not in _BITS:
+        return _Bits(False, "dtypes %s / %s: fp32 or fp64 on both sides" % (a.dtype, b.dtype))
+    if a.shape != b.shape:
+        return _Bits(False, "shapes %s / %s" % (tuple(a.shape), tuple(b.shape)))
+    na, nb = torch.isnan(a), torch.isnan(b)
+    ia, ib = a.view(_BITS[a.dtype]), b.view(_BITS[a.dtype])
+    bad = (na != nb) | (~na & ~nb & (ia != ib))
+    if not bool(bad.any()):
+        return _Bits(True)
+    flat = int(bad.flatten().nonzero()[0])
+    idx = tuple(int(i) for i in np.unravel_index(flat, tuple(a.shape))) if a.dim() else ()
+    mask = (1 << (8 * a.element_size())) - 1
+    va, vb = a.flatten()[flat], b.flatten()[flat]
+    pa, pb = int(ia.flatten()[flat]) & mask, int(ib.flatten()[flat]) & mask
+    width = 2 * a.element_size()
+    return _Bits(False, "%d of %d cells differ; the first at %s: %r (0x%0*X) / %r (0x%0*X)"
+                 % (int(bad.sum()), a.numel(), idx, float(va), width, pa, float(vb), width, pb))
+
+
 GUARD_SENTINEL = -123456.789   # finite, and no input of the tests holds it (fields are rand / randn / small BC values)
 
 

@@ -80,7 +80,8 @@ def upwind_term(x: Tensor, up: Tensor, um: Tensor, a: int, periodic: bool, mesh)
     return t
 
 
-def quick_term(x: Tensor, up: Tensor, um: Tensor, a: int, periodic: bool, mesh) -> Tensor:
+def quick_halves(x: Tensor, a: int, periodic: bool) -> tuple[Tensor, Tensor]:
+    """(bq, fq) of the component ``x`` (*n) along mesh axis ``a``"""
     n = x.shape[a]
     assert n >= 5, "quick: an axis needs at least 5 nodes"
     xp, xm = torch.roll(x, -1, a), torch.roll(x, 1, a)
@@ -100,9 +101,14 @@ def quick_term(x: Tensor, up: Tensor, um: Tensor, a: int, periodic: bool, mesh) 
     if not periodic:
         cen = xp - xm
         cen = 0.5 * cen
-        idx = torch.arange(n).reshape([n if q == a else 1 for q in range(mesh.dim)])
+        idx = torch.arange(n).reshape([n if q == a else 1 for q in range(x.dim())])
         bq = torch.where(idx <= 1, cen, bq)
         fq = torch.where(idx >= n - 2, cen, fq)
+    return bq, fq
+
+
+def quick_term(x: Tensor, up: Tensor, um: Tensor, a: int, periodic: bool, mesh) -> Tensor:
+    bq, fq = quick_halves(x, a, periodic)
     inv = torch.ones((), dtype=x.dtype) / mesh.dx[a]
     p = up * bq
     m = um * fq

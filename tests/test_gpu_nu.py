@@ -27,7 +27,7 @@ from pyapes_amd.variables.bcs import mixed_bcs
 
 pytestmark = pytest.mark.gpu
 
-ZPER = ([0.25, -0.5, 2.0, 0.0, None, None], ["dirichlet", "dirichlet", "dirichlet", "dirichlet", "periodic", "periodic"])
+ZPER = G.ZPER
 BCS = dict(G.BCS, zper=ZPER)
 TILED = [([14, 12, 16], "single"), ([14, 12, 16], "double"), ([10, 12, 132], "single"), ([10, 12, 132], "double"),
          ([6, 7, 260], "single"), ([6, 7, 130], "double")]
