@@ -6,7 +6,8 @@ march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step c
 (--sections source) beside the three-launch workaround and the generic kernel, the marches in a velocity field (--sections
 velocity) beside the one-speed marches and the generic kernel, the momentum march of a vector field (--sections momentum)
 beside three scalar marches in three frozen fields, the Euler step with a diffusivity field (--sections nu) beside the
-constant-nu step and its torch composition, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+constant-nu step and its torch composition, the two projection kernels (--sections projection) beside their compositions from
+pa_grad, torch and apply_bcs, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -71,6 +72,8 @@ def main():
                          "vself 0, fastpath 0; not in the default list; momentum_baseline: the yardstick alone, three scalar rk_march "
                          "calls in three velocity fields, which a library without pa_momentum_march can run), nu (the Euler step with a diffusivity field at 256^3 and "
                          "512^3 fp32: tiled, generic, the constant-nu step and the torch composition; not in the default list), "
+                         "projection (pa_divergence and pa_project_correct at 256^3 fp32 and fp64 beside their compositions from "
+                         "pa_grad, torch and apply_bcs, and as a fraction of a device copy; not in the default list), "
                          "small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
@@ -131,7 +134,80 @@ def main():
         momentum_rows(q, emit, with_momentum="momentum" in sections)
     if "nu" in sections:
         nu_rows(q, emit)
+    if "projection" in sections:
+        projection_rows(q, emit)
     solver_rows(q, emit, sections)
+
+
+def projection_rows(q, emit):
+    """The two streaming kernels of the pressure projection at 256^3, fp32 and fp64, all-dirichlet faces, on pre-allocated
+    outputs: ``pa_divergence`` (d + 1 = 4 arrays) beside its composition from existing entry points -- ``pa_grad`` of every
+    component into a (3, 3, *n) buffer, the diagonal summed and scaled in torch -- and ``pa_project_correct`` with its BC fills
+    (2 d + 1 = 7 arrays) beside ``pa_grad(p)``, three torch updates of U and ``apply_bcs``.  Every variant is timed three times
+    in alternation; ms is the median, ms_all the three.  ``frac_of_copy``: the algorithmic bytes per second over those of a
+    device copy of one array of the mesh (1 read + 1 write), measured in the same alternation."""
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    n = 128 if q else 256
+    for dt, es in (("single", 4), ("double", 8)):
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", dt)
+        vals = [[0.0, 0.0, 0.0]] * 5 + [[1.0, 0.5, 0.0]]
+        Uf = Field("U", 3, mesh, {"domain": mixed_bcs(vals, ["dirichlet"] * 6), "obstacle": None}, init_val="random")
+        Uf.apply_bcs()
+        ctx = context_for(mesh)
+        U = Uf()
+        g = torch.Generator(device="cuda").manual_seed(0)
+        p = torch.rand((n, n, n), generator=g, device="cuda", dtype=U.dtype)
+        d, d2 = torch.empty_like(p), torch.empty_like(p)
+        g9 = torch.empty((3, 3, n, n, n), dtype=U.dtype, device="cuda")
+        g3 = g9[0]
+        scale, cscale = 1.0 / 0.01, 1e-6
+        ctx.bind_bcs(U, Uf.bcs, 0)
+
+        def fused_div():
+            ctx.divergence(U, scale, out=d)
+
+        def composed_div():
+            for c in range(3):
+                ctx.grad(U[c], False, out=g9[c])
+            torch.add(g9[0][0], g9[1][1], out=d2)
+            d2.add_(g9[2][2])
+            d2.mul_(scale)
+
+        def fused_correct():
+            ctx.project_correct(U, p, cscale, Uf.bcs)
+
+        def composed_correct():
+            ctx.grad(p, False, out=g3)
+            for c in range(3):
+                U[c].sub_(g3[c], alpha=cscale)
+            Uf.apply_bcs()
+
+        def copy():
+            d.copy_(p)
+
+        rows = [("divergence, fused k_divergence", fused_div, 4, 100),
+                ("divergence, composed: pa_grad per component + torch sums", composed_div, 4, 20),
+                ("project_correct, fused k_project_correct + BC fills", fused_correct, 7, 100),
+                ("project_correct, composed: pa_grad(p) + torch updates + apply_bcs", composed_correct, 7, 20),
+                ("torch copy_ of one array (reference point: 1 read + 1 write)", copy, 2, 100)]
+        ms = {name: [] for name, *_ in rows}
+        for _ in range(3):
+            for name, fn, _, iters in rows:
+                ms[name].append(timed(fn, iters))
+        med = {name: sorted(v)[1] for name, v in ms.items()}
+        copy_gbs = 2 * es * n ** 3 / (med[rows[4][0]] * 1e-3) / 1e9
+        f = "f64" if dt == "double" else "f32"
+        for k, (name, _, passes, _) in enumerate(rows):
+            extra = {"ms_all": ms[name], "frac_of_copy": passes * es * n ** 3 / (med[name] * 1e-3) / 1e9 / copy_gbs}
+            if k in (0, 2):
+                extra["speedup_over_composition"] = med[rows[k + 1][0]] / med[name]
+            emit(f"{name} {n}^3 {f}, dirichlet", n ** 3, med[name], passes, es, extra)
+        assert bool(torch.isfinite(U).all()) and bool(torch.isfinite(d).all())
+        del Uf, mesh, ctx, U, p, d, d2, g9, g3
 
 
 def nu_rows(q, emit):

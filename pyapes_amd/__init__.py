@@ -14,7 +14,7 @@ _SUBMODULES = (
     "backend", "geometry", "geometry.basis", "geometry.box", "geometry.cylinder", "mesh", "mesh.mesh",
     "mesh.tools", "variables", "variables.bcs", "variables.fields", "variables.container", "solver",
     "solver.fdm", "solver.fdc", "solver.ops", "solver.linalg", "solver.tools", "solver.types", "solver.rfp",
-    "solver.march", "testing", "testing.poisson",
+    "solver.march", "solver.projection", "testing", "testing.poisson",
 )
 
 

@@ -413,6 +413,44 @@ class HipContext:
             self.h, *ptrs, nd, int(order), kind, None if pv is None else C.byref(pv), float(nu), float(dt), int(nsteps), final,
             ps, bv)))
 
+    def _vector(self, t: Tensor, what: str) -> Tensor:
+        """a contiguous vector field ``(dim, *nx)`` of the mesh dtype on the GPU"""
+        self.use_current_stream()
+        require_gpu(t, what)
+        if t.dtype != self.dtype or not t.is_contiguous() or t.numel() != self.mesh.dim * self.mesh.N:
+            raise ValueError(f"pyapes_amd: {what}: a contiguous (dim, *nx) buffer of the mesh dtype is needed")
+        return t
+
+    def divergence(self, U: Tensor, scale: float = 1.0, out: Tensor | None = None) -> Tensor:
+        """``pa_divergence``: ``scale`` times the central divergence of the BC-filled vector ``U`` ((dim, *nx), contiguous) on
+        the interior set, +0 off it, in one pass; returns ``out`` (a scalar field of the mesh's shape, made here when None)"""
+        U = self._vector(U, "divergence")
+        y = (torch.empty(tuple(self.mesh.nx), dtype=self.dtype, device=self.device) if out is None
+             else self._field(out, "divergence out"))
+        self._rc(self.lib.pa_divergence(self.h, self._ptr(U), self.mesh.dim, float(scale), self._ptr(y)))
+        return y
+
+    def project_correct(self, U: Tensor, p: Tensor, scale: float, bcs: Sequence[Any] | None = None,
+                        out: Tensor | None = None) -> Tensor:
+        """``pa_project_correct``: ``out_c = U_c - scale * d_c p`` on the interior set for every component in one launch
+        (``out`` None: in place), then -- ``bcs`` given -- the ordered BC fill of every component with its own face values,
+        resolved here, once.  The BC list must be bound (``bind_bcs(U, bcs, 0)``) when ``bcs`` is given.  Returns the tensor
+        that holds the result."""
+        U = self._vector(U, "project_correct")
+        p = self._field(p, "project_correct p")
+        o = U if out is None else self._vector(out, "project_correct out")
+        bv, _kb = None, []
+        if bcs is not None:
+            bv = (L.PaBcValues * self.mesh.dim)()
+            for q in range(self.mesh.dim):
+                one, kept = self.bc_values(U, bcs, q)
+                bv[q] = one
+                _kb.append(kept)
+        self._keep["project"] = _kb   # what the enqueued fills still read
+        self._rc(self.lib.pa_project_correct(self.h, self._ptr(U), self.mesh.dim, self._ptr(p), float(scale),
+                                             self._ptr(None if out is None else o), bv))
+        return o
+
     def euler_march(self, phi: Tensor, tmp: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
                     nsteps: int, source: float | Tensor | None = None) -> Tensor:
         """``nsteps`` explicit Euler steps enqueued back to back, ping-ponging phi <-> tmp; returns the
