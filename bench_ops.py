@@ -7,7 +7,8 @@ march (div(phi, phi)) beside a frozen speed tensor and beside its step-by-step c
 velocity) beside the one-speed marches and the generic kernel, the momentum march of a vector field (--sections momentum)
 beside three scalar marches in three frozen fields, the Euler step with a diffusivity field (--sections nu) beside the
 constant-nu step and its torch composition, the two projection kernels (--sections projection) beside their compositions from
-pa_grad, torch and apply_bcs, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
+pa_grad, torch and apply_bcs, the pressure-carrying projection and the flow diagnostics (--sections pressure) beside the calls
+and the torch passes they replace, Jacobi (config 1 and 3-D), BiCGSTAB, 2-D CG.
 achieved GB/s uses the ALGORITHMIC bytes of SURVEY 8d (apply 2 passes, Euler 2-3, Jacobi 3,
 CG 10, BiCGSTAB 22 = 2 applies x 2 + 9 axpy/dot passes x 2) against the 8 TB/s HBM peak.
 
@@ -74,6 +75,9 @@ def main():
                          "512^3 fp32: tiled, generic, the constant-nu step and the torch composition; not in the default list), "
                          "projection (pa_divergence and pa_project_correct at 256^3 fp32 and fp64 beside their compositions from "
                          "pa_grad, torch and apply_bcs, and as a fraction of a device copy; not in the default list), "
+                         "pressure (pa_project_update beside pa_project_correct + two pa_vec_axpy, pa_flow_stats beside its torch "
+                         "composition, ns_step incremental beside chorin with the iteration counts, 256^3 fp32 and fp64; not in the "
+                         "default list), "
                          "small (the reference's "
                          "own mesh sizes, resident vs launch per phase), big (Jacobi / BiCGSTAB 256^3, 2-D 4096^2, odd extents)")
     args = ap.parse_args()
@@ -136,6 +140,8 @@ def main():
         nu_rows(q, emit)
     if "projection" in sections:
         projection_rows(q, emit)
+    if "pressure" in sections:
+        pressure_rows(q, emit)
     solver_rows(q, emit, sections)
 
 
@@ -208,6 +214,107 @@ def projection_rows(q, emit):
             emit(f"{name} {n}^3 {f}, dirichlet", n ** 3, med[name], passes, es, extra)
         assert bool(torch.isfinite(U).all()) and bool(torch.isfinite(d).all())
         del Uf, mesh, ctx, U, p, d, d2, g9, g3
+
+
+def pressure_rows(q, emit):
+    """The pressure-carrying projection at 256^3, fp32 and fp64, on pre-allocated buffers.  ``pa_project_update`` in its
+    rotational form with the BC fills of U (2 d + 4 = 10 arrays, one launch) beside the sequence it replaces,
+    ``pa_project_correct`` with those fills and two ``pa_vec_axpy`` (2 d + 7 = 13 arrays, three launches).  ``pa_flow_stats``
+    (d = 3 arrays read, one synchronise) beside the torch composition of the same four numbers with one synchronise (rolls,
+    elementwise passes and reductions; counted as 3 arrays too: the bytes that have to move).  Then ``ns_step`` on one flow --
+    a lid-driven box with an outflow face, from p = 0 -- four steps per run, "incremental" beside "chorin", CG to 1e-6 with at
+    most 4000 iterations: ms per step and the iteration counts of every step.  Every variant is timed three times in alternation; ms is the median,
+    ms_all the three."""
+    import math
+
+    from pyapes_amd.geometry import Box
+    from pyapes_amd.hip.context import context_for
+    from pyapes_amd.mesh import Mesh
+    from pyapes_amd.solver.projection import ns_step
+    from pyapes_amd.variables import Field
+    from pyapes_amd.variables.bcs import mixed_bcs
+    n = 128 if q else 256
+    for dt, es in (("single", 4), ("double", 8)):
+        f = "f64" if dt == "double" else "f32"
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", dt)
+        uvals = [[0.0, 0.0, 0.0]] * 5 + [[1.0, 0.5, 0.0]]
+        utypes = ["dirichlet", "neumann"] + ["dirichlet"] * 4
+        ubc = {"domain": mixed_bcs(uvals, utypes), "obstacle": None}
+        pbc = {"domain": mixed_bcs([0.0] * 6, ["neumann", "dirichlet"] + ["neumann"] * 4), "obstacle": None}
+        Uf = Field("U", 3, mesh, ubc, init_val="random")
+        Uf.apply_bcs()
+        ctx = context_for(mesh)
+        U = Uf()
+        g = torch.Generator(device="cuda").manual_seed(0)
+        p, phi, r = (torch.rand((n, n, n), generator=g, device="cuda", dtype=U.dtype) for _ in range(3))
+        U2, p2 = U.clone(), p.clone()
+        cscale, chi = 1e-6, 1e-7
+        ctx.bind_bcs(U, Uf.bcs, 0)
+        ih = [1.0 / float(h) for h in mesh.dx_list]
+
+        def fused_update():
+            ctx.project_update(U, phi, cscale, p, r, chi, Uf.bcs)
+
+        def composed_update():
+            ctx.project_correct(U2, phi, cscale, Uf.bcs)
+            ctx.vec_axpy(p2, p2, 1.0, phi)
+            ctx.vec_axpy(p2, p2, chi, r)
+
+        def fused_stats():
+            ctx.flow_stats(U)
+
+        def torch_stats():
+            rate = U[0].abs() * ih[0] + U[1].abs() * ih[1] + U[2].abs() * ih[2]
+            div = sum((torch.roll(U[a], -1, a) - torch.roll(U[a], 1, a)) * (0.5 * ih[a]) for a in range(3))[1:-1, 1:-1, 1:-1]
+            torch.stack([rate.max().double(), div.abs().max().double(), (div * div).sum(dtype=torch.float64),
+                         (U * U).sum(dtype=torch.float64)]).tolist()
+
+        rows = [("project_update (rotational), fused k_project_update + BC fills", fused_update, 10, 400),
+                ("project_update, composed: pa_project_correct + BC fills + two pa_vec_axpy", composed_update, 13, 400),
+                ("flow_stats, fused k_flow_stats", fused_stats, 3, 400),
+                ("flow_stats, composed: torch rolls, elementwise passes and reductions", torch_stats, 3, 40)]
+        ms = {name: [] for name, *_ in rows}
+        for _ in range(3):
+            for name, fn, _, iters in rows:
+                ms[name].append(timed(fn, iters))
+        med = {name: sorted(v)[1] for name, v in ms.items()}
+        for k, (name, _, passes, _) in enumerate(rows):
+            extra = {"ms_all": ms[name]}
+            if k in (0, 2):
+                extra["speedup_over_composition"] = med[rows[k + 1][0]] / med[name]
+            emit(f"{name} {n}^3 {f}", n ** 3, med[name], passes, es, extra)
+        assert bool(torch.isfinite(U).all()) and bool(torch.isfinite(p).all())
+        del U2, p2, phi, r
+
+        # ns_step on one flow: the lid sets a box of fluid at rest in motion
+        X, Y, Z = mesh.X, mesh.Y, mesh.Z
+        U0 = torch.stack([torch.sin(math.pi * X) * torch.cos(math.pi * Y) * Z, -torch.cos(math.pi * X) * torch.sin(math.pi * Y) * Z,
+                          0.1 * torch.sin(math.pi * Z) * X]).to(U.dtype).contiguous()
+        nu, step, nsteps = 1e-3, 0.2 * float(mesh.dx_list[0]), 4
+        solver = {"fdm": {"method": "cg", "tol": 1e-6, "max_it": 4000, "report": False}}
+
+        def run(form):
+            Ug, pg = Field("U", 3, mesh, ubc), Field("p", 1, mesh, pbc)
+            Ug.set_var_tensor(U0.clone())
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            itr = [ns_step(Ug, pg, nu, step, None, 3, rho=1.0, solver=solver, form=form)["itr"] for _ in range(nsteps)]
+            torch.cuda.synchronize()
+            assert bool(torch.isfinite(Ug()).all())
+            return (time.perf_counter() - t0) * 1e3 / nsteps, itr
+
+        run("incremental")                                   # warm: work tensors, the solver's scratch
+        res = {"chorin": [], "incremental": []}
+        for _ in range(3):
+            for form in res:
+                res[form].append(run(form))
+        meds = {form: sorted(v)[1][0] for form, v in res.items()}
+        for form, v in res.items():
+            extra = {"ms_all": [m for m, _ in v], "itr_per_step": v[0][1], "steps": nsteps}
+            if form == "incremental":
+                extra["speedup_over_chorin"] = meds["chorin"] / meds[form]
+            emit(f"ns_step {form}, lid-driven box, order 3, CG tol 1e-6 max_it 4000, per step {n}^3 {f}", n ** 3, meds[form], 0, es, extra)
+        del Uf, mesh, ctx, U, p, U0
 
 
 def nu_rows(q, emit):

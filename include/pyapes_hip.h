@@ -434,6 +434,39 @@ int pa_momentum_march_nu(pa_ctx* ctx, void* U, void* w1, void* w2, int ncomp, in
 int pa_divergence(pa_ctx* ctx, const void* U, int ncomp, double scale, void* out);
 int pa_project_correct(pa_ctx* ctx, void* U, int ncomp, const void* p, double scale, void* out, const pa_bc_values* bcv);
 
+/* ---- incremental projection and flow diagnostics (new, defined by this library; DESIGN.md section 4 "Incremental form" and
+ * "Flow diagnostics").  Buffers, h_a, the interior set and the rounding are those of the projection block above.
+ *   pa_project_update    the last statement of a pressure-carrying projection step, ONE launch.  phi is the BC-filled increment
+ *                        of the pressure.  On the interior set, every component c, in place:
+ *                            g = phi[+1]_c - phi[-1]_c;  g = g * h_c;  g = scale * g;  U_c = U_c - g
+ *                        and at EVERY node, on and off the interior set:
+ *                            q = p + phi;   nrhs != NULL:  t = chi * nrhs;  q = q + t;   p = q
+ *                        (nrhs = -(rho / dt) div(U*) and chi = nu dt give the rotational form's p + phi - nu rho div(U*); chi
+ *                        is not read when nrhs is NULL).  phi and nrhs are not written.  bcv != NULL: the ordered BC fill of
+ *                        every component of U follows, as behind pa_project_correct; p's fill is the caller's (another BC
+ *                        list).  It is pa_project_correct(U, phi, scale) followed by pa_vec_axpy(p, p, 1, phi) and
+ *                        pa_vec_axpy(p, p, chi, nrhs), bit for bit: 2 d + 4 arrays moved in one launch for 2 d + 7 in three.
+ *   pa_flow_stats        result[0..3] = rate, div_max, div_sq, ke_sq of the BC-filled U in one pass, q_a = 1 / dx_a formed in
+ *                        double and converted once, axes ascending:
+ *                            rate     max over ALL nodes of s:           r = |U_a| * q_a;  s = s + r     (s starts at +0)
+ *                            div_max  max over the interior set of |s|,  s pa_divergence's sum before the scale
+ *                            div_sq   sum over the interior set of (double)(s * s), the square rounded in the grid dtype
+ *                            ke_sq    sum over all nodes and axes of (double)(U_a * U_a)
+ *                        The maxima are doubles (an exact conversion); a NaN in any contribution to a maximum makes that
+ *                        maximum NaN.  The sums are accumulated in double, per block and then over the blocks in a fixed order:
+ *                        the same call gives the same bits, another grid may differ by the rounding of a double sum.
+ *                        dt * rate is the CFL number of an explicit step.  Synchronises.
+ *     PA_E_ARG    ncomp != the mesh dimension, a 1-D mesh, an axisymmetric mesh; a missing buffer; phi overlapping U, p or nrhs;
+ *                 p overlapping U or nrhs; nrhs overlapping U; a BC face array that overlaps U, phi, p or nrhs
+ *     PA_E_STATE  slab mode, a live stepwise solve (pa_cg_begin ... pa_cg_end)
+ * and the context stays usable after either.  Kernels: k_project_update (one cell per lane in a grid-stride loop; U and p are
+ * read and written by the same lane only; old U, old p and nrhs are non-temporal accesses, phi's neighbours plain loads) and
+ * k_flow_stats / k_flow_stats_final (per-block partial sums and maxima in the context's scratch, folded by one block).  Both
+ * appear in the PYAPES_HIP_DEBUG launch log, k_project_update as "k_project_update (rotational)" when nrhs is given. */
+int pa_project_update(pa_ctx* ctx, void* U, int ncomp, const void* phi, double scale, void* p, const void* nrhs, double chi,
+                      const pa_bc_values* bcv);
+int pa_flow_stats(pa_ctx* ctx, const void* U, int ncomp, double* result);
+
 /* ---- vector steps for a host-stepped solver loop (pyapes_amd/solver/host_stepped.py: BC callables that read the iterate
  * make the reference's loop come back to Python for every face of every fill, bcs.py:200-253; the loop's AXPYs and dot
  * products between those fills are these).  Fields of the grid's shape and dtype.

@@ -10,7 +10,7 @@ OBJ="$HERE/build"
 mkdir -p "$OUT" "$OBJ"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-variable ${PA_EXTRA_FLAGS:-})
-TUS=(pa_core pa_bc pa_ops pa_march pa_project pa_solver pa_cg pa_bicgstab pa_jacobi pa_cg3d pa_cg3d_b pa_sf pa_sf_self pa_sf_src pa_sf_src_bcl pa_sf_vel pa_sf_vself pa_sfq pa_sfq_src pa_sft pa_sfn pa_comm pa_rfp pa_resident pa_place)
+TUS=(pa_core pa_bc pa_ops pa_march pa_project pa_stats pa_solver pa_cg pa_bicgstab pa_jacobi pa_cg3d pa_cg3d_b pa_sf pa_sf_self pa_sf_src pa_sf_src_bcl pa_sf_vel pa_sf_vself pa_sfq pa_sfq_src pa_sft pa_sfn pa_comm pa_rfp pa_resident pa_place)
 pids=()
 objs=()
 for tu in "${TUS[@]}"; do

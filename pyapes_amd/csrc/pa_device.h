@@ -463,3 +463,33 @@ __device__ __forceinline__ void pa_block_reduce_store(double (&v)[NS], double* _
     }
   }
 }
+
+// the larger of two, a NaN on either side winning (fmax alone drops it): the maxima of pa_stats.hip
+__device__ __forceinline__ double pa_max_nan(double a, double b) {
+  if (a != a) return a;
+  if (b != b) return b;
+  return a > b ? a : b;
+}
+
+// pa_block_reduce_store's sibling for maxima (pa_max_nan): one row of NS values per block
+template <int NS>
+__device__ __forceinline__ void pa_block_reduce_max_store(double (&v)[NS], double* __restrict__ partials) {
+  __shared__ double sm[NS][PA_BLOCK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    double x = v[s];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = pa_max_nan(x, __shfl_down(x, off, 64));
+    if (lane == 0) sm[s][wave] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      double x = sm[s][0];
+      for (int w = 1; w < (int)(blockDim.x >> 6); ++w) x = pa_max_nan(x, sm[s][w]);
+      partials[(int64_t)blockIdx.x * NS + s] = x;
+    }
+  }
+}

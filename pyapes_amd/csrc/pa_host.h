@@ -30,7 +30,7 @@ struct HostBC {
 
 enum {
   SCR_R = 0, SCR_D0, SCR_D1, SCR_PART, SCR_PART2, SCR_SHELL, SCR_R0, SCR_V0, SCR_V1, SCR_S, SCR_TT,
-  SCR_GHOST, SCR_SHELL2, SCR_RZ, SCR_RES, PA_NSCRATCH
+  SCR_GHOST, SCR_SHELL2, SCR_RZ, SCR_RES, SCR_STATS, PA_NSCRATCH
 };
 
 // room behind every scratch allocation: any of the roles r / d / d' of a CG solve fits any block of the placement

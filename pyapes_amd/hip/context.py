@@ -46,6 +46,7 @@ class HipContext:
         self._rc(self.lib.pa_grid_set(self.h, nd, n, dx, L.PA_F64 if self.dtype == torch.float64 else L.PA_F32,
                                       int(mesh.i_off), n0g))
         self._keep: dict[str, Any] = {}
+        self._work: dict[str, Tensor] = {}
         self._bc_sig: Any = None
         if mesh.coord_sys == "rz":
             self._rc(self.lib.pa_coord_set(self.h, L.PA_COORD_RZ, self._ptr(mesh.x[0].contiguous())))
@@ -81,6 +82,14 @@ class HipContext:
 
     def _ptr(self, t: Tensor | None) -> C.c_void_p:
         return C.c_void_p(0 if t is None else t.data_ptr())
+
+    def work(self, name: str, ncomp: int) -> Tensor:
+        """the work tensor ``name``, ``(ncomp, *nx)`` of the mesh dtype: made at its first use and kept with the context (its
+        content is whatever the last user left: every user writes all of it before reading)"""
+        t = self._work.get(name)
+        if t is None or t.shape[0] != ncomp:
+            t = self._work[name] = torch.empty((ncomp, *self.mesh.nx), dtype=self.dtype, device=self.device)
+        return t
 
     def _field(self, t: Tensor, what: str) -> Tensor:
         """a contiguous scalar field view ``(*nx)`` of the mesh dtype on the GPU"""
@@ -450,6 +459,36 @@ class HipContext:
         self._rc(self.lib.pa_project_correct(self.h, self._ptr(U), self.mesh.dim, self._ptr(p), float(scale),
                                              self._ptr(None if out is None else o), bv))
         return o
+
+    def project_update(self, U: Tensor, phi: Tensor, scale: float, p: Tensor, nrhs: Tensor | None = None, chi: float = 0.0,
+                       bcs: Sequence[Any] | None = None) -> Tensor:
+        """``pa_project_update``: ``U_c -= scale * d_c phi`` on the interior set for every component and ``p += phi`` (``nrhs``
+        given: ``+ chi * nrhs``, every operation rounded on its own) at every node, in one launch, in place; then -- ``bcs``
+        given -- the ordered BC fill of every component of ``U`` as behind ``project_correct``.  ``p``'s fill is the caller's.
+        Returns ``U``."""
+        U = self._vector(U, "project_update")
+        phi = self._field(phi, "project_update phi")
+        p = self._field(p, "project_update p")
+        r = None if nrhs is None else self._field(nrhs, "project_update nrhs")
+        bv, _kb = None, []
+        if bcs is not None:
+            bv = (L.PaBcValues * self.mesh.dim)()
+            for q in range(self.mesh.dim):
+                one, kept = self.bc_values(U, bcs, q)
+                bv[q] = one
+                _kb.append(kept)
+        self._keep["project"] = _kb   # what the enqueued fills still read
+        self._rc(self.lib.pa_project_update(self.h, self._ptr(U), self.mesh.dim, self._ptr(phi), float(scale), self._ptr(p),
+                                            self._ptr(r), float(chi), bv))
+        return U
+
+    def flow_stats(self, U: Tensor) -> tuple[float, float, float, float]:
+        """``pa_flow_stats``: (rate, div_max, div_sq, ke_sq) of the BC-filled vector ``U`` ((dim, *nx), contiguous) in one pass
+        (synchronises)"""
+        U = self._vector(U, "flow_stats")
+        res = (C.c_double * 4)()
+        self._rc(self.lib.pa_flow_stats(self.h, self._ptr(U), self.mesh.dim, res))
+        return float(res[0]), float(res[1]), float(res[2]), float(res[3])
 
     def euler_march(self, phi: Tensor, tmp: Tensor, kind: int, u: float | Tensor, nu: float, dt: float,
                     nsteps: int, source: float | Tensor | None = None) -> Tensor:

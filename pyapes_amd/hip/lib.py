@@ -149,6 +149,8 @@ SIGNATURES: dict[str, tuple[Any, list[Any]]] = {
                                        C.POINTER(PaDiffusivity)]),
     "pa_divergence": (C.c_int, [_VP, _VP, C.c_int, C.c_double, _VP]),
     "pa_project_correct": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_double, _VP, C.POINTER(PaBcValues)]),
+    "pa_project_update": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_double, _VP, _VP, C.c_double, C.POINTER(PaBcValues)]),
+    "pa_flow_stats": (C.c_int, [_VP, _VP, C.c_int, _F64P]),
     "pa_cg_begin": (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_int64]),
     "pa_cg_phase_a": (C.c_int, [_VP]),
     "pa_cg_phase_b": (C.c_int, [_VP]),
@@ -213,10 +215,10 @@ def load_library(path: str | None = None) -> C.CDLL:
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(p)
     # an A/B library named by PYAPES_HIP_LIB (bench_ops.py *_baseline sections) may predate the source term, the velocity, the
-    # momentum march, the diffusivity field or the projection kernels: it runs everything but a call with one of them, which then
-    # fails on the missing symbol
+    # momentum march, the diffusivity field, the projection kernels or the flow diagnostics: it runs everything but a call with
+    # one of them, which then fails on the missing symbol
     older = p != LIB_PATH
-    later = ("pa_momentum_march", "pa_divergence", "pa_project_correct")
+    later = ("pa_momentum_march", "pa_divergence", "pa_project_correct", "pa_project_update", "pa_flow_stats")
     for name, (res, args) in SIGNATURES.items():
         if older and (name.endswith(("_src", "_vel", "_nu")) or name in later) and not hasattr(lib, name):
             continue

@@ -23,11 +23,37 @@ This is an APPROXIMATE projection.  The central divergence and the central gradi
 wavenumber k the two symbols are sin^2(k h) / h^2 and 4 sin^2(k h / 2) / h^2, so the projection removes the fraction
 cos^2(k h / 2) of the mode's divergence and leaves sin^2(k h / 2) of it: the remaining discrete divergence is O(h^2) of the
 original, not rounding.  An exact discrete projection needs the wide Laplacian (which decouples odd and even nodes) or a
-staggered grid; neither is built.  Not built either: the incremental (pressure-carrying) form, slab and axisymmetric meshes.
+staggered grid; neither is built.  Not built either: slab and axisymmetric meshes.
+
+``form=`` on ``project`` / ``ns_step``: ``"chorin"`` (the default) is the splitting above.  ``"incremental"`` and ``"rotational"``
+CARRY the pressure: the predictor feels ``-grad(p^n) / rho`` and the solve is for the increment ``phi``, which is O(dt) of ``p``.
+One step is these statements in this order, every operation rounded on its own in the mesh dtype, the scalars 1 / rho,
+dt / rho, -(rho / dt) and nu dt formed in double and converted once:
+
+    1  B(p)
+    2  src_c = S_c - (1 / rho) grad_c(p)  on the interior set, S_c off it   (``pa_project_correct``, out of place, no fill;
+                                                                            S: ``source`` as a (d, *n) tensor, zeros for None)
+    3  momentum_step(U, nu, dt, config, order, source=src)
+    4  nrhs = -(rho / dt) div(U)                                            (``divergence``)
+    5  phi = +0;  solve  -lap(phi) = nrhs  with phi's BCs -- the homogeneous counterparts of p's;  B(phi)
+    6  U_c <- U_c - (dt / rho) grad_c(phi)  on the interior set;  p <- p + phi  at every node;
+       "rotational":  t = (nu dt) nrhs;  p <- p + t   (p + phi - nu rho div(U*));  then B(U)          (``pa_project_update``)
+    7  B(p);  U's time advances by dt
+
+A fluid at rest under a body force f = grad(p0) / rho with p = p0 is a FIXED POINT of these statements, bit for bit: statement 2
+gives an exact zero, U stays +0, nrhs is a zero, the solve returns after one iteration with phi = +0, and p keeps its bits.
+Chorin's form accelerates that fluid by dt f and cannot restore the balance with the approximate projection (DESIGN.md section 4
+"Incremental form" has the figures).  ``project(..., form=)`` is statements 4 - 7 with ``p`` read as p^n.
+
+``flow_stats(U, dt)``: the CFL rate max sum_a |U_a| / dx_a, the divergence that is left (its maximum and its sum of squares on the
+interior set) and the sum of squares of U, in ONE pass (``pa_flow_stats``).  ``ns_march``: a loop of ``ns_step`` with an optional
+CFL cap on every step's dt.
 """
 from __future__ import annotations
 
 from typing import Any
+
+import math
 
 import torch
 from torch import Tensor
@@ -36,11 +62,12 @@ from ..backend import require_gpu
 from ..hip.context import context_for
 from ..variables import Field
 from .fdm import FDM
-from .march import momentum_step
+from .march import _Component, _diffusivity_of, _momentum_args, momentum_step
 from .ops import Solver
 
 # the default solve of ``project``: CG on  -lap(p) = -rhs
 DEFAULT_SOLVER: dict[str, dict[str, Any]] = {"fdm": {"method": "cg", "tol": 1e-6, "max_it": 1000, "report": False}}
+FORMS = ("chorin", "incremental", "rotational")
 
 
 def _vector_args(U: Any, what: str) -> None:
@@ -77,6 +104,44 @@ def _project_args(U: Any, p: Any, dt: Any, rho: Any, what: str) -> None:
             raise ValueError(f"pyapes_amd: {what}: {name} = {v!r} (a positive number)")
 
 
+def _form_args(U: Field, p: Field, form: Any, phi: Any, nu: Any, what: str) -> None:
+    """the checks of ``form=`` / ``phi=`` (after ``_project_args``), made before a device is touched"""
+    if not isinstance(form, str) or form not in FORMS:
+        raise ValueError(f"pyapes_amd: {what}: form {form!r} (one of {', '.join(FORMS)})")
+    if form == "rotational":
+        if isinstance(nu, (Tensor, Field)):
+            raise NotImplementedError(f"pyapes_amd: {what}: form 'rotational' with a diffusivity field (the term nu rho div(U*) "
+                                      "is defined for a number)")
+        if isinstance(nu, bool) or not isinstance(nu, (float, int)):
+            raise TypeError(f"pyapes_amd: {what}: form 'rotational' needs nu, a number (got {type(nu).__name__})")
+    if phi is None:
+        return
+    if not isinstance(phi, Field) or phi.dim != 1:
+        raise TypeError(f"pyapes_amd: {what}: phi is a scalar Field (got {type(phi).__name__}"
+                        + (f" with {phi.dim} components)" if isinstance(phi, Field) else ")"))
+    if phi is p:
+        raise ValueError(f"pyapes_amd: {what}: phi is p itself (the increment needs a Field of its own)")
+    if phi.mesh is not U.mesh:
+        raise ValueError(f"pyapes_amd: {what}: the increment Field phi lives on another mesh")
+    if phi().dtype != U().dtype:
+        raise ValueError(f"pyapes_amd: {what}: phi dtype {phi().dtype} != U dtype {U().dtype}")
+    if phi().device != U().device:
+        raise ValueError(f"pyapes_amd: {what}: phi on {phi().device}, U on {U().device}")
+
+
+def _increment_of(p: Field, phi: Field | None) -> Field:
+    """the Field that receives the increment: the caller's, or one built once from ``p``'s BC config with every value
+    replaced by 0.0 (the homogeneous counterpart; a face without a value -- periodic -- keeps None) and kept on ``p``"""
+    if phi is not None:
+        return phi
+    phi = getattr(p, "_increment", None)
+    if phi is None or phi.mesh is not p.mesh or phi().dtype != p().dtype or phi().device != p().device:
+        dom = [dict(bc, bc_val=None if bc["bc_val"] is None else 0.0) for bc in p.bc_config["domain"]]
+        phi = Field(p.name + "_increment", 1, p.mesh, {"domain": dom, "obstacle": None})
+        p._increment = phi
+    return phi
+
+
 def _divergence(U: Field, scale: float, out: Tensor | None, what: str) -> Tensor:
     require_gpu(U(), what)
     if not U().is_contiguous():
@@ -107,14 +172,22 @@ def divergence(U: Field, scale: float = 1.0, out: Tensor | None = None) -> Tenso
     return _divergence(U, float(scale), out, "divergence")
 
 
-def project(U: Field, p: Field, dt: float, rho: float = 1.0, solver: dict | None = None) -> dict:
+def project(U: Field, p: Field, dt: float, rho: float = 1.0, solver: dict | None = None, form: str = "chorin",
+            phi: Field | None = None, nu: float | None = None) -> dict:
     """Make ``U`` (approximately, module docstring) divergence-free: solve ``lap(p) = (rho / dt) div(U)`` for the scalar Field
     ``p`` -- with ``p``'s own BCs, from ``p``'s current content -- and correct ``U <- B(U - (dt / rho) grad(p))`` in place.
     ``solver``: the ``{"fdm": {...}}`` dict a ``Solver`` takes (default: CG, tol 1e-6, at most 1000 iterations); the equation
     is handed over as ``-laplacian(1.0, p) == -rhs``, the form that is positive definite.  Returns the solver's report.
-    Nothing is allocated per call beyond the right-hand side."""
+    Nothing is allocated per call beyond the right-hand side.
+
+    ``form`` "incremental" / "rotational" (module docstring, statements 4 - 7): ``p`` is read as p^n and UPDATED by the
+    increment, which is solved for from zero in ``phi`` (a scalar Field with the homogeneous counterparts of ``p``'s BCs; None:
+    built once and kept on ``p``).  "rotational" needs ``nu``, a number.  ``phi`` and ``nu`` are not read by "chorin"."""
     _project_args(U, p, dt, rho, "project")
-    return _project(U, p, float(dt), float(rho), solver, "project")
+    _form_args(U, p, form, phi, nu, "project")
+    if form == "chorin":
+        return _project(U, p, float(dt), float(rho), solver, "project")
+    return _project_increment(U, p, float(dt), float(rho), solver, form, phi, nu, "project")
 
 
 def _project(U: Field, p: Field, dt: float, rho: float, solver: dict | None, what: str) -> dict:
@@ -130,14 +203,132 @@ def _project(U: Field, p: Field, dt: float, rho: float, solver: dict | None, wha
     return report
 
 
+def _project_increment(U: Field, p: Field, dt: float, rho: float, solver: dict | None, form: str, phi: Field | None,
+                       nu: float | None, what: str) -> dict:
+    """statements 4 - 7 of the pressure-carrying forms but the time stamp (module docstring)"""
+    require_gpu(U(), what)
+    ctx = context_for(U.mesh)
+    phi = _increment_of(p, phi)
+    nrhs = _divergence(U, -(rho / dt), ctx.work("projection nrhs", 1), what)
+    if not phi().is_contiguous():
+        phi.set_var_tensor(torch.empty_like(p()))
+    phi().zero_()                                            # no state between calls: a step on a used mesh is a fresh one
+    sol = Solver(DEFAULT_SOLVER if solver is None else solver)
+    sol.set_eq(-FDM().laplacian(1.0, phi) == nrhs)
+    report = sol.solve()
+    phi.apply_bcs()
+    if not p().is_contiguous():
+        p.set_var_tensor(p().contiguous())
+    ctx.bind_bcs(U(), U.bcs, 0)
+    rot = form == "rotational"
+    ctx.project_update(U(), phi()[0], dt / rho, p()[0], nrhs[0] if rot else None, float(nu) * dt if rot else 0.0, U.bcs)
+    p.apply_bcs()
+    return report
+
+
+def _source_tensor(ctx: Any, U: Field, srcs: list | None) -> Tensor:
+    """the per-component sources ``_momentum_args`` resolved, as the work tensor S (d, *n): zeros where there is none"""
+    S = ctx.work("projection S", U.dim)
+    S.zero_()
+    for c, e in enumerate(srcs or ()):
+        if isinstance(e, Tensor):
+            S[c].copy_(e.reshape(S[c].shape))
+        elif e is not None:
+            S[c].fill_(float(e))
+    return S
+
+
 def ns_step(U: Field, p: Field, nu: float | Tensor | Field, dt: float, config: dict | None = None, order: int = 3, *,
-            rho: float = 1.0, source: Tensor | Field | tuple | list | None = None, solver: dict | None = None) -> dict:
-    """One step of the incompressible Navier-Stokes equations in Chorin's non-incremental form: ``momentum_step(U, nu, dt,
-    config, order, source=source)``, then ``project(U, p, dt, rho, solver)``.  ``U``'s time advances by ``dt``; returns the
-    solver's report.  Every check of both halves is made before a device is touched."""
+            rho: float = 1.0, source: Tensor | Field | tuple | list | None = None, solver: dict | None = None,
+            form: str = "chorin", phi: Field | None = None) -> dict:
+    """One step of the incompressible Navier-Stokes equations.  ``form`` "chorin" (the default), Chorin's non-incremental
+    form: ``momentum_step(U, nu, dt, config, order, source=source)``, then ``project(U, p, dt, rho, solver)``.  "incremental"
+    and "rotational": the seven statements of the module docstring -- the predictor feels ``-grad(p) / rho``, the solve is
+    for the increment ``phi`` (None: built once from ``p``'s BCs, kept on ``p``), ``p`` is updated -- which hold a balanced
+    state (``source = grad(p) / rho`` on a fluid at rest) bit for bit.  ``U``'s time advances by ``dt``; returns the solver's
+    report.  Every check of both halves is made before a device is touched."""
     _project_args(U, p, dt, rho, "ns_step")
-    momentum_step(U, nu, dt, config, order, source=source)
-    report = _project(U, p, float(dt), float(rho), solver, "ns_step")
+    _form_args(U, p, form, phi, nu, "ns_step")
+    if form == "chorin":
+        momentum_step(U, nu, dt, config, order, source=source)
+        report = _project(U, p, float(dt), float(rho), solver, "ns_step")
+    else:
+        _, _, srcs = _momentum_args(U, config, order, None, source, "ns_step")
+        _diffusivity_of(_Component(U), nu, config, "ns_step")
+        require_gpu(U(), "ns_step")
+        ctx = context_for(U.mesh)
+        if not U().is_contiguous():
+            U.set_var_tensor(U().contiguous())
+        p.apply_bcs()
+        S = _source_tensor(ctx, U, srcs)
+        src = ctx.work("projection src", U.dim)
+        ctx.bind_bcs(U(), U.bcs, 0)                          # the interior set is that of U's faces
+        ctx.project_correct(S, p()[0], 1.0 / float(rho), None, out=src)
+        momentum_step(U, nu, dt, config, order, source=src)
+        report = _project_increment(U, p, float(dt), float(rho), solver, form, phi, nu, "ns_step")
     if hasattr(U, "_t"):
         U.update_time(dt)
     return report
+
+
+def flow_stats(U: Field, dt: float | None = None) -> dict:
+    """The diagnostics of a time loop, of the vector Field ``U`` in ONE pass (``pa_flow_stats``; ``U.apply_bcs()`` runs
+    first): ``rate`` = max over all nodes of sum_a |U_a| / dx_a, ``div_max`` = max |div(U)| and ``div_sq`` = sum div(U)^2 over
+    the interior set (``divergence``'s values), ``ke_sq`` = sum over all nodes of |U|^2; a NaN in ``U`` makes the maximum it
+    contributes to NaN.  With ``dt`` also ``cfl = dt * rate``, ``div_l2 = sqrt(div_sq * cell volume)`` and ``ke = 0.5 * ke_sq *
+    cell volume``.  Synchronises."""
+    _vector_args(U, "flow_stats")
+    if dt is not None:
+        if isinstance(dt, bool) or not isinstance(dt, (float, int)):
+            raise TypeError(f"pyapes_amd: flow_stats: dt is a number or None (got {type(dt).__name__})")
+        if not dt > 0:
+            raise ValueError(f"pyapes_amd: flow_stats: dt = {dt!r} (a positive number)")
+    require_gpu(U(), "flow_stats")
+    if not U().is_contiguous():
+        U.set_var_tensor(U().contiguous())
+    U.apply_bcs()
+    rate, div_max, div_sq, ke_sq = context_for(U.mesh).flow_stats(U())
+    out = {"rate": rate, "div_max": div_max, "div_sq": div_sq, "ke_sq": ke_sq}
+    if dt is not None:
+        vol = math.prod(float(h) for h in U.mesh.dx_list)
+        out.update(cfl=float(dt) * rate, div_l2=math.sqrt(div_sq * vol), ke=0.5 * ke_sq * vol)
+    return out
+
+
+def ns_march(U: Field, p: Field, nu: float | Tensor | Field, dt: float, nsteps: int, config: dict | None = None, order: int = 3,
+             *, rho: float = 1.0, source: Tensor | Field | tuple | list | None = None, solver: dict | None = None,
+             form: str = "incremental", phi: Field | None = None, cfl: float | None = None) -> dict:
+    """``nsteps`` steps of ``ns_step`` (a Python loop: every step solves).  ``cfl`` a positive number: step k takes
+    ``dt_k = min(dt, cfl / rate_k)`` with ``rate_k`` from ``flow_stats`` before the step, which fills ``U``'s faces (``dt``
+    when the fluid is at rest); a
+    rate that is not finite raises ``RuntimeError`` and names the step.  Returns ``{"steps", "t", "dt": [...], "itr": [...],
+    "converge": [...]}``: the steps taken, the time covered, and per step its dt and the solver's report."""
+    _project_args(U, p, dt, rho, "ns_march")
+    _form_args(U, p, form, phi, nu, "ns_march")
+    if isinstance(nsteps, bool) or not isinstance(nsteps, int):
+        raise TypeError(f"pyapes_amd: ns_march: nsteps is an int (got {type(nsteps).__name__})")
+    if nsteps < 0:
+        raise ValueError(f"pyapes_amd: ns_march: nsteps = {nsteps!r} (not negative)")
+    if cfl is not None:
+        if isinstance(cfl, bool) or not isinstance(cfl, (float, int)):
+            raise TypeError(f"pyapes_amd: ns_march: cfl is a number or None (got {type(cfl).__name__})")
+        if not (cfl > 0 and math.isfinite(cfl)):
+            raise ValueError(f"pyapes_amd: ns_march: cfl = {cfl!r} (a positive number)")
+    _momentum_args(U, config, order, None, source, "ns_march")
+    _diffusivity_of(_Component(U), nu, config, "ns_march")
+    out: dict[str, Any] = {"steps": 0, "t": 0.0, "dt": [], "itr": [], "converge": []}
+    for k in range(nsteps):
+        dt_k = float(dt)
+        if cfl is not None:
+            rate = flow_stats(U)["rate"]
+            if not math.isfinite(rate):
+                raise RuntimeError(f"pyapes_amd: ns_march: step {k}: the CFL rate of U is {rate!r}")
+            if rate > 0.0:
+                dt_k = min(dt_k, float(cfl) / rate)
+        rep = ns_step(U, p, nu, dt_k, config, order, rho=rho, source=source, solver=solver, form=form, phi=phi)
+        out["steps"] += 1
+        out["t"] += dt_k
+        out["dt"].append(dt_k)
+        out["itr"].append(rep["itr"])
+        out["converge"].append(rep["converge"])
+    return out
