@@ -26,29 +26,12 @@ __global__ void __launch_bounds__(PA_BLOCK) k_divergence(DevGeom G, ProjVec<T> U
     int64_t i, j, k;
     pa_decode(G, idx, i, j, k);
     T v = (T)0;
-    if (pa_in_S(G, i, j, k)) {
-      T s = (T)0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        if (!G.act[a]) continue;
-        FieldAcc<T> acc{U.v[a]};
-        T xp, xm;
-        pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T d = xp - xm;
-        d = d * U.h[a];
-        s = s + d;
-      }
-      v = scale * s;
-    }
+    if (pa_in_S(G, i, j, k)) v = scale * proj_div_sum<T>(G, U, i, j, k);
     __builtin_nontemporal_store(v, out + idx);
   }
 }
 
-// U.v[a].p: component of internal axis a, read at the cell only; o[a]: where it goes (o[a] == U.v[a].p: in place -- a cell's
-// value is read and written by the same lane, and no lane reads another cell of U)
-template <typename T>
-struct ProjOut { T* o[3]; };
-
+// U.v[a].p: component of internal axis a, read at the cell only; O.o[a]: where it goes
 template <typename T>
 __global__ void __launch_bounds__(PA_BLOCK) k_project_correct(DevGeom G, ProjVec<T> U, Vec<T> pv, T scale, ProjOut<T> O) {
   FieldAcc<T> acc{pv};
@@ -60,22 +43,13 @@ __global__ void __launch_bounds__(PA_BLOCK) k_project_correct(DevGeom G, ProjVec
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       if (!G.act[a]) continue;
-      T v = __builtin_nontemporal_load(U.v[a].p + idx);
-      if (in) {
-        T xp, xm;
-        pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T g = xp - xm;
-        g = g * U.h[a];
-        g = scale * g;
-        v = v - g;
-      }
-      O.o[a][idx] = v;
+      O.o[a][idx] = proj_corrected<T>(G, U, acc, scale, a, idx, i, j, k, in);
     }
   }
 }
 
-// the update of the incremental (pressure-carrying) forms: k_project_correct's body on the d components with the increment phi
-// in the place of p, in place, and at the same cell -- on and off the interior set --
+// the update of the incremental (pressure-carrying) forms: the correction of the d components by the increment phi, in place,
+// and at the same cell -- on and off the interior set --
 //   q = p + phi;  nrhs given: t = chi * nrhs; q = q + t;  p = q
 // U and p are read and written by the same lane only; phi's neighbours are plain loads, old U, old p and nrhs non-temporal
 template <typename T>
@@ -90,16 +64,7 @@ __global__ void __launch_bounds__(PA_BLOCK) k_project_update(DevGeom G, ProjVec<
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       if (!G.act[a]) continue;
-      T v = __builtin_nontemporal_load(U.v[a].p + idx);
-      if (in) {
-        T xp, xm;
-        pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T g = xp - xm;
-        g = g * U.h[a];
-        g = scale * g;
-        v = v - g;
-      }
-      O.o[a][idx] = v;
+      O.o[a][idx] = proj_corrected<T>(G, U, acc, scale, a, idx, i, j, k, in);
     }
     T q = __builtin_nontemporal_load(p + idx);
     q = q + phiv.p[idx];
@@ -138,50 +103,53 @@ static int fill_components(pa_ctx* c, void* out, int ncomp, const pa_bc_values* 
   return rc;
 }
 
-// the kernel, then -- bcv non-null -- the fill
+// the correction of U by the scalar x into `out`; p non-null: the update, p (and nrhs) carried along.  The kernel, then --
+// bcv non-null -- the fill
 template <typename T>
-static int correct_t(pa_ctx* c, const void* U, int ncomp, const void* p, double scale, void* out, const pa_bc_values* bcv) {
-  static int dbg = -1;
-  if (proj_dbg(&dbg, 64))
-    fprintf(stderr, "[pyapes_hip] k_project_correct%s: generic kernel, %lld cells\n", out == U ? " (in place)" : "", (long long)c->G.ncell);
-  const int sh = 3 - c->ndim;
-  const int64_t nc = c->G.ncell;
-  ProjOut<T> O;
-  for (int a = 0; a < 3; ++a) O.o[a] = (T*)out + (int64_t)(a >= sh ? a - sh : 0) * nc;
-  hipLaunchKernelGGL(k_project_correct<T>, dim3(pa_grid_blocks(nc)), dim3(PA_BLOCK), 0, c->stream, c->G, proj_vec<T>(c, U),
-                     pa_vec_self<T>(c, (const T*)p), (T)scale, O);
+static int correct_t(pa_ctx* c, const void* U, int ncomp, const void* x, double scale, void* out, void* p, const void* nrhs,
+                     double chi, const pa_bc_values* bcv) {
+  static int dbg[2] = {-1, -1};
+  if (proj_dbg(&dbg[p != nullptr], 64))
+    fprintf(stderr, "[pyapes_hip] k_project_%s%s: generic kernel, %lld cells\n", p ? "update" : "correct",
+            p ? (nrhs ? " (rotational)" : "") : (out == U ? " (in place)" : ""), (long long)c->G.ncell);
+  const dim3 grid(pa_grid_blocks(c->G.ncell)), block(PA_BLOCK);
+  const ProjVec<T> Uv = proj_vec<T>(c, U);
+  const Vec<T> xv = pa_vec_self<T>(c, (const T*)x);
+  if (p)
+    hipLaunchKernelGGL(k_project_update<T>, grid, block, 0, c->stream, c->G, Uv, xv, (T)scale, proj_out<T>(c, out), (T*)p,
+                       (const T*)nrhs, (T)chi);
+  else
+    hipLaunchKernelGGL(k_project_correct<T>, grid, block, 0, c->stream, c->G, Uv, xv, (T)scale, proj_out<T>(c, out));
   PA_HIP(c, hipGetLastError());
   return bcv ? fill_components<T>(c, out, ncomp, bcv) : PA_OK;
 }
 
-template <typename T>
-static int update_t(pa_ctx* c, void* U, int ncomp, const void* phi, double scale, void* p, const void* nrhs, double chi,
-                    const pa_bc_values* bcv) {
-  static int dbg = -1;
-  if (proj_dbg(&dbg, 64))
-    fprintf(stderr, "[pyapes_hip] k_project_update%s: generic kernel, %lld cells\n", nrhs ? " (rotational)" : "", (long long)c->G.ncell);
-  const int sh = 3 - c->ndim;
-  const int64_t nc = c->G.ncell;
-  ProjOut<T> O;
-  for (int a = 0; a < 3; ++a) O.o[a] = (T*)U + (int64_t)(a >= sh ? a - sh : 0) * nc;
-  hipLaunchKernelGGL(k_project_update<T>, dim3(pa_grid_blocks(nc)), dim3(PA_BLOCK), 0, c->stream, c->G, proj_vec<T>(c, U),
-                     pa_vec_self<T>(c, (const T*)phi), (T)scale, O, (T*)p, (const T*)nrhs, (T)chi);
-  PA_HIP(c, hipGetLastError());
-  return bcv ? fill_components<T>(c, U, ncomp, bcv) : PA_OK;
-}
+// one scalar buffer of a call and what is said when it lies on a vector buffer or on a scalar buffer named after it
+struct ProjScalar {
+  const void* p;
+  const char* refusal;
+};
 
-// a face array of `bcv` (null: no fill, nothing to check) against the vector and the scalar buffers of a call
-static bool face_overlaps(const pa_ctx* c, const pa_bc_values* bcv, int ncomp, std::initializer_list<const void*> vecs,
-                          std::initializer_list<const void*> scalars) {
-  if (!bcv) return false;
+// the overlap refusals of a correction, stated once: every scalar against the vectors and against the scalars after it, then
+// every face array of `bcv` (null: no fill, nothing to check) against everything.  Null buffers are not part of the call.
+static int check_overlaps(pa_ctx* c, const char* who, int ncomp, std::initializer_list<const void*> vecs,
+                          std::initializer_list<ProjScalar> scalars, const pa_bc_values* bcv) {
   const size_t cbytes = (size_t)c->G.ncell * c->esize, vbytes = cbytes * (size_t)ncomp;
+  for (const ProjScalar* s = scalars.begin(); s != scalars.end(); ++s) {
+    bool hit = overlaps(s->p, cbytes, vecs, vbytes);
+    for (const ProjScalar* t = s + 1; t != scalars.end(); ++t) hit = hit || overlaps(s->p, cbytes, {t->p}, cbytes);
+    if (hit) { pa_set_err(c, "%s: %s", who, s->refusal); return PA_E_ARG; }
+  }
   const int64_t n[3] = {c->G.n0, c->G.n1, c->G.n2};
-  for (int q = 0; q < ncomp; ++q)
+  for (int q = 0; bcv && q < ncomp; ++q)
     for (int f = 0; f < 2 * c->ndim; ++f) {
+      const void* face = bcv[q].vals[f];
       const size_t fbytes = cbytes / (size_t)n[(f >> 1) + 3 - c->ndim];
-      if (overlaps(bcv[q].vals[f], fbytes, vecs, vbytes) || overlaps(bcv[q].vals[f], fbytes, scalars, cbytes)) return true;
+      bool hit = overlaps(face, fbytes, vecs, vbytes);
+      for (const ProjScalar& s : scalars) hit = hit || overlaps(face, fbytes, {s.p}, cbytes);
+      if (hit) { pa_set_err(c, "%s: a BC face array must not overlap a buffer of the call", who); return PA_E_ARG; }
     }
-  return false;
+  return PA_OK;
 }
 
 extern "C" {
@@ -201,16 +169,13 @@ int pa_project_correct(pa_ctx* c, void* U, int ncomp, const void* p, double scal
   if (int rc = check_projection_call(c, who, ncomp)) return rc;
   if (!U || !p) { pa_set_err(c, "%s: U and p are needed", who); return PA_E_ARG; }
   if (!out) out = U;
-  const size_t cbytes = (size_t)c->G.ncell * c->esize, vbytes = cbytes * (size_t)ncomp;
-  if (overlaps(p, cbytes, {U, out}, vbytes)) { pa_set_err(c, "%s: p must not overlap U or out", who); return PA_E_ARG; }
+  if (int rc = check_overlaps(c, who, ncomp, {U, out}, {{p, "p must not overlap U or out"}}, bcv)) return rc;
+  const size_t vbytes = (size_t)c->G.ncell * c->esize * (size_t)ncomp;
   if (out != U && overlaps(out, vbytes, {U}, vbytes)) { pa_set_err(c, "%s: out is U itself (in place) or a buffer of its own", who); return PA_E_ARG; }
-  if (face_overlaps(c, bcv, ncomp, {U, out}, {p})) {
-    pa_set_err(c, "%s: a BC face array must not overlap a buffer of the call", who);
-    return PA_E_ARG;
-  }
   PaRange range_("pyapes projection correction");
   PA_HIP(c, hipSetDevice(c->device));
-  return c->dtype == PA_F64 ? correct_t<double>(c, U, ncomp, p, scale, out, bcv) : correct_t<float>(c, U, ncomp, p, scale, out, bcv);
+  return c->dtype == PA_F64 ? correct_t<double>(c, U, ncomp, p, scale, out, nullptr, nullptr, 0.0, bcv)
+                            : correct_t<float>(c, U, ncomp, p, scale, out, nullptr, nullptr, 0.0, bcv);
 }
 
 int pa_project_update(pa_ctx* c, void* U, int ncomp, const void* phi, double scale, void* p, const void* nrhs, double chi,
@@ -218,24 +183,12 @@ int pa_project_update(pa_ctx* c, void* U, int ncomp, const void* phi, double sca
   const char* who = "pa_project_update";
   if (int rc = check_projection_call(c, who, ncomp)) return rc;
   if (!U || !phi || !p) { pa_set_err(c, "%s: U, phi and p are needed", who); return PA_E_ARG; }
-  const size_t cbytes = (size_t)c->G.ncell * c->esize, vbytes = cbytes * (size_t)ncomp;
-  if (overlaps(phi, cbytes, {U}, vbytes) || overlaps(phi, cbytes, {p, nrhs}, cbytes)) {
-    pa_set_err(c, "%s: phi must not overlap U, p or nrhs", who);
-    return PA_E_ARG;
-  }
-  if (overlaps(p, cbytes, {U}, vbytes) || overlaps(p, cbytes, {nrhs}, cbytes)) {
-    pa_set_err(c, "%s: p must not overlap U or nrhs", who);
-    return PA_E_ARG;
-  }
-  if (overlaps(nrhs, cbytes, {U}, vbytes)) { pa_set_err(c, "%s: nrhs must not overlap U", who); return PA_E_ARG; }
-  if (face_overlaps(c, bcv, ncomp, {U}, {phi, p, nrhs})) {
-    pa_set_err(c, "%s: a BC face array must not overlap a buffer of the call", who);
-    return PA_E_ARG;
-  }
+  if (int rc = check_overlaps(c, who, ncomp, {U}, {{phi, "phi must not overlap U, p or nrhs"}, {p, "p must not overlap U or nrhs"},
+                                                    {nrhs, "nrhs must not overlap U"}}, bcv)) return rc;
   PaRange range_("pyapes projection update");
   PA_HIP(c, hipSetDevice(c->device));
-  return c->dtype == PA_F64 ? update_t<double>(c, U, ncomp, phi, scale, p, nrhs, chi, bcv)
-                            : update_t<float>(c, U, ncomp, phi, scale, p, nrhs, chi, bcv);
+  return c->dtype == PA_F64 ? correct_t<double>(c, U, ncomp, phi, scale, U, p, nrhs, chi, bcv)
+                            : correct_t<float>(c, U, ncomp, phi, scale, U, p, nrhs, chi, bcv);
 }
 
 }  // extern "C"

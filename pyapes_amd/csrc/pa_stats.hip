@@ -5,8 +5,8 @@
 // The arithmetic is a definition of this library.  Per node, every operation rounded on its own in the grid dtype (no FMA),
 // q_a = 1 / dx_a and h_a = 0.5 / dx_a formed in double on the host and converted once, axes ascending:
 //   rate      max over ALL nodes of s:          r = |U_a| * q_a;  s = s + r                      (s starts at +0)
-//   div_max   max over the interior set of |s|: d = U_a[+1]_a - U_a[-1]_a;  d = d * h_a;  s = s + d   (k_divergence's sum)
-//   div_sq    sum over the interior set of (double)(s * s), that same s
+//   div_max   max over the interior set of |s|: d = U_a[+1]_a - U_a[-1]_a;  d = d * h_a;  s = s + d   (proj_div_sum)
+//   div_sq    sum over the interior set of (double)(s * s), that s
 //   ke_sq     sum over all nodes and axes of (double)(U_a * U_a)
 // The maxima are carried as doubles (an exact conversion) and a NaN in any contribution makes that maximum NaN (pa_max_nan);
 // the sums are accumulated in double in the order the grid gives them.
@@ -42,17 +42,7 @@ __global__ void __launch_bounds__(PA_BLOCK) k_flow_stats(DevGeom G, ProjVec<T> U
     }
     mx[0] = pa_max_nan(mx[0], (double)s);
     if (pa_in_S(G, i, j, k)) {
-      T d = (T)0;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        if (!G.act[a]) continue;
-        FieldAcc<T> acc{U.v[a]};
-        T xp, xm;
-        pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T t = xp - xm;
-        t = t * U.h[a];
-        d = d + t;
-      }
+      const T d = proj_div_sum<T>(G, U, i, j, k);
       mx[1] = pa_max_nan(mx[1], (double)pa_abs(d));
       T e = d * d;
       sum[0] += (double)e;

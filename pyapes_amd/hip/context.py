@@ -383,6 +383,18 @@ class HipContext:
                 bv.vals[f] = arr.data_ptr()
         return bv, keep
 
+    def _component_bcs(self, U: Tensor, bcs: Sequence[Any] | None) -> tuple[Any, list[list[Tensor]]]:
+        """``bc_values`` of every component of the vector ``U`` as one ``pa_bc_values`` array, and the arrays it points into
+        (``bcs`` None: no fill -- a null array, nothing to keep)"""
+        if bcs is None:
+            return None, []
+        bv = (L.PaBcValues * self.mesh.dim)()
+        keep = []
+        for q in range(self.mesh.dim):
+            bv[q], kept = self.bc_values(U, bcs, q)
+            keep.append(kept)
+        return bv, keep
+
     def momentum_march(self, U: Tensor, w1: Tensor, w2: Tensor | None, order: int, kind: int,
                        vel: Sequence[float | Tensor] | None, nu: float | Tensor, dt: float, nsteps: int,
                        sources: Sequence[float | Tensor | None] | None, bcs: Sequence[Any]) -> Tensor:
@@ -406,12 +418,7 @@ class HipContext:
                 if one is not None:
                     ps[q].has, ps[q].value, ps[q].field = 1, one.value, one.field
                     _ks.append(kept)
-        bv = (L.PaBcValues * nd)()
-        _kb = []
-        for q in range(nd):
-            one, kept = self.bc_values(U, bcs, q)
-            bv[q] = one
-            _kb.append(kept)
+        bv, _kb = self._component_bcs(U, bcs)
         pd, _kd = self._diffusivity(nu)
         self._keep["momentum"] = (_kv, _ks, _kb, _kd)   # what the enqueued launches still read
         if pd is not None:   # a diffusivity field: the scalar nu is not read
@@ -448,13 +455,7 @@ class HipContext:
         U = self._vector(U, "project_correct")
         p = self._field(p, "project_correct p")
         o = U if out is None else self._vector(out, "project_correct out")
-        bv, _kb = None, []
-        if bcs is not None:
-            bv = (L.PaBcValues * self.mesh.dim)()
-            for q in range(self.mesh.dim):
-                one, kept = self.bc_values(U, bcs, q)
-                bv[q] = one
-                _kb.append(kept)
+        bv, _kb = self._component_bcs(U, bcs)
         self._keep["project"] = _kb   # what the enqueued fills still read
         self._rc(self.lib.pa_project_correct(self.h, self._ptr(U), self.mesh.dim, self._ptr(p), float(scale),
                                              self._ptr(None if out is None else o), bv))
@@ -470,13 +471,7 @@ class HipContext:
         phi = self._field(phi, "project_update phi")
         p = self._field(p, "project_update p")
         r = None if nrhs is None else self._field(nrhs, "project_update nrhs")
-        bv, _kb = None, []
-        if bcs is not None:
-            bv = (L.PaBcValues * self.mesh.dim)()
-            for q in range(self.mesh.dim):
-                one, kept = self.bc_values(U, bcs, q)
-                bv[q] = one
-                _kb.append(kept)
+        bv, _kb = self._component_bcs(U, bcs)
         self._keep["project"] = _kb   # what the enqueued fills still read
         self._rc(self.lib.pa_project_update(self.h, self._ptr(U), self.mesh.dim, self._ptr(phi), float(scale), self._ptr(p),
                                             self._ptr(r), float(chi), bv))

@@ -85,27 +85,39 @@ def _vector_args(U: Any, what: str) -> None:
         raise NotImplementedError(f"pyapes_amd: {what}: a vector field with one component per mesh axis ({U.dim} for {mesh.dim})")
 
 
-def _project_args(U: Any, p: Any, dt: Any, rho: Any, what: str) -> None:
-    """every check of ``project`` / ``ns_step``, made before a device is touched"""
+def _number(name: str, v: Any, what: str, positive: bool = True, optional: bool = False) -> None:
+    """``v`` is a number, not a bool (``optional``: or None), and -- ``positive`` -- > 0, which refuses NaN"""
+    if v is None and optional:
+        return
+    if isinstance(v, bool) or not isinstance(v, (float, int)):
+        raise TypeError(f"pyapes_amd: {what}: {name} is a number{' or None' if optional else ''} (got {type(v).__name__})")
+    if positive and not v > 0:
+        raise ValueError(f"pyapes_amd: {what}: {name} = {v!r} (a positive number)")
+
+
+_SCALAR_FIELDS = {"p": "pressure Field", "phi": "increment Field phi"}
+
+
+def _scalar_field(name: str, f: Any, U: Field, what: str) -> None:
+    """``f`` (``p`` or ``phi``) is a scalar Field on ``U``'s mesh, of ``U``'s dtype and device"""
+    if not isinstance(f, Field) or f.dim != 1:
+        raise TypeError(f"pyapes_amd: {what}: {name} is a scalar Field (got {type(f).__name__}"
+                        + (f" with {f.dim} components)" if isinstance(f, Field) else ")"))
+    if f.mesh is not U.mesh:
+        raise ValueError(f"pyapes_amd: {what}: the {_SCALAR_FIELDS[name]} lives on another mesh")
+    if f().dtype != U().dtype:
+        raise ValueError(f"pyapes_amd: {what}: {name} dtype {f().dtype} != U dtype {U().dtype}")
+    if f().device != U().device:
+        raise ValueError(f"pyapes_amd: {what}: {name} on {f().device}, U on {U().device}")
+
+
+def _project_args(U: Any, p: Any, dt: Any, rho: Any, form: Any, phi: Any, nu: Any, what: str) -> None:
+    """every check of ``project`` / ``ns_step`` / ``ns_march`` on the velocity, the pressure, the numbers and ``form=`` /
+    ``phi=``, made before a device is touched"""
     _vector_args(U, what)
-    if not isinstance(p, Field) or p.dim != 1:
-        raise TypeError(f"pyapes_amd: {what}: p is a scalar Field (got {type(p).__name__}"
-                        + (f" with {p.dim} components)" if isinstance(p, Field) else ")"))
-    if p.mesh is not U.mesh:
-        raise ValueError(f"pyapes_amd: {what}: the pressure Field lives on another mesh")
-    if p().dtype != U().dtype:
-        raise ValueError(f"pyapes_amd: {what}: p dtype {p().dtype} != U dtype {U().dtype}")
-    if p().device != U().device:
-        raise ValueError(f"pyapes_amd: {what}: p on {p().device}, U on {U().device}")
-    for name, v in (("dt", dt), ("rho", rho)):
-        if isinstance(v, bool) or not isinstance(v, (float, int)):
-            raise TypeError(f"pyapes_amd: {what}: {name} is a number (got {type(v).__name__})")
-        if not v > 0:
-            raise ValueError(f"pyapes_amd: {what}: {name} = {v!r} (a positive number)")
-
-
-def _form_args(U: Field, p: Field, form: Any, phi: Any, nu: Any, what: str) -> None:
-    """the checks of ``form=`` / ``phi=`` (after ``_project_args``), made before a device is touched"""
+    _scalar_field("p", p, U, what)
+    _number("dt", dt, what)
+    _number("rho", rho, what)
     if not isinstance(form, str) or form not in FORMS:
         raise ValueError(f"pyapes_amd: {what}: form {form!r} (one of {', '.join(FORMS)})")
     if form == "rotational":
@@ -114,19 +126,10 @@ def _form_args(U: Field, p: Field, form: Any, phi: Any, nu: Any, what: str) -> N
                                       "is defined for a number)")
         if isinstance(nu, bool) or not isinstance(nu, (float, int)):
             raise TypeError(f"pyapes_amd: {what}: form 'rotational' needs nu, a number (got {type(nu).__name__})")
-    if phi is None:
-        return
-    if not isinstance(phi, Field) or phi.dim != 1:
-        raise TypeError(f"pyapes_amd: {what}: phi is a scalar Field (got {type(phi).__name__}"
-                        + (f" with {phi.dim} components)" if isinstance(phi, Field) else ")"))
-    if phi is p:
-        raise ValueError(f"pyapes_amd: {what}: phi is p itself (the increment needs a Field of its own)")
-    if phi.mesh is not U.mesh:
-        raise ValueError(f"pyapes_amd: {what}: the increment Field phi lives on another mesh")
-    if phi().dtype != U().dtype:
-        raise ValueError(f"pyapes_amd: {what}: phi dtype {phi().dtype} != U dtype {U().dtype}")
-    if phi().device != U().device:
-        raise ValueError(f"pyapes_amd: {what}: phi on {phi().device}, U on {U().device}")
+    if phi is not None:
+        if phi is p:
+            raise ValueError(f"pyapes_amd: {what}: phi is p itself (the increment needs a Field of its own)")
+        _scalar_field("phi", phi, U, what)
 
 
 def _increment_of(p: Field, phi: Field | None) -> Field:
@@ -159,8 +162,7 @@ def divergence(U: Field, scale: float = 1.0, out: Tensor | None = None) -> Tenso
     tensor (``out``, shaped like it or like one component, is filled and returned when given).  ``U.apply_bcs()`` runs first:
     the stencil reads the BC-filled face values.  One kernel, ``pa_divergence`` (module docstring)."""
     _vector_args(U, "divergence")
-    if isinstance(scale, bool) or not isinstance(scale, (float, int)):
-        raise TypeError(f"pyapes_amd: divergence: scale is a number (got {type(scale).__name__})")
+    _number("scale", scale, "divergence", positive=False)
     if out is not None:
         comp = tuple(U().shape[1:])
         if not isinstance(out, Tensor) or tuple(out.shape) not in ((1, *comp), comp):
@@ -183,45 +185,39 @@ def project(U: Field, p: Field, dt: float, rho: float = 1.0, solver: dict | None
     ``form`` "incremental" / "rotational" (module docstring, statements 4 - 7): ``p`` is read as p^n and UPDATED by the
     increment, which is solved for from zero in ``phi`` (a scalar Field with the homogeneous counterparts of ``p``'s BCs; None:
     built once and kept on ``p``).  "rotational" needs ``nu``, a number.  ``phi`` and ``nu`` are not read by "chorin"."""
-    _project_args(U, p, dt, rho, "project")
-    _form_args(U, p, form, phi, nu, "project")
-    if form == "chorin":
-        return _project(U, p, float(dt), float(rho), solver, "project")
-    return _project_increment(U, p, float(dt), float(rho), solver, form, phi, nu, "project")
+    _project_args(U, p, dt, rho, form, phi, nu, "project")
+    return _project(U, p, float(dt), float(rho), solver, form, phi, nu, "project")
 
 
-def _project(U: Field, p: Field, dt: float, rho: float, solver: dict | None, what: str) -> dict:
+def _project(U: Field, p: Field, dt: float, rho: float, solver: dict | None, form: str, phi: Field | None, nu: float | None,
+             what: str) -> dict:
+    """statements 4 - 7 of the module docstring but the time stamp.  "chorin" is the same sequence with ``p`` itself solved
+    for, from its current content, a right-hand side of its own, and the plain correction at the end"""
+    carried = form != "chorin"
+    x, out = p, None                                         # the Field that is solved for; where the right-hand side goes
+    if carried:
+        require_gpu(U(), what)
+        out = context_for(U.mesh).work("projection nrhs", 1)
+        x = _increment_of(p, phi)
     # -rhs, formed by the kernel itself: (-s) * x and -(s * x) are the same bits
-    nrhs = _divergence(U, -(rho / dt), None, what)
+    nrhs = _divergence(U, -(rho / dt), out, what)
+    if carried:
+        if not x().is_contiguous():
+            x.set_var_tensor(torch.empty_like(p()))
+        x().zero_()                                          # no state between calls: a step on a used mesh is a fresh one
     sol = Solver(DEFAULT_SOLVER if solver is None else solver)
-    sol.set_eq(-FDM().laplacian(1.0, p) == nrhs)
+    sol.set_eq(-FDM().laplacian(1.0, x) == nrhs)
     report = sol.solve()
-    p.apply_bcs()
-    ctx = context_for(U.mesh)
-    ctx.bind_bcs(U(), U.bcs, 0)
-    ctx.project_correct(U(), p()[0], dt / rho, U.bcs)
-    return report
-
-
-def _project_increment(U: Field, p: Field, dt: float, rho: float, solver: dict | None, form: str, phi: Field | None,
-                       nu: float | None, what: str) -> dict:
-    """statements 4 - 7 of the pressure-carrying forms but the time stamp (module docstring)"""
-    require_gpu(U(), what)
-    ctx = context_for(U.mesh)
-    phi = _increment_of(p, phi)
-    nrhs = _divergence(U, -(rho / dt), ctx.work("projection nrhs", 1), what)
-    if not phi().is_contiguous():
-        phi.set_var_tensor(torch.empty_like(p()))
-    phi().zero_()                                            # no state between calls: a step on a used mesh is a fresh one
-    sol = Solver(DEFAULT_SOLVER if solver is None else solver)
-    sol.set_eq(-FDM().laplacian(1.0, phi) == nrhs)
-    report = sol.solve()
-    phi.apply_bcs()
-    if not p().is_contiguous():
+    x.apply_bcs()
+    if carried and not p().is_contiguous():
         p.set_var_tensor(p().contiguous())
+    ctx = context_for(U.mesh)
     ctx.bind_bcs(U(), U.bcs, 0)
+    if not carried:
+        ctx.project_correct(U(), p()[0], dt / rho, U.bcs)
+        return report
     rot = form == "rotational"
-    ctx.project_update(U(), phi()[0], dt / rho, p()[0], nrhs[0] if rot else None, float(nu) * dt if rot else 0.0, U.bcs)
+    ctx.project_update(U(), x()[0], dt / rho, p()[0], nrhs[0] if rot else None, float(nu) * dt if rot else 0.0, U.bcs)
     p.apply_bcs()
     return report
 
@@ -247,11 +243,9 @@ def ns_step(U: Field, p: Field, nu: float | Tensor | Field, dt: float, config: d
     for the increment ``phi`` (None: built once from ``p``'s BCs, kept on ``p``), ``p`` is updated -- which hold a balanced
     state (``source = grad(p) / rho`` on a fluid at rest) bit for bit.  ``U``'s time advances by ``dt``; returns the solver's
     report.  Every check of both halves is made before a device is touched."""
-    _project_args(U, p, dt, rho, "ns_step")
-    _form_args(U, p, form, phi, nu, "ns_step")
+    _project_args(U, p, dt, rho, form, phi, nu, "ns_step")
     if form == "chorin":
         momentum_step(U, nu, dt, config, order, source=source)
-        report = _project(U, p, float(dt), float(rho), solver, "ns_step")
     else:
         _, _, srcs = _momentum_args(U, config, order, None, source, "ns_step")
         _diffusivity_of(_Component(U), nu, config, "ns_step")
@@ -265,7 +259,7 @@ def ns_step(U: Field, p: Field, nu: float | Tensor | Field, dt: float, config: d
         ctx.bind_bcs(U(), U.bcs, 0)                          # the interior set is that of U's faces
         ctx.project_correct(S, p()[0], 1.0 / float(rho), None, out=src)
         momentum_step(U, nu, dt, config, order, source=src)
-        report = _project_increment(U, p, float(dt), float(rho), solver, form, phi, nu, "ns_step")
+    report = _project(U, p, float(dt), float(rho), solver, form, phi, nu, "ns_step")
     if hasattr(U, "_t"):
         U.update_time(dt)
     return report
@@ -278,11 +272,7 @@ def flow_stats(U: Field, dt: float | None = None) -> dict:
     contributes to NaN.  With ``dt`` also ``cfl = dt * rate``, ``div_l2 = sqrt(div_sq * cell volume)`` and ``ke = 0.5 * ke_sq *
     cell volume``.  Synchronises."""
     _vector_args(U, "flow_stats")
-    if dt is not None:
-        if isinstance(dt, bool) or not isinstance(dt, (float, int)):
-            raise TypeError(f"pyapes_amd: flow_stats: dt is a number or None (got {type(dt).__name__})")
-        if not dt > 0:
-            raise ValueError(f"pyapes_amd: flow_stats: dt = {dt!r} (a positive number)")
+    _number("dt", dt, "flow_stats", optional=True)
     require_gpu(U(), "flow_stats")
     if not U().is_contiguous():
         U.set_var_tensor(U().contiguous())
@@ -303,17 +293,14 @@ def ns_march(U: Field, p: Field, nu: float | Tensor | Field, dt: float, nsteps: 
     when the fluid is at rest); a
     rate that is not finite raises ``RuntimeError`` and names the step.  Returns ``{"steps", "t", "dt": [...], "itr": [...],
     "converge": [...]}``: the steps taken, the time covered, and per step its dt and the solver's report."""
-    _project_args(U, p, dt, rho, "ns_march")
-    _form_args(U, p, form, phi, nu, "ns_march")
+    _project_args(U, p, dt, rho, form, phi, nu, "ns_march")
     if isinstance(nsteps, bool) or not isinstance(nsteps, int):
         raise TypeError(f"pyapes_amd: ns_march: nsteps is an int (got {type(nsteps).__name__})")
     if nsteps < 0:
         raise ValueError(f"pyapes_amd: ns_march: nsteps = {nsteps!r} (not negative)")
-    if cfl is not None:
-        if isinstance(cfl, bool) or not isinstance(cfl, (float, int)):
-            raise TypeError(f"pyapes_amd: ns_march: cfl is a number or None (got {type(cfl).__name__})")
-        if not (cfl > 0 and math.isfinite(cfl)):
-            raise ValueError(f"pyapes_amd: ns_march: cfl = {cfl!r} (a positive number)")
+    _number("cfl", cfl, "ns_march", optional=True)
+    if cfl is not None and not math.isfinite(cfl):
+        raise ValueError(f"pyapes_amd: ns_march: cfl = {cfl!r} (a positive number)")
     _momentum_args(U, config, order, None, source, "ns_march")
     _diffusivity_of(_Component(U), nu, config, "ns_march")
     out: dict[str, Any] = {"steps": 0, "t": 0.0, "dt": [], "itr": [], "converge": []}

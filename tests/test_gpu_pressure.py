@@ -1,9 +1,9 @@
 """-m gpu: the pressure-carrying projection -- ``pa_project_update`` (k_project_update) and ``pa_flow_stats`` (k_flow_stats) at
 the C ABI, and ``form=`` of ``project`` / ``ns_step``, ``flow_stats`` and ``ns_march`` of pyapes_amd/solver/projection.py.
 
-The yardstick is tests/pressure_ref.py, and the device must give its BITS: the setups, meshes, BC sets, scales and offsets are
-those of tests/test_gpu_projection.py, with DISTINCT random U, p, phi and nrhs.  ``pa_project_update`` is also held against the
-sequence it replaces, ``pa_project_correct`` and two ``pa_vec_axpy``.  The maxima of ``pa_flow_stats`` are exact; its two sums are
+The yardstick is tests/projection_ref.py, and the device must give its BITS: the setups, meshes, BC sets, scales and offsets are
+those of tests/test_gpu_projection.py (tests/projection_gpu.py has them), with DISTINCT random U, p, phi and nrhs.
+``pa_project_update`` is also held against the sequence it replaces, ``pa_project_correct`` and two ``pa_vec_axpy``.  The maxima of ``pa_flow_stats`` are exact; its two sums are
 double sums of N non-negative addends in the grid's order, within 2 N 2^-53 relative of the restatement's ``math.fsum``
 (tests/test_pressure_host.py has the bound).  ``ns_step(form=...)`` is compared with the CPU chain at a fixed iteration count, to
 the suite's solver tolerances; the rest state of DESIGN.md section 4 "Incremental form" must be held in every bit.
@@ -16,10 +16,9 @@ import pytest
 import torch
 
 import march_gpu as G
-import pressure_ref as Q
+import projection_gpu as PG
 import projection_ref as PR
 import pyapes_oracle as O
-import test_gpu_projection as TP
 from helpers import guards_intact, rel_err, same_bits
 from pyapes_amd.geometry import Box, Cylinder
 from pyapes_amd.hip import lib as L
@@ -33,41 +32,29 @@ from pyapes_amd.variables.bcs import mixed_bcs
 
 pytestmark = pytest.mark.gpu
 
-DT, SCALES, TWO_PASSES = TP.DT, TP.SCALES, TP.TWO_PASSES
+DT, SCALES, TWO_PASSES = PG.DT, PG.SCALES, PG.TWO_PASSES
 CHI = 0.37
 _ids = G.mesh_id
-_EXTRA = {}
-
-
-def _setup(n, dtype, bcname):
-    """test_gpu_projection's setup and, distinct from its U and p, an increment and a right-hand side (1, *n)"""
-    base = TP._setup(n, dtype, bcname)
-    key = (tuple(n), dtype)
-    if key not in _EXTRA:
-        g = torch.Generator().manual_seed(17)
-        tdt = base[4].dtype
-        _EXTRA[key] = tuple(torch.randn((1, *n), generator=g, dtype=torch.float64).to(tdt) for _ in range(2))
-    return base + _EXTRA[key]
 
 
 # ---- pa_project_update ----------------------------------------------------------------------------------------------
 def check_update(n, dtype, bcnames, scales=SCALES, offsets=(None,)):
     bad = []
     for bcname in bcnames:
-        mesh, bc, om, obcs, U_c, p_c, phi_c, r_c = _setup(n, dtype, bcname)
+        mesh, bc, om, obcs, U_c, p_c, phi_c, r_c = PG.setup(n, dtype, bcname)
         ctx = context_for(mesh)
         f = G.fresh_field(mesh, bc, U_c)
         ctx.bind_bcs(f(), f.bcs, 0)
         for scale in scales:
             for rot in (False, True):
-                want_U, want_p = Q.update(U_c, phi_c, p_c, r_c if rot else None, scale, CHI, om, obcs)
-                want_n = Q.update(U_c, phi_c, p_c, r_c if rot else None, scale, CHI, om, obcs, fill=False)[0]
+                want_U, want_p = PR.update(U_c, phi_c, p_c, r_c if rot else None, scale, CHI, om, obcs)
+                want_n = PR.update(U_c, phi_c, p_c, r_c if rot else None, scale, CHI, om, obcs, fill=False)[0]
                 for k in offsets:
                     tag = (bcname, scale, rot, k)
-                    Ud, Ua = TP._dev(U_c, k)
-                    pd, pa = TP._dev(p_c[0], k)
-                    fd, fa = TP._dev(phi_c[0], k)
-                    rd, ra = TP._dev(r_c[0], k)
+                    Ud, Ua = PG.dev(U_c, k)
+                    pd, pa = PG.dev(p_c[0], k)
+                    fd, fa = PG.dev(phi_c[0], k)
+                    rd, ra = PG.dev(r_c[0], k)
                     got = ctx.project_update(Ud, fd, scale, pd, rd if rot else None, CHI, f.bcs)
                     if got is not Ud or not same_bits(Ud, want_U) or not same_bits(pd, want_p[0]):
                         bad.append((tag, "fused", same_bits(Ud, want_U), same_bits(pd, want_p[0])))
@@ -113,29 +100,29 @@ def test_update_on_operands_off_16_byte_alignment(n, dtype):
 # ---- pa_flow_stats --------------------------------------------------------------------------------------------------
 def stats_differ(got, U_c, om, obcs):
     """what of (rate, div_max, div_sq, ke_sq) misses the restatement: the maxima exactly, the sums within 2 N 2^-53 relative"""
-    want = Q.flow_stats(U_c, om, obcs)
-    n_div, n_ke = Q.addends(U_c, om, obcs)
+    want = PR.flow_stats(U_c, om, obcs)
+    n_div, n_ke = PR.addends(U_c, om, obcs)
     bad = []
     for name, g in zip(("rate", "div_max"), got[:2]):
         if not (g == want[name] or (math.isnan(g) and math.isnan(want[name]))):
             bad.append((name, g, want[name]))
     for name, g, N in (("div_sq", got[2], n_div), ("ke_sq", got[3], n_ke)):
-        if not abs(g - want[name]) <= Q.SUM_BOUND * N * want[name]:
-            bad.append((name, g, want[name], abs(g - want[name]) / max(want[name], 1e-300), Q.SUM_BOUND * N))
+        if not abs(g - want[name]) <= PR.SUM_BOUND * N * want[name]:
+            bad.append((name, g, want[name], abs(g - want[name]) / max(want[name], 1e-300), PR.SUM_BOUND * N))
     return bad
 
 
 def check_stats(n, dtype, bcnames, offsets=(None,), fields=None):
     bad = []
     for bcname in bcnames:
-        mesh, bc, om, obcs, U_c, _, _, _ = _setup(n, dtype, bcname)
+        mesh, bc, om, obcs, U_c, _, _, _ = PG.setup(n, dtype, bcname)
         ctx = context_for(mesh)
         f = G.fresh_field(mesh, bc, U_c)
         ctx.bind_bcs(f(), f.bcs, 0)
         sl = O.interior_slicer(len(n), obcs)
         for name, V in (fields(U_c) if fields else [("random", U_c)]):
             for k in offsets:
-                Vd, Va = TP._dev(V, k)
+                Vd, Va = PG.dev(V, k)
                 got = ctx.flow_stats(Vd)
                 bad += [(bcname, name, k) + b for b in stats_differ(got, V, om, obcs)]
                 dmax = float(ctx.divergence(Vd, 1.0)[sl].abs().max().double())
@@ -179,7 +166,7 @@ def test_flow_stats_on_two_passes_of_the_flat_grid_and_their_extremes(dtype):
 @pytest.mark.parametrize("dtype", ["double", "single"])
 def test_flow_stats_of_a_zero_field_and_of_a_nan(dtype):
     n = [11, 13, 17]
-    mesh, bc, om, obcs, U_c, _, _, _ = _setup(n, dtype, "dir")
+    mesh, bc, om, obcs, U_c, _, _, _ = PG.setup(n, dtype, "dir")
     ctx = context_for(mesh)
     f = G.fresh_field(mesh, bc, U_c)
     ctx.bind_bcs(f(), f.bcs, 0)
@@ -200,7 +187,7 @@ def test_flow_stats_of_a_zero_field_and_of_a_nan(dtype):
 def test_flow_stats_entry_point(n, dtype):
     """``flow_stats(U)``: the BC fill first, the four numbers; with ``dt`` the three derived ones, formed in double"""
     for bcname in ("mix", "per"):
-        mesh, bc, om, obcs, U_c, _, _, _ = _setup(n, dtype, bcname)
+        mesh, bc, om, obcs, U_c, _, _, _ = PG.setup(n, dtype, bcname)
         filled = O.bc_fill(U_c.clone(), obcs)
         f = G.fresh_field(mesh, bc, U_c)
         got = flow_stats(f)
@@ -229,11 +216,11 @@ def _source(U_c):
 def test_ns_step_against_the_cpu_chain(form, dtype):
     """a fixed iteration count (tol -1, max_it 4): U, p and itr against the seven statements on the CPU, with and without a
     source; the suite's solver tolerances"""
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = TP._project_case("walled", dtype)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", dtype)
     tol = 1e-10 if dtype == "double" else 1e-5
     for S in (None, _source(U_c)):
-        U_w, p_w, rep_w = Q.ns_step(U_c, p_c, NU, STEP_DT, RHO, om, ubcs, pcfg, form, -1.0, 4, "upwind", 3, S)
-        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), TP._pressure(mesh, pbc, p_c)
+        U_w, p_w, rep_w = PR.ns_step(U_c, p_c, NU, STEP_DT, RHO, om, ubcs, pcfg, form, -1.0, 4, "upwind", 3, S)
+        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), PG.pressure(mesh, pbc, p_c)
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             rep = ns_step(Uf, pf, NU, STEP_DT, G.config("upwind"), 3, rho=RHO, solver=SOLVER, form=form,
@@ -245,7 +232,7 @@ def test_ns_step_against_the_cpu_chain(form, dtype):
         assert abs(float(Uf.t) - (1.5 + STEP_DT)) <= 1e-12
         assert rel_err(U_w, U_c) > 1e-3 and rel_err(p_w, p_c) > 1e-3          # the step did something to both
     # the two forms differ, and both differ from Chorin's (the CPU chain: what the device was just held against)
-    others = [Q.ns_step(U_c, p_c, NU, STEP_DT, RHO, om, ubcs, pcfg, g, -1.0, 4)[1] for g in Q.FORMS if g != form]
+    others = [PR.ns_step(U_c, p_c, NU, STEP_DT, RHO, om, ubcs, pcfg, g, -1.0, 4)[1] for g in PR.FORMS if g != form]
     assert all(rel_err(o, p_w) > 1e-6 for o in others)
 
 
@@ -254,12 +241,12 @@ def test_ns_step_against_the_cpu_chain(form, dtype):
 def test_a_step_on_a_used_mesh_equals_a_step_on_a_fresh_one(form, dtype):
     """three steps on one mesh -- with a source, without, with -- against every step redone on a mesh that has seen nothing,
     from the previous state, bit for bit: neither phi nor the work tensors S / src / nrhs carry state"""
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = TP._project_case("walled", dtype)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", dtype)
     cfg = G.config("upwind")
     srcs = [_source(U_c).cuda(), None, (0.5 * _source(U_c)).cuda()]
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        Uf, pf = G.fresh_field(mesh, ubc, U_c), TP._pressure(mesh, pbc, p_c)
+        Uf, pf = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
         states = []
         for step in range(3):
             assert ns_step(Uf, pf, NU, STEP_DT, cfg, 3, rho=RHO, solver=SOLVER, form=form, source=srcs[step])["itr"] == 5
@@ -268,7 +255,7 @@ def test_a_step_on_a_used_mesh_equals_a_step_on_a_fresh_one(form, dtype):
         prev = (U_c.cuda(), p_c.cuda())
         for step in range(3):
             fresh = Mesh(G.box(3), None, list(U_c.shape[1:]), "cuda", dtype)
-            Uh, ph = G.fresh_field(fresh, ubc, prev[0]), TP._pressure(fresh, pbc, prev[1].clone())
+            Uh, ph = G.fresh_field(fresh, ubc, prev[0]), PG.pressure(fresh, pbc, prev[1].clone())
             phi = Field("phi", 1, fresh, {"domain": mixed_bcs([0.0] * 6, ["neumann", "dirichlet"] + ["neumann"] * 4), "obstacle": None})
             phi.set_var_tensor(torch.full_like(ph(), 7.0))                  # a caller's phi, with content: it is zeroed
             ns_step(Uh, ph, NU, STEP_DT, cfg, 3, rho=RHO, solver=SOLVER, form=form, source=srcs[step], phi=phi)
@@ -281,29 +268,29 @@ def test_a_step_on_a_used_mesh_equals_a_step_on_a_fresh_one(form, dtype):
 @pytest.mark.parametrize("dtype", ["double", "single"])
 def test_form_chorin_is_the_path_as_it_was(dtype):
     """``form="chorin"`` and no ``form`` at all: the bits of ``momentum_step`` then ``project``, on ``ns_step`` and ``project``"""
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = TP._project_case("walled", dtype)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", dtype)
     cfg = G.config("upwind")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        Ug, pg = G.fresh_field(mesh, ubc, U_c), TP._pressure(mesh, pbc, p_c)
+        Ug, pg = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
         momentum_step(Ug, NU, STEP_DT, cfg, 3)
         mid = Ug().clone()
         project(Ug, pg, STEP_DT, RHO, SOLVER)
         for kw in ({}, {"form": "chorin"}):
-            Uf, pf = G.fresh_field(mesh, ubc, U_c), TP._pressure(mesh, pbc, p_c)
+            Uf, pf = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
             ns_step(Uf, pf, NU, STEP_DT, cfg, 3, rho=RHO, solver=SOLVER, **kw)
             assert same_bits(Uf(), Ug()) and same_bits(pf(), pg()), kw
             assert not hasattr(pf, "_increment")
-        Uf, pf = G.fresh_field(mesh, ubc, mid), TP._pressure(mesh, pbc, p_c)
+        Uf, pf = G.fresh_field(mesh, ubc, mid), PG.pressure(mesh, pbc, p_c)
         project(Uf, pf, STEP_DT, RHO, SOLVER, "chorin")
         assert same_bits(Uf(), Ug()) and same_bits(pf(), pg())
         # project(form="incremental") is statements 4 - 7 on its own
-        Uf, pf = G.fresh_field(mesh, ubc, mid), TP._pressure(mesh, pbc, p_c)
+        Uf, pf = G.fresh_field(mesh, ubc, mid), PG.pressure(mesh, pbc, p_c)
         rep = project(Uf, pf, STEP_DT, RHO, SOLVER, "incremental")
         Us = O.bc_fill(mid.cpu().clone(), ubcs)
         nrhs = PR.divergence(Us, om, ubcs, -(RHO / STEP_DT))
-        phi, rep_w = Q._cg(om, Q.increment_cfg(pcfg), nrhs, torch.zeros_like(p_c), -1.0, 4)
-        U_w, q = Q.update(Us, phi, p_c, None, STEP_DT / RHO, 0.0, om, ubcs)
+        phi, rep_w = PR.cg(om, PR.increment_cfg(pcfg), nrhs, torch.zeros_like(p_c), -1.0, 4)
+        U_w, q = PR.update(Us, phi, p_c, None, STEP_DT / RHO, 0.0, om, ubcs)
         p_w = O.bc_fill(q, O.make_bcs(om, pcfg))
         tol = 1e-10 if dtype == "double" else 1e-5
         assert rep["itr"] == rep_w["itr"] == 5
@@ -315,37 +302,37 @@ def test_form_chorin_is_the_path_as_it_was(dtype):
 @pytest.mark.parametrize("n", [[17, 21], [10, 12, 20]], ids=_ids)
 @pytest.mark.parametrize("form", ["incremental", "rotational"])
 def test_the_rest_state_is_held_in_every_bit(form, n, dtype):
-    """U = 0 between walls under the body force that p0 balances (pressure_ref.rest_case): after three steps with the
+    """U = 0 between walls under the body force that p0 balances (projection_ref.rest_case): after three steps with the
     default solver U is +0 in every bit and p has p0's bits.  The right-hand side of every solve is a zero: CG returns after
     its first iteration (0 / 0 -> 0: family A of tests/degenerate_cases.py, ``zero_start_returned``)"""
     nd = len(n)
-    om, ubcs, (uvals, utypes), (pcfg, ptypes), U0, p0, S = Q.rest_case(n, dtype)
+    om, ubcs, (uvals, utypes), (pcfg, ptypes), U0, p0, S = PR.rest_case(n, dtype)
     mesh = Mesh(G.box(nd), None, list(n), "cuda", dtype)
     Uf = G.fresh_field(mesh, {"domain": mixed_bcs(uvals, utypes), "obstacle": None}, U0, time=True)
-    pf = TP._pressure(mesh, {"domain": mixed_bcs([0.0] * (2 * nd), ptypes), "obstacle": None}, p0)
+    pf = PG.pressure(mesh, {"domain": mixed_bcs([0.0] * (2 * nd), ptypes), "obstacle": None}, p0)
     Sd = S.cuda()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        for step in range(Q.REST_STEPS):
-            rep = ns_step(Uf, pf, Q.REST_NU, Q.REST_DT, None, 3, rho=Q.REST_RHO, source=Sd, form=form)
+        for step in range(PR.REST_STEPS):
+            rep = ns_step(Uf, pf, PR.REST_NU, PR.REST_DT, None, 3, rho=PR.REST_RHO, source=Sd, form=form)
             assert rep["itr"] == 1, (step, rep)
     assert same_bits(Uf(), torch.zeros_like(U0))
     assert same_bits(pf(), p0)
     assert float(p0.abs().max()) > 0.9 and float(S.abs().max()) > 0.5
-    st = flow_stats(Uf, Q.REST_DT)
+    st = flow_stats(Uf, PR.REST_DT)
     assert st["rate"] == 0.0 and st["div_max"] == 0.0 and st["ke"] == 0.0
 
 
 # ---- ns_march -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ["double", "single"])
 def test_ns_march_is_a_loop_of_ns_step(dtype):
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = TP._project_case("walled", dtype)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", dtype)
     cfg = G.config("upwind")
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), TP._pressure(mesh, pbc, p_c)
+        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), PG.pressure(mesh, pbc, p_c)
         out = ns_march(Uf, pf, NU, STEP_DT, 3, cfg, 3, rho=RHO, solver=SOLVER)
-        Ug, pg = G.fresh_field(mesh, ubc, U_c), TP._pressure(mesh, pbc, p_c)
+        Ug, pg = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
         reps = [ns_step(Ug, pg, NU, STEP_DT, cfg, 3, rho=RHO, solver=SOLVER, form="incremental") for _ in range(3)]
     assert same_bits(Uf(), Ug()) and same_bits(pf(), pg())
     assert out == {"steps": 3, "t": sum([STEP_DT] * 3), "dt": [STEP_DT] * 3, "itr": [r["itr"] for r in reps],
@@ -357,18 +344,18 @@ def test_ns_march_is_a_loop_of_ns_step(dtype):
 def test_ns_march_caps_every_step_by_the_cfl_rate(dtype):
     """dt_k = min(dt, cfl / rate_k), rate_k the restatement's of the BC-filled state before step k.  The rates of this flow fall from
     64 to 42 over four steps (CPU chain: 64.2, 62.3, 52.4, 41.7), so cfl = 57 dt caps the first steps and not the last"""
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = TP._project_case("walled", dtype)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", dtype)
     cfg = G.config("upwind")
     cfl = 57.0 * STEP_DT
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), TP._pressure(mesh, pbc, p_c)
+        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), PG.pressure(mesh, pbc, p_c)
         out = ns_march(Uf, pf, NU, STEP_DT, 4, cfg, 3, rho=RHO, solver=SOLVER, form="rotational", cfl=cfl)
-        Ug, pg = G.fresh_field(mesh, ubc, U_c), TP._pressure(mesh, pbc, p_c)
+        Ug, pg = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
         want = []
         for k in range(4):
             Ug.apply_bcs()                                                   # as flow_stats does in front of its pass
-            rate = Q.flow_stats(Ug().cpu(), om, ubcs)["rate"]
+            rate = PR.flow_stats(Ug().cpu(), om, ubcs)["rate"]
             want.append(min(STEP_DT, cfl / rate))
             ns_step(Ug, pg, NU, want[-1], cfg, 3, rho=RHO, solver=SOLVER, form="rotational")
     print(f"ns_march cfl {dtype}: dt {out['dt']}")
@@ -380,23 +367,23 @@ def test_ns_march_caps_every_step_by_the_cfl_rate(dtype):
 
 
 def test_ns_march_names_the_step_whose_rate_is_not_finite():
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = TP._project_case("walled", "double")
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", "double")
     V = U_c.clone()
     V[1, 5, 6, 7] = float("nan")
-    Uf, pf = G.fresh_field(mesh, ubc, V), TP._pressure(mesh, pbc, p_c)
+    Uf, pf = G.fresh_field(mesh, ubc, V), PG.pressure(mesh, pbc, p_c)
     with pytest.raises(RuntimeError, match="step 0"):
         ns_march(Uf, pf, NU, STEP_DT, 2, G.config("upwind"), 3, solver=SOLVER, cfl=0.5)
     assert same_bits(pf(), p_c)                                              # refused before the step was taken
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        Ug, pg = G.fresh_field(mesh, ubc, U_c), TP._pressure(mesh, pbc, p_c)
+        Ug, pg = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
         assert ns_march(Ug, pg, NU, STEP_DT, 1, G.config("upwind"), 3, solver=SOLVER, cfl=0.5)["steps"] == 1
 
 
 # ---- the launch log -------------------------------------------------------------------------------------------------
 def log_case():
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = TP._project_case("walled", "double")
-    Uf, pf = G.fresh_field(mesh, ubc, U_c), TP._pressure(mesh, pbc, p_c)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", "double")
+    Uf, pf = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         for form in ("incremental", "incremental", "rotational"):
@@ -422,13 +409,13 @@ def test_the_launches_appear_in_the_launch_log():
 # ---- errors ---------------------------------------------------------------------------------------------------------
 def test_c_abi_errors_leave_the_context_usable():
     n, dtype = [10, 12, 132], "double"
-    _, bc, om, obcs, U_c, p_c, phi_c, r_c = _setup(n, dtype, "mix")
+    _, bc, om, obcs, U_c, p_c, phi_c, r_c = PG.setup(n, dtype, "mix")
     mesh = Mesh(G.box(3), None, list(n), "cuda", dtype)   # a context of its own
     ctx = context_for(mesh)
     f = G.fresh_field(mesh, bc, U_c)
     lib, h = ctx.lib, ctx.h
     ncell = U_c[0].numel()
-    want_U, want_p = Q.update(U_c, phi_c, p_c, r_c, 0.5, CHI, om, obcs)
+    want_U, want_p = PR.update(U_c, phi_c, p_c, r_c, 0.5, CHI, om, obcs)
 
     def good():
         ctx.bind_bcs(f(), f.bcs, 0)
@@ -472,11 +459,11 @@ def test_c_abi_errors_leave_the_context_usable():
     assert same_bits(U, U_c) and same_bits(p, p_c[0])
     good()
     # a BC face array inside a buffer of the call
-    arr_vals = [None if v is None else [v, v, v] for v in TP.BCS["mix"][0]]
+    arr_vals = [None if v is None else [v, v, v] for v in PG.BCS["mix"][0]]
     for buf, name in ((U, "U"), (phi, "phi"), (p, "p"), (r, "nrhs")):
         vals = [None if v is None else list(v) for v in arr_vals]
         vals[0][2] = buf.reshape(-1)[7:7 + n[1] * n[2]]                             # face "xl" of component 2
-        fb = Field("U", 3, mesh, {"domain": mixed_bcs(vals, TP.BCS["mix"][1]), "obstacle": None})
+        fb = Field("U", 3, mesh, {"domain": mixed_bcs(vals, PG.BCS["mix"][1]), "obstacle": None})
         assert code_of(lambda: ctx.project_update(U, phi, 1.0, p, r, CHI, fb.bcs)) == L.PA_E_ARG, name
     good()
     # a live stepwise solve: PA_E_STATE, and after its abort the calls are good again
@@ -508,7 +495,7 @@ def test_c_abi_errors_leave_the_context_usable():
     good()
     # and an ordinary step on the same context still works
     Uf = G.fresh_field(mesh, bc, U_c)
-    pf = TP._pressure(mesh, {"domain": mixed_bcs([0.0] * 6, ["dirichlet"] * 6), "obstacle": None}, torch.zeros_like(p_c))
+    pf = PG.pressure(mesh, {"domain": mixed_bcs([0.0] * 6, ["dirichlet"] * 6), "obstacle": None}, torch.zeros_like(p_c))
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         assert project(Uf, pf, 0.01, 1.0, {"fdm": {"method": "cg", "tol": -1.0, "max_it": 2, "report": False}}, "incremental")["itr"] == 3

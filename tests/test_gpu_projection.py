@@ -9,17 +9,15 @@ in place and out of place, with ``scale`` 1, 1 / dt and negative.  ``project`` i
 oracle CG -> restated kernel at a fixed iteration count, and with the derived fraction of tests/test_projection_host.py on the
 converged single-mode problem (the walled one: that module's docstring says why not the periodic one).
 """
-import ctypes as C
 
 import pytest
 import torch
 
 import march_gpu as G
+import projection_gpu as PG
 import projection_ref as PR
 import pyapes_oracle as O
-from grid_cap_cases import MESHES, PASS, cells
-from helpers import guards_intact, offset_view, rel_err, same_bits
-from march_gpu import ALLDIR, MIXED, XPER
+from helpers import guards_intact, rel_err, same_bits
 from pyapes_amd.geometry import Box, Cylinder
 from pyapes_amd.hip import lib as L
 from pyapes_amd.hip.context import context_for
@@ -30,53 +28,17 @@ from pyapes_amd.solver.march import momentum_step
 from pyapes_amd.solver.projection import divergence, ns_step, project
 from pyapes_amd.variables import Field
 from pyapes_amd.variables.bcs import mixed_bcs
-from test_projection_host import REMAINING_FRACTION
 
 pytestmark = pytest.mark.gpu
 
-BCS = {"dir": ALLDIR, "mix": MIXED, "xper": XPER, "per": ([None] * 6, ["periodic"] * 6)}
-TWO_PASSES = MESHES["one_and_a_bit"][0]
-assert PASS < cells(TWO_PASSES) < 1.02 * PASS
-DT = 0.003
-SCALES = (1.0, 1.0 / DT, -0.75)
-
+BCS, DT, SCALES, TWO_PASSES = PG.BCS, PG.DT, PG.SCALES, PG.TWO_PASSES
 _ids = G.mesh_id
-_SETUPS = {}
-
-
-def _setup(n, dtype, bcname):
-    """the GPU mesh and its BC config (one type per face, a value per component), the oracle mesh and BC list (its values
-    are lists: one per component), and CPU tensors: a BC-filled vector field with distinct random components, a scalar"""
-    key = (tuple(n), dtype, bcname)
-    if key not in _SETUPS:
-        nd = len(n)
-        vals, types = BCS[bcname]
-        vals, types = vals[:2 * nd], types[:2 * nd]
-        per_face = [None if v is None else [v + 0.375 * c - 0.125 * f * c for c in range(nd)] for f, v in enumerate(vals)]
-        mesh = Mesh(G.box(nd), None, list(n), "cuda", dtype)
-        bc = {"domain": mixed_bcs(per_face, types), "obstacle": None}
-        om = O.OMesh([0.0] * nd, [1.0] * nd, list(n), dtype)
-        obcs = O.make_bcs(om, O.mixed_cfg(per_face, types, O.FACES[:2 * nd]))
-        g = torch.Generator().manual_seed(5)
-        tdt = mesh.dtype.float
-        U = torch.randn((nd, *n), generator=g, dtype=torch.float64).to(tdt)
-        O.bc_fill(U, obcs)
-        p = torch.randn((1, *n), generator=g, dtype=torch.float64).to(tdt)
-        _SETUPS[key] = (mesh, bc, om, obcs, U, p)
-    return _SETUPS[key]
-
-
-def _dev(t, k):
-    """a device copy of ``t``: plain (k None), or a view ``k`` elements off a 16-byte boundary with guards (helpers.offset_view)"""
-    if k is None:
-        return t.cuda(), None
-    return offset_view(t.cuda(), k)
 
 
 def check_kernels(n, dtype, bcnames, scales=SCALES, offsets=(None,)):
     bad = []
     for bcname in bcnames:
-        mesh, bc, om, obcs, U_c, p_c = _setup(n, dtype, bcname)
+        mesh, bc, om, obcs, U_c, p_c = PG.setup(n, dtype, bcname)[:6]
         ctx = context_for(mesh)
         f = G.fresh_field(mesh, bc, U_c)
         ctx.bind_bcs(f(), f.bcs, 0)
@@ -86,10 +48,10 @@ def check_kernels(n, dtype, bcnames, scales=SCALES, offsets=(None,)):
             want_n = PR.correct(U_c, p_c, om, obcs, scale, fill=False)
             for k in offsets:
                 tag = (bcname, scale, k)
-                Ud, Ua = _dev(U_c, k)
-                pd, pa = _dev(p_c[0], k)
-                dd, da = _dev(torch.full_like(p_c[0], float("nan")), k)
-                od, oa = _dev(torch.full_like(U_c, float("nan")), k)
+                Ud, Ua = PG.dev(U_c, k)
+                pd, pa = PG.dev(p_c[0], k)
+                dd, da = PG.dev(torch.full_like(p_c[0], float("nan")), k)
+                od, oa = PG.dev(torch.full_like(U_c, float("nan")), k)
                 got = ctx.divergence(Ud, scale, out=dd)
                 if got is not dd or not same_bits(dd, want_d):
                     bad.append((tag, "divergence", same_bits(dd, want_d)))
@@ -134,7 +96,7 @@ def test_divergence_entry_point(n, dtype):
     """``divergence(U)``: the BC fill first (a periodic fill is not idempotent: the reference fills again too), the result
     (1, *n), ``out`` in either shape filled and returned"""
     for bcname in ("mix", "per"):
-        mesh, bc, om, obcs, U_c, _ = _setup(n, dtype, bcname)
+        mesh, bc, om, obcs, U_c, _ = PG.setup(n, dtype, bcname)[:6]
         filled = O.bc_fill(U_c.clone(), obcs)
         for scale in (1.0, -1.0 / DT):
             want = PR.divergence(filled, om, obcs, scale)
@@ -156,7 +118,7 @@ def test_divergence_is_the_sum_of_the_gradients_diagonal(n, dtype):
     reference's special rows, another operator).  The rounding order differs -- grad forms fl(1 / fl(2 h)) x[+1] + 0 x +
     fl(-1 / fl(2 h)) x[-1] -- so: per axis at most 4 roundings on either side of an operand pair, |difference| <= 8 eps
     (|U[+1]| + |U[-1]|) h_a summed over the axes, cell by cell on the interior set."""
-    mesh, bc, om, obcs, U_c, _ = _setup(n, dtype, "dir")
+    mesh, bc, om, obcs, U_c, _ = PG.setup(n, dtype, "dir")[:6]
     nd = len(n)
     f = G.fresh_field(mesh, bc, U_c)
     grads = FDC({"grad": {"edge": False}}).grad(f)
@@ -176,48 +138,15 @@ def test_divergence_is_the_sum_of_the_gradients_diagonal(n, dtype):
 PROJECT_K = 6
 
 
-def _project_case(kind, dtype):
-    if kind == "periodic":
-        n = [16, 16, 32]
-        utypes, uvals = ["periodic"] * 6, [None] * 6
-        ptypes, pvals = ["periodic"] * 6, [None] * 6
-    else:   # walls, a lid on zu, an outflow face xu: U leaves it freely (neumann 0), p = 0 there makes the system non-singular
-        n = [12, 20, 36]
-        utypes = ["dirichlet", "neumann", "dirichlet", "dirichlet", "dirichlet", "dirichlet"]
-        uvals = [[0.3, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [1.0, 0.5, 0.0]]
-        ptypes = ["neumann", "dirichlet", "neumann", "neumann", "neumann", "neumann"]
-        pvals = [0.0] * 6
-    mesh = Mesh(G.box(3), None, n, "cuda", dtype)
-    om = O.OMesh([0.0] * 3, [1.0] * 3, n, dtype)
-    ubc = {"domain": mixed_bcs(uvals, utypes), "obstacle": None}
-    pbc = {"domain": mixed_bcs(pvals, ptypes), "obstacle": None}
-    ubcs = O.make_bcs(om, O.mixed_cfg(uvals, utypes))
-    pcfg = O.mixed_cfg(pvals, ptypes)
-    g = torch.Generator().manual_seed(9)
-    X = [x.double() for x in om.grid]
-    U = torch.stack([torch.sin(2.0 * X[0] + 0.3) * torch.cos(3.0 * X[1]) + 0.2 * X[2],
-                     torch.cos(1.5 * X[1] - 0.2) * torch.sin(2.5 * X[2]) - 0.1 * X[0],
-                     torch.sin(3.0 * X[2] + 0.1) * torch.cos(2.0 * X[0]) + 0.3 * X[1]])
-    U = (U + 0.05 * torch.randn(U.shape, generator=g, dtype=torch.float64)).to(om.dtype)
-    p = (0.01 * torch.randn((1, *n), generator=g, dtype=torch.float64)).to(om.dtype)
-    return mesh, om, ubc, pbc, ubcs, pcfg, U, p
-
-
-def _pressure(mesh, pbc, p_c):
-    pf = Field("p", 1, mesh, pbc)
-    pf.set_var_tensor(p_c.cuda())
-    return pf
-
-
 @pytest.mark.parametrize("dtype", ["double", "single"])
 @pytest.mark.parametrize("kind", ["periodic", "walled"])
 def test_project_against_the_cpu_chain(kind, dtype):
     """a fixed iteration count (tol -1): U, p and itr against restated divergence -> oracle CG -> restated correction, from a
     non-zero p; the suite's solver tolerances"""
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = _project_case(kind, dtype)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case(kind, dtype)
     dt, rho = 0.01, 1.3
     U_w, p_w, rep_w = PR.project(U_c, p_c, dt, rho, om, ubcs, pcfg, -1.0, PROJECT_K)
-    Uf, pf = G.fresh_field(mesh, ubc, U_c), _pressure(mesh, pbc, p_c)
+    Uf, pf = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -240,28 +169,28 @@ def test_converged_projection_leaves_the_derived_fraction(dtype):
     mesh = Mesh(G.box(2), None, n, "cuda", dtype)
     ubc = {"domain": mixed_bcs(face_vals, ["dirichlet"] * 4), "obstacle": None}
     pbc = {"domain": mixed_bcs([0.0] * 4, ["dirichlet"] * 4), "obstacle": None}
-    Uf, pf = G.fresh_field(mesh, ubc, U_c), _pressure(mesh, pbc, torch.zeros((1, *n), dtype=U_c.dtype))
+    Uf, pf = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, torch.zeros((1, *n), dtype=U_c.dtype))
     before = PR.inner_norm(divergence(Uf).cpu())
     rep = project(Uf, pf, PR.MODE_DT, PR.MODE_RHO, {"fdm": {"method": "cg", "tol": 1e-13 if dtype == "double" else 1e-7,
                                                             "max_it": 500, "report": False}})
     ratio = PR.inner_norm(divergence(Uf).cpu()) / before
-    print(f"converged projection {dtype}: itr {rep['itr']}, ratio {ratio!r}, derived {REMAINING_FRACTION!r}")
+    print(f"converged projection {dtype}: itr {rep['itr']}, ratio {ratio!r}, derived {PR.REMAINING_FRACTION!r}")
     assert rep["itr"] < 500
-    assert abs(ratio - REMAINING_FRACTION) <= 0.01 * REMAINING_FRACTION
+    assert abs(ratio - PR.REMAINING_FRACTION) <= 0.01 * PR.REMAINING_FRACTION
 
 
 # ---- ns_step --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", ["double", "single"])
 def test_ns_step_is_momentum_step_then_project(dtype):
     """bit for bit, and three steps on one context give the bits of a fresh mesh per step"""
-    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = _project_case("walled", dtype)
+    mesh, om, ubc, pbc, ubcs, pcfg, U_c, p_c = PG.project_case("walled", dtype)
     nu, dt, rho = 1e-3, 2e-3, 1.3
     solver = {"fdm": {"method": "cg", "tol": -1.0, "max_it": 4, "report": False}}
     cfg = G.config("upwind")
     import warnings
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
-        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), _pressure(mesh, pbc, p_c)
+        Uf, pf = G.fresh_field(mesh, ubc, U_c, time=True), PG.pressure(mesh, pbc, p_c)
         states = []
         for step in range(3):
             rep = ns_step(Uf, pf, nu, dt, cfg, 3, rho=rho, solver=solver)
@@ -269,7 +198,7 @@ def test_ns_step_is_momentum_step_then_project(dtype):
             states.append((Uf().clone(), pf().clone()))
         assert abs(float(Uf.t) - (1.5 + 3 * dt)) <= 1e-12
         # the two halves by hand, on the used mesh
-        Ug, pg = G.fresh_field(mesh, ubc, U_c), _pressure(mesh, pbc, p_c)
+        Ug, pg = G.fresh_field(mesh, ubc, U_c), PG.pressure(mesh, pbc, p_c)
         momentum_step(Ug, nu, dt, cfg, 3)
         project(Ug, pg, dt, rho, solver)
         assert same_bits(Ug(), states[0][0]) and same_bits(pg(), states[0][1])
@@ -277,7 +206,7 @@ def test_ns_step_is_momentum_step_then_project(dtype):
         prev = (U_c.cuda(), p_c.cuda())
         for step in range(3):
             fresh = Mesh(G.box(3), None, list(U_c.shape[1:]), "cuda", dtype)
-            Uh, ph = G.fresh_field(fresh, ubc, prev[0]), _pressure(fresh, pbc, prev[1].clone())
+            Uh, ph = G.fresh_field(fresh, ubc, prev[0]), PG.pressure(fresh, pbc, prev[1].clone())
             ns_step(Uh, ph, nu, dt, cfg, 3, rho=rho, solver=solver)
             assert same_bits(Uh(), states[step][0]), (step, same_bits(Uh(), states[step][0]))
             assert same_bits(ph(), states[step][1]), (step, same_bits(ph(), states[step][1]))
@@ -286,7 +215,7 @@ def test_ns_step_is_momentum_step_then_project(dtype):
 
 # ---- the launch log -------------------------------------------------------------------------------------------------
 def log_case():
-    mesh, bc, om, obcs, U_c, p_c = _setup([11, 13, 17], "double", "mix")
+    mesh, bc, om, obcs, U_c, p_c = PG.setup([11, 13, 17], "double", "mix")[:6]
     f = G.fresh_field(mesh, bc, U_c)
     ctx = context_for(mesh)
     divergence(f)
@@ -309,7 +238,7 @@ def test_the_launches_appear_in_the_launch_log():
 # ---- errors ---------------------------------------------------------------------------------------------------------
 def test_c_abi_errors_leave_the_context_usable():
     n, dtype = [10, 12, 132], "double"
-    _, bc, om, obcs, U_c, p_c = _setup(n, dtype, "mix")
+    _, bc, om, obcs, U_c, p_c = PG.setup(n, dtype, "mix")[:6]
     mesh = Mesh(G.box(3), None, list(n), "cuda", dtype)   # a context of its own
     ctx = context_for(mesh)
     f = G.fresh_field(mesh, bc, U_c)
@@ -401,7 +330,7 @@ def test_c_abi_errors_leave_the_context_usable():
     # and an ordinary solve on the same context still works
     import warnings
     Uf = G.fresh_field(mesh, bc, U_c)
-    pf = _pressure(mesh, {"domain": mixed_bcs([0.0] * 6, ["dirichlet"] * 6), "obstacle": None}, torch.zeros_like(p_c))
+    pf = PG.pressure(mesh, {"domain": mixed_bcs([0.0] * 6, ["dirichlet"] * 6), "obstacle": None}, torch.zeros_like(p_c))
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         assert project(Uf, pf, 0.01, 1.0, {"fdm": {"method": "cg", "tol": -1.0, "max_it": 2, "report": False}})["itr"] == 3

@@ -1,4 +1,4 @@
-"""No GPU: the pressure-carrying projection step and the flow diagnostics restated on the CPU (tests/pressure_ref.py) against
+"""No GPU: the pressure-carrying projection step and the flow diagnostics restated on the CPU (tests/projection_ref.py) against
 independent float64 formulas, the well-balanced property of the incremental forms on the CPU chain -- and its absence in
 Chorin's form --, the determinacy of the four diagnostics, and the argument checks of ``form=`` / ``phi=`` / ``flow_stats`` /
 ``ns_march`` (pyapes_amd/solver/projection.py), which fire before a device is touched.
@@ -17,12 +17,11 @@ import numpy as np
 import pytest
 import torch
 
-import pressure_ref as Q
 import projection_ref as PR
 import pyapes_oracle as O
+from projection_ref import MIXED_TYPES, cpu_field as _cpu_field, eps_of, interior_mask, smooth_vector
 from pyapes_amd.solver import march as M
 from pyapes_amd.solver import projection as P
-from test_projection_host import MIXED_TYPES, _cpu_field, eps_of, interior_mask, smooth_vector
 
 INT_OF = {torch.float64: torch.int64, torch.float32: torch.int32}
 
@@ -67,7 +66,7 @@ def test_restatement_against_a_float64_formula(n, dtype):
     inside = interior_mask(om, bcs)
     for scale, chi in ((1.0, 0.0), (1.0 / 0.003, 5e-5), (-0.75, -2.0)):
         for with_r in (False, True):
-            Un, q = Q.update(U, phi, p, nrhs if with_r else None, scale, chi, om, bcs, fill=False)
+            Un, q = PR.update(U, phi, p, nrhs if with_r else None, scale, chi, om, bcs, fill=False)
             assert torch.equal(Un, PR.correct(U, phi, om, bcs, scale, fill=False))
             want = p64 + phi64 + (chi * r64 if with_r else 0.0)
             bound = 4.0 * eps * (np.abs(p64) + np.abs(phi64) + (abs(chi) * np.abs(r64) if with_r else 0.0))
@@ -79,9 +78,9 @@ def test_restatement_against_a_float64_formula(n, dtype):
                 tol = 6.0 * eps * (abs(scale) * gb + np.abs(U64[c]))
                 assert np.all(np.abs(Un[c].double().numpy() - (U64[c] - scale * grad))[inside] <= tol[inside]), (scale, c)
         # the fill behind the update is the oracle's, and p gets none
-        Uf, qf = Q.update(U, phi, p, nrhs, scale, chi, om, bcs)
-        assert torch.equal(Uf, O.bc_fill(Q.update(U, phi, p, nrhs, scale, chi, om, bcs, fill=False)[0], bcs)) and torch.equal(qf, q)
-    got = Q.flow_stats(U, om, bcs)
+        Uf, qf = PR.update(U, phi, p, nrhs, scale, chi, om, bcs)
+        assert torch.equal(Uf, O.bc_fill(PR.update(U, phi, p, nrhs, scale, chi, om, bcs, fill=False)[0], bcs)) and torch.equal(qf, q)
+    got = PR.flow_stats(U, om, bcs)
     rate64 = sum(np.abs(U64[a]) / dx[a] for a in range(nd))
     assert abs(got["rate"] - rate64.max()) <= (3 + nd) * eps * rate64.max()
     div64 = sum((np.roll(U64[a], -1, a) - np.roll(U64[a], 1, a)) / (2.0 * dx[a]) for a in range(nd))
@@ -91,7 +90,7 @@ def test_restatement_against_a_float64_formula(n, dtype):
     assert abs(got["div_sq"] - math.fsum((div64[inside] ** 2).tolist())) <= math.fsum(sq_bound.tolist())
     ke64 = math.fsum((U64 ** 2).reshape(-1).tolist())
     assert abs(got["ke_sq"] - ke64) <= 3.0 * eps * ke64
-    assert Q.addends(U, om, bcs) == (int(inside.sum()), U.numel())
+    assert PR.addends(U, om, bcs) == (int(inside.sum()), U.numel())
     assert got["div_max"] > 0.1 and got["rate"] > 1.0
 
 
@@ -104,18 +103,18 @@ def test_the_restatement_rounds_every_operation_in_the_dtype():
     U = torch.randn((2, 11, 13), generator=g, dtype=torch.float64).to(torch.float32)
     p, phi, r = (torch.randn((1, 11, 13), generator=g, dtype=torch.float64).to(torch.float32) for _ in range(3))
     chi = 0.37
-    _, q = Q.update(U, phi, p, r, 1.0, chi, om, bcs)
+    _, q = PR.update(U, phi, p, r, 1.0, chi, om, bcs)
     t = torch.tensor(chi, dtype=torch.float32) * r
     assert torch.equal(q, (p + phi) + t)
     once = (p.double() + phi.double() + chi * r.double()).float()
     assert not torch.equal(q, once)
-    assert torch.equal(Q.update(U, phi, p, None, 1.0, chi, om, bcs)[1], p + phi)
+    assert torch.equal(PR.update(U, phi, p, None, 1.0, chi, om, bcs)[1], p + phi)
     q0, q1 = (torch.tensor(1.0 / float(om.dx[a]), dtype=torch.float64).float() for a in range(2))
     s = (torch.zeros_like(U[0]) + U[0].abs() * q0) + U[1].abs() * q1
-    assert torch.equal(Q.rate_field(U, om), s)
+    assert torch.equal(PR.rate_field(U, om), s)
     once = (U[0].abs().double() / float(om.dx[0]) + U[1].abs().double() / float(om.dx[1])).float()
     assert not torch.equal(s, once)
-    st = Q.flow_stats(U, om, bcs)
+    st = PR.flow_stats(U, om, bcs)
     d = PR.divergence(U, om, bcs)[0]
     assert st["div_sq"] == math.fsum((d * d).double().flatten().tolist())          # the square in fp32, the sum in double
     assert st["div_sq"] != math.fsum((d.double() * d.double()).flatten().tolist())
@@ -124,10 +123,10 @@ def test_the_restatement_rounds_every_operation_in_the_dtype():
 
 # ---- the rest state -------------------------------------------------------------------------------------------------
 def _three_steps(form, dtype, n=(17, 21)):
-    om, ubcs, _, (pcfg, _), U, p0, S = Q.rest_case(list(n), dtype)
+    om, ubcs, _, (pcfg, _), U, p0, S = PR.rest_case(list(n), dtype)
     p, itr = p0.clone(), []
-    for _ in range(Q.REST_STEPS):
-        U, p, rep = Q.ns_step(U, p, Q.REST_NU, Q.REST_DT, Q.REST_RHO, om, ubcs, pcfg, form, 1e-6, 1000, S=S)
+    for _ in range(PR.REST_STEPS):
+        U, p, rep = PR.ns_step(U, p, PR.REST_NU, PR.REST_DT, PR.REST_RHO, om, ubcs, pcfg, form, 1e-6, 1000, S=S)
         itr.append(rep["itr"])
     return U, p, p0, itr
 
@@ -160,14 +159,14 @@ def test_flow_stats_do_not_depend_on_the_order_of_the_cells(dtype):
     (every partial sum is at most the total, N - 1 roundings of 2^-53 relative each, the fsum's own one on top)"""
     om, bcs = _mixed([7, 9, 12], dtype)
     U = torch.from_numpy(smooth_vector(om)[0]).to(om.dtype)
-    st = Q.flow_stats(U, om, bcs)
+    st = PR.flow_stats(U, om, bcs)
     sl = O.interior_slicer(3, bcs)
-    s = Q.rate_field(U, om).double().flatten()
+    s = PR.rate_field(U, om).double().flatten()
     d = PR.divergence(U, om, bcs)[0][sl]
     dabs = d.abs().double().flatten()
     dsq = (d * d).double().flatten()
     ke = (U * U).double().flatten()
-    assert Q.addends(U, om, bcs) == (dsq.numel(), ke.numel())
+    assert PR.addends(U, om, bcs) == (dsq.numel(), ke.numel())
     gen = torch.Generator().manual_seed(11)
     for trial in range(4):
         for name, v in (("rate", s), ("div_max", dabs)):
@@ -178,7 +177,7 @@ def test_flow_stats_do_not_depend_on_the_order_of_the_cells(dtype):
             assert m == st[name], (name, trial)
         for name, v in (("div_sq", dsq), ("ke_sq", ke)):
             perm = torch.randperm(v.numel(), generator=gen)
-            bound = Q.SUM_BOUND * v.numel() * st[name]
+            bound = PR.SUM_BOUND * v.numel() * st[name]
             for order in (v, v.flip(0), v[perm]):
                 run = 0.0
                 for x in order.tolist():
@@ -188,13 +187,13 @@ def test_flow_stats_do_not_depend_on_the_order_of_the_cells(dtype):
     # a NaN in a contribution makes that maximum NaN
     V = U.clone()
     V[2, 0, 3, 4] = float("nan")                         # on face xl (dirichlet): no interior stencil of component 2 reads it
-    bad = Q.flow_stats(V, om, bcs)
+    bad = PR.flow_stats(V, om, bcs)
     assert math.isnan(bad["rate"]) and bad["div_max"] == st["div_max"]
     V = U.clone()
     V[0, 3, 3, 4] = float("nan")
-    bad = Q.flow_stats(V, om, bcs)
+    bad = PR.flow_stats(V, om, bcs)
     assert math.isnan(bad["rate"]) and math.isnan(bad["div_max"])
-    zero = Q.flow_stats(torch.zeros_like(U), om, bcs)
+    zero = PR.flow_stats(torch.zeros_like(U), om, bcs)
     assert list(zero.values()) == [0.0] * 4 and not any(math.copysign(1.0, v) < 0 for v in zero.values())
 
 
@@ -340,7 +339,7 @@ def test_the_names_are_part_of_the_package_surface():
     assert len(L.SIGNATURES["pa_project_update"][1]) == 9 and len(L.SIGNATURES["pa_flow_stats"][1]) == 4
     for name in ("project_update", "flow_stats"):
         assert callable(getattr(HipContext, name))
-    assert P.FORMS == ("chorin", "incremental", "rotational") == Q.FORMS
+    assert P.FORMS == ("chorin", "incremental", "rotational") == PR.FORMS
     for fn, form in ((P.ns_step, "chorin"), (P.project, "chorin"), (P.ns_march, "incremental")):
         par = inspect.signature(fn).parameters
         assert par["form"].default == form and par["phi"].default is None

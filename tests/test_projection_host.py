@@ -28,38 +28,15 @@ import torch
 
 import projection_ref as PR
 import pyapes_oracle as O
+from projection_ref import MIXED_TYPES, REMAINING_FRACTION, cpu_field as _cpu_field, eps_of, interior_mask, smooth_vector
 from pyapes_amd.solver import march as M
 from pyapes_amd.solver import projection as P
 
-# sin^2(theta / 2) at theta = pi / 4 (module docstring): the fraction of the divergence the approximate projection leaves
-REMAINING_FRACTION = (2.0 - math.sqrt(2.0)) / 4.0
 MODE_N, MODE_M, MODE_DT, MODE_RHO = PR.MODE_N, PR.MODE_M, PR.MODE_DT, PR.MODE_RHO
-
-
-def eps_of(dtype):
-    return float(torch.finfo(dtype).eps)
 
 
 def periodic_cfg(nd):
     return O.mixed_cfg([None] * (2 * nd), ["periodic"] * (2 * nd), O.FACES[:2 * nd])
-
-
-MIXED_TYPES = ["dirichlet", "neumann", "symmetry", "dirichlet", "periodic", "periodic"]
-
-
-def smooth_vector(om):
-    """a smooth vector field with distinct components and a smooth scalar, float64 numpy, on the mesh's nodes"""
-    X = [g.double().numpy() for g in om.grid]
-    nd = om.dim
-    U = np.stack([np.sin(1.3 * X[a] + 0.4 * a) * np.cos(0.7 * X[(a + 1) % nd] - 0.2) + 0.1 * (a + 1) for a in range(nd)])
-    p = np.cos(0.9 * X[0] + 0.3) * np.sin(1.1 * X[-1] + 0.5) + 0.25
-    return U, p
-
-
-def interior_mask(om, bcs):
-    m = np.zeros(tuple(om.nx), dtype=bool)
-    m[O.interior_slicer(om.dim, bcs)] = True
-    return m
 
 
 # ---- the restatement against an independent formula -----------------------------------------------------------------
@@ -164,21 +141,6 @@ def test_projection_leaves_the_derived_fraction_of_a_mode(dtype):
 
 
 # ---- the checks in front of the device ------------------------------------------------------------------------------
-def _cpu_field(n=(9, 9), dim=None, slab=None, geo=None, dtype="double", name="U", mesh=None):
-    from pyapes_amd.geometry import Box
-    from pyapes_amd.mesh import Mesh
-    from pyapes_amd.variables import Field
-    from pyapes_amd.variables.bcs import mixed_bcs
-    if mesh is None:
-        box = geo if geo is not None else (Box[0:1] if len(n) == 1 else (Box[0:1, 0:1] if len(n) == 2 else Box[0:1, 0:1, 0:1]))
-        mesh = Mesh(box, None, list(n), "cpu", dtype, **({"slab": slab} if slab else {}))
-    nd = mesh.dim
-    cfg = mixed_bcs([0.0] * (2 * nd), ["dirichlet"] * (2 * nd))
-    if mesh.coord_sys == "rz":
-        cfg = [dict(c, bc_face=f) for c, f in zip(cfg, O.FACES_RZ)]
-    return Field(name, nd if dim is None else dim, mesh, {"domain": cfg, "obstacle": None})
-
-
 @pytest.fixture
 def no_device(monkeypatch):
     """a refusal must come before context_for (and before require_gpu) is reached, in this module and in the march's"""
