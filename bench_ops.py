@@ -118,6 +118,22 @@ def main():
         ms = timed(lambda: y.copy_(x), 20)
         emit(f"torch copy_ {n}^3 {f} (reference point: 1 read + 1 write)", n ** 3, ms, 2, es)
         del var, mesh, ctx, x, y, g3
+        # every Div kind on the generic kernel (k_aop, "fastpath" 0) at 256^3, a scalar speed and a speed field; dirichlet
+        # faces, which the central kind needs
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [256, 256, 256], "cuda", dt)
+        var = Field("p", 1, mesh, {"domain": homogeneous_bcs(3, 0.0, "dirichlet"), "obstacle": None}, init_val="random")
+        ctx = context_for(mesh)
+        ctx.bind_bcs(var(), var.bcs, 0)
+        ctx.set_option("fastpath", 0)
+        x = var()[0]
+        y, uf = torch.empty_like(x), torch.randn_like(x)
+        for kname, kind in (("central", L.OP_DIV_CENTRAL), ("upwind compat", L.OP_DIV_UPWIND_COMPAT), ("upwind", L.OP_DIV_UPWIND),
+                            ("quick", L.OP_DIV_QUICK), ("minmod", L.OP_DIV_MINMOD), ("mc", L.OP_DIV_MC)):
+            for uname, u, passes in (("scalar speed", 0.7, 2), ("speed field", uf, 3)):
+                ms = timed(lambda: ctx.div(kind, u, x, out=y), 20)
+                emit(f"div apply 256^3 {f} {kname}, {uname}, fastpath 0 (k_aop)", 256 ** 3, ms, passes, es)
+        ctx.set_option("fastpath", 1)
+        del var, mesh, ctx, x, y, uf
 
     # --- config 4: explicit adv-diff march 256^3 fp32, upwind, Neumann / Symmetry ------------------
     if "euler" in sections:
@@ -891,7 +907,7 @@ def solver_rows(q, emit, sections):
     from pyapes_amd.variables.bcs import homogeneous_bcs, mixed_bcs
 
     # --- solvers: ms per iteration from fixed-iteration solves ------------------------------------
-    def solver_ms(meshf, bcsf, method, K, rhs_fn=None, extra_cfg=None, resident=True):
+    def solver_ms(meshf, bcsf, method, K, rhs_fn=None, extra_cfg=None, resident=True, eq=lambda v: FDM().laplacian(1.0, v)):
         os.environ["PYAPES_HIP_RESIDENT"] = "1" if resident else "0"   # read when the mesh's context is created
         mesh = meshf()
         var = Field("p", 1, mesh, {"domain": bcsf, "obstacle": None})
@@ -901,10 +917,10 @@ def solver_rows(q, emit, sections):
         # one short untimed solve first (same mesh / context): code-object load, scratch allocation
         warm = Field("p", 1, mesh, {"domain": bcsf, "obstacle": None})
         sw = Solver({"fdm": dict(cfg, max_it=3)})
-        sw.set_eq(FDM().laplacian(1.0, warm) == rhs.clone())
+        sw.set_eq(eq(warm) == rhs.clone())
         sw.solve()
         s = Solver({"fdm": cfg})
-        s.set_eq(FDM().laplacian(1.0, var) == rhs)
+        s.set_eq(eq(var) == rhs)
         t0 = time.perf_counter()
         rep = s.solve()
         wall = (time.perf_counter() - t0) * 1e3
@@ -953,10 +969,33 @@ def solver_rows(q, emit, sections):
             ms, wall, itr, N = solver_ms(meshf, bcs_, meth, its, rfn, resident=res)
             how = f"resident, {solver_ms.boxes} workgroups" if solver_ms.boxes else "launch per phase"
             emit(f"{name} [{how}]", N, ms, passes, 8, {"wall_ms_per_iter": wall, "iters": itr})
+    if "small" in sections:
+        # a term list with a Div term: the resident kernel evaluates the generic term list on its box (no lean stencil)
+        fdm_up = FDM({"div": {"limiter": "upwind", "edge": False}})
+        for res in (True, False):
+            torch.manual_seed(0)
+            ms, wall, itr, N = solver_ms(m3(32), homogeneous_bcs(3, 0.0, "dirichlet"), "bicgstab", 40, lambda m, v: torch.ones_like(v()),
+                                         resident=res, eq=lambda v: fdm_up.div(1.0, v) - fdm_up.laplacian(0.05, v))
+            how = f"resident, {solver_ms.boxes} workgroups" if solver_ms.boxes else "launch per phase"
+            emit(f"bicgstab 3-D 32^3 f64 steady advection-diffusion (upwind Div + Laplacian), dirichlet [{how}]", N, ms, 22, 8,
+                 {"wall_ms_per_iter": wall, "iters": itr})
     os.environ["PYAPES_HIP_RESIDENT"] = "1"
     if "big" not in sections:
         return
-    n = 128 if q else 256
+    # the generic one-cell-per-thread solver kernels (k_jacobi, k_cg_a / k_cg_b, k_bicg_*: "fastpath" 0, launch per phase) at 128^3
+    def generic_mesh(dt):
+        from pyapes_amd.hip.context import context_for as _cf
+        mesh = Mesh(Box[0:1, 0:1, 0:1], None, [128, 128, 128], "cuda", dt)
+        _cf(mesh).set_option("fastpath", 0)
+        return mesh
+
+    for dt, es in (("double", 8), ("single", 4)):
+        for meth, its, passes in (("jacobi", 200, 3), ("cg", 100, 10), ("bicgstab", 60, 22)):
+            torch.manual_seed(0)
+            ms, wall, itr, N = solver_ms(lambda: generic_mesh(dt), mixbc, meth, its, resident=False)
+            emit(f"{meth} 3-D 128^3 {'f64' if es == 8 else 'f32'} dirichlet/neumann faces, fastpath 0 (generic kernels)", N, ms, passes, es,
+                 {"wall_ms_per_iter": wall, "iters": itr})
+    n = 128 if q else 256   # (solver_ms sets the resident switch on every call: the rows below run with it on again)
     ms, wall, itr, N = solver_ms(lambda: Mesh(Box[0:1, 0:1, 0:1], None, [n, n, n], "cuda", "double"),
                                  homogeneous_bcs(3, 0.0, "dirichlet"), "jacobi", K)
     emit(f"jacobi 3-D {n}^3 f64 dirichlet", N, ms, 3, 8, {"wall_ms_per_iter": wall, "iters": itr})

@@ -149,12 +149,7 @@ __device__ __forceinline__ T pa_lap_axis(const DevGeom& G, const LapCoef<T>& L, 
   const int rc = pa_row_case(G, a, g, N, G.treat);
   if (rc == 1) { cP = cB; cC = -cB; cM = (T)0; }
   if (rc == 2) { cP = (T)0; cC = -cB; cM = cB; }
-  T s = cP * xp;
-  T m = cC * xc;
-  s = s + m;
-  m = cM * xm;
-  s = s + m;
-  return s;
+  return pa_row3<T>(cP, xp, cC, xc, cM, xm);
 }
 
 template <typename T>

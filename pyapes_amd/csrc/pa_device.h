@@ -220,6 +220,43 @@ __device__ __forceinline__ void pa_tvd_halves(T xmm, T xm, T xc, T xp, T xpp, bo
   }
 }
 
+// ---- per-axis statements the generic (one cell per thread) kernels share (DESIGN.md section 4 "Where a scheme is stated"):
+// values in, value out, one rounding per statement.  The tiled kernels keep statements of their own. ----
+// the three-point row ((cP x+ + cC x) + cM x-), fdc.py:190-198
+template <typename T>
+__device__ __forceinline__ T pa_row3(T cP, T xp, T cC, T xc, T cM, T xm) {
+  T s = cP * xp;
+  T m = cC * xc;
+  s = s + m;
+  m = cM * xm;
+  s = s + m;
+  return s;
+}
+
+// PA_OP_DIV_CENTRAL on one axis (fdc.py:708-743): the row's three coefficients from the speed at the two neighbours and
+// cC = (+0) * u at the node, or the rz row (tools.py:64-78) times it, formed by the caller; a periodic face cuts the
+// coefficient that would reach across it.  cC is IN / OUT: the caller's centre coefficient comes back divided by 2h like the
+// other two.  The row itself is pa_row3.
+template <typename T>
+__device__ __forceinline__ void pa_central_row(const DevGeom& G, int a, int64_t g, int64_t N, T up, T um, T h2, T& cP, T& cC, T& cM) {
+  cP = up;
+  cM = -um;
+  if (G.bct[2 * a] == 4 && g == 1) cM = (T)0;
+  if (G.bct[2 * a + 1] == 4 && g == N - 2) cP = (T)0;
+  cP = cP / h2;
+  cC = cC / h2;
+  cM = cM / h2;
+}
+
+// PA_OP_DIV_UPWIND_COMPAT on one axis (literal fdc.py:746-772); fC: (+0), or the rz row on the r axis
+template <typename T>
+__device__ __forceinline__ T pa_upwind_compat_axis(T ucen, T fC, T xp, T xc, T xm) {
+  const T cP = (T)2 * (ucen > (T)0 ? (T)0 : ucen);
+  const T cC = fC * ((T)2 * ucen);
+  const T cM = (T)2 * (ucen < (T)0 ? (T)0 : ucen);
+  return pa_row3<T>(cP, xp, cC, xc, cM, xm);
+}
+
 __device__ __forceinline__ void pa_gidx(const DevGeom& G, int64_t i, int64_t j, int64_t k, int64_t* g,
                                         int64_t* N) {
   g[0] = i + G.off0; g[1] = j; g[2] = k;
@@ -249,6 +286,8 @@ __device__ __forceinline__ int pa_row_case(const DevGeom& G, int ax, int64_t g, 
 }
 
 // sum_k sign_k * param_k * Op_k(acc)   at local node (i,j,k); xc = acc.at(i,j,k)
+// The rows of the Laplacian, Grad, central and literal-upwind branches are the helpers above; the advective branches (upwind,
+// QUICK, minmod / mc) are written out here and again in pa_adv_vel (pa_march.hip): k_euler measured slower with them shared.
 // TVD: the term list may hold the explicit-only kinds PA_OP_DIV_MINMOD / _MC (the TVD instantiations of k_aop for pa_div and of
 // k_euler for the steps).  Every other kernel -- the solver kernels never see them, pa_eq_set refuses -- is compiled without
 // that branch and stays the code it was.
@@ -279,12 +318,7 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
         if (rc == 2) { cP = (T)0; cC = -cB; cM = cB; }
         T xp, xm;
         pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T s = cP * xp;
-        T m = cC * xc;
-        s = s + m;
-        m = cM * xm;
-        s = s + m;
-        ax = ax + s;
+        ax = ax + pa_row3<T>(cP, xp, cC, xc, cM, xm);
       }
       if (t.has_coeff) ax = ax * (t.coeff_f ? t.coeff_f[o] : t.coeff);
     } else if (t.kind == 1) {  // PA_OP_GRAD (1-D in the solver; sums axes otherwise never reached)
@@ -299,12 +333,7 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
         if (G.bct[2 * a + 1] == 4 && g[a] == N[a] - 2) cP = (T)0;  // periodic upper (fdc.py:600-602)
         T xp, xm;
         pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T s = cP * xp;
-        T m = cC * xc;
-        s = s + m;
-        m = cM * xm;
-        s = s + m;
-        ax = ax + s;
+        ax = ax + pa_row3<T>(cP, xp, cC, xc, cM, xm);
       }
       if (t.has_coeff) ax = ax * (t.coeff_f ? t.coeff_f[o] : t.coeff);
     } else if (t.kind == 2) {  // PA_OP_DIV_CENTRAL (fdc.py:708-743), scalar phi: adv[0] on every axis
@@ -323,40 +352,23 @@ __device__ __forceinline__ T pa_apply_terms(const DevGeom& G, const DevEq<T>& E,
           um = t.u_f[i2 * G.s0 + j2 * G.s1 + k2];
         }
         T ucen = t.u_f ? t.u_f[o] : t.u;
-        T cP = up, cC = (T)0 * ucen, cM = -um;
+        T cP, cC = (T)0 * ucen, cM;
         if (E.rz && a == PA_RZ_AXIS) cC = E.rz[4 * E.rz_n + g[a]] * ucen;  // tools.py:64-78
-        if (G.bct[2 * a] == 4 && g[a] == 1) cM = (T)0;
-        if (G.bct[2 * a + 1] == 4 && g[a] == N[a] - 2) cP = (T)0;
-        cP = cP / E.grd.h2[a];
-        cC = cC / E.grd.h2[a];
-        cM = cM / E.grd.h2[a];
+        pa_central_row<T>(G, a, g[a], N[a], up, um, E.grd.h2[a], cP, cC, cM);
         T xp, xm;
         pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T s = cP * xp;
-        T m = cC * xc;
-        s = s + m;
-        m = cM * xm;
-        s = s + m;
-        ax = ax + s;
+        ax = ax + pa_row3<T>(cP, xp, cC, xc, cM, xm);
       }
     } else if (t.kind == 3) {  // PA_OP_DIV_UPWIND_COMPAT (literal fdc.py:746-772)
       T ucen = t.u_f ? t.u_f[o] : t.u;
-      T cP = (T)2 * (ucen > (T)0 ? (T)0 : ucen);
-      T cC0 = (T)0 * ((T)2 * ucen);
-      T cM = (T)2 * (ucen < (T)0 ? (T)0 : ucen);
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         if (!G.act[a]) continue;
-        T cC = cC0;
-        if (E.rz && a == PA_RZ_AXIS) cC = E.rz[4 * E.rz_n + g[a]] * ((T)2 * ucen);
+        T fC = (T)0;
+        if (E.rz && a == PA_RZ_AXIS) fC = E.rz[4 * E.rz_n + g[a]];
         T xp, xm;
         pa_nbrs<T>(G, acc, a, i, j, k, xp, xm);
-        T s = cP * xp;
-        T m = cC * xc;
-        s = s + m;
-        m = cM * xm;
-        s = s + m;
-        ax = ax + s;
+        ax = ax + pa_upwind_compat_axis<T>(ucen, fC, xp, xc, xm);
       }
     } else if (t.kind == 5) {  // PA_OP_DIV_QUICK (DESIGN.md "QUICK"): advective form, the speed at the node
       T ucen = t.u_f ? t.u_f[o] : t.u;

@@ -63,7 +63,8 @@ __device__ __forceinline__ T pa_nu_term(const DevGeom& G, const EulerNu<T, true>
 }
 
 // adv = (+0) + t_0 + t_1 + t_2 over the active axes: the per-axis term of pa_apply_terms' scheme `kind` (central, QUICK,
-// minmod / mc, upwind), operation for operation, with axis a's own speed W.f[a] / W.val[a] in the place of the one speed
+// minmod / mc, upwind), operation for operation -- the central row through pa_central_row / pa_row3, the rest written out as
+// there.  What differs: axis a's own speed W.f[a] / W.val[a] stands in the place of the one speed, and there is no rz row.
 // TVD: W.kind may be PA_OP_DIV_MINMOD / _MC (k_euler's TVD instantiations); without it that branch is not compiled
 template <typename T, bool TVD = false>
 __device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd, const EulerVel<T, true>& W, const FieldAcc<T>& acc,
@@ -89,18 +90,9 @@ __device__ __forceinline__ T pa_adv_vel(const DevGeom& G, const GradCoef<T>& grd
         up = uf[ii * G.s0 + jj * G.s1 + kk];
         um = uf[i2 * G.s0 + j2 * G.s1 + k2];
       }
-      T cP = up, cC = (T)0 * ucen, cM = -um;
-      if (G.bct[2 * a] == 4 && g[a] == 1) cM = (T)0;
-      if (G.bct[2 * a + 1] == 4 && g[a] == N[a] - 2) cP = (T)0;
-      cP = cP / grd.h2[a];
-      cC = cC / grd.h2[a];
-      cM = cM / grd.h2[a];
-      T s = cP * xp;
-      T m = cC * xc;
-      s = s + m;
-      m = cM * xm;
-      s = s + m;
-      ax = ax + s;
+      T cP, cC = (T)0 * ucen, cM;
+      pa_central_row<T>(G, a, g[a], N[a], up, um, grd.h2[a], cP, cC, cM);
+      ax = ax + pa_row3<T>(cP, xp, cC, xc, cM, xm);
     } else {
       const T upl = ucen < (T)0 ? (T)0 : ucen;
       const T umi = ucen > (T)0 ? (T)0 : ucen;

@@ -71,30 +71,14 @@ __global__ void __launch_bounds__(PA_BLOCK) k_div_general(DevGeom G, DevEq<T> E,
         const T* uf = S.ui[a];
         const T ucen = uf ? uf[o] : S.u;
         if (S.kind == PA_OP_DIV_CENTRAL) {
-          T cP = uf ? uf[op] : S.u;
-          T cM = -(uf ? uf[om] : S.u);
-          T cC = (T)0 * ucen;
+          T cP, cC = (T)0 * ucen, cM;
           if (E.rz && a == PA_RZ_AXIS) cC = E.rz[4 * E.rz_n + ga] * ucen;
-          if (G.bct[2 * a] == 4 && ga == 1) cM = (T)0;
-          if (G.bct[2 * a + 1] == 4 && ga == Na - 2) cP = (T)0;
-          cP = cP / E.grd.h2[a];
-          cC = cC / E.grd.h2[a];
-          cM = cM / E.grd.h2[a];
-          T s = cP * xp;
-          T m = cC * xc;
-          s = s + m;
-          m = cM * xm;
-          disc = s + m;
+          pa_central_row<T>(G, a, ga, Na, uf ? uf[op] : S.u, uf ? uf[om] : S.u, E.grd.h2[a], cP, cC, cM);
+          disc = pa_row3<T>(cP, xp, cC, xc, cM, xm);
         } else if (S.kind == PA_OP_DIV_UPWIND_COMPAT) {
-          T cP = (T)2 * (ucen > (T)0 ? (T)0 : ucen);
-          T cC = (T)0 * ((T)2 * ucen);
-          if (E.rz && a == PA_RZ_AXIS) cC = E.rz[4 * E.rz_n + ga] * ((T)2 * ucen);
-          T cM = (T)2 * (ucen < (T)0 ? (T)0 : ucen);
-          T s = cP * xp;
-          T m = cC * xc;
-          s = s + m;
-          m = cM * xm;
-          disc = s + m;
+          T fC = (T)0;
+          if (E.rz && a == PA_RZ_AXIS) fC = E.rz[4 * E.rz_n + ga];
+          disc = pa_upwind_compat_axis<T>(ucen, fC, xp, xc, xm);
         } else {
           T upl = ucen < (T)0 ? (T)0 : ucen;
           T umi = ucen > (T)0 ? (T)0 : ucen;

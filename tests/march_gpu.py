@@ -23,7 +23,8 @@ MIXED = ([0.5, 0.1, None, 1.0, -0.3, None], ["dirichlet", "neumann", "symmetry",
 XPER = ([None, None, 0.25, -0.5, 2.0, 0.0], ["periodic", "periodic", "dirichlet", "dirichlet", "dirichlet", "dirichlet"])
 BCS = {"dir": ALLDIR, "mix": MIXED, "xper": XPER}
 ZPER = ([0.25, -0.5, 2.0, 0.0, None, None], ["dirichlet", "dirichlet", "dirichlet", "dirichlet", "periodic", "periodic"])   # beside BCS
-LIMITER_BCS = {"upwind": ("dir", "mix"), "quick": ("dir", "mix"), "none": ("dir",)}   # central Div refuses neumann / symmetry
+LIMITER_BCS = {"upwind": ("dir", "mix"), "quick": ("dir", "mix"), "none": ("dir",),   # central Div refuses neumann / symmetry
+               "minmod": ("dir", "mix"), "mc": ("dir", "mix")}
 
 VECTOR = [([7, 13, 132], "double"), ([9, 14, 132], "double"), ([7, 13, 260], "single"), ([9, 14, 260], "single")]
 GENERIC = [([6, 7, 9], "double"), ([17, 12], "double"), ([33], "single")]

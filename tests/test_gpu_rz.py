@@ -9,7 +9,8 @@ import torch
 
 import pyapes_oracle as O
 from conftest import golden_cases, golden_load
-from helpers import rel_err
+import grid_cap_cases as C
+from helpers import rel_err, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -79,6 +80,48 @@ def test_rz_jacobi_and_euler_vs_oracle(dtype):
         v.set_var_tensor(phi0.cuda().clone())
         euler_step(v, u.cuda() if isinstance(u, torch.Tensor) else u, 1e-2, 1e-3, {"div": {"limiter": "upwind"}})
         assert rel_err(v().cpu(), po) < (1e-13 if dtype == "double" else 1e-6)
+
+
+@pytest.mark.parametrize("lim", ["none", "compat", "upwind"])
+@pytest.mark.parametrize("dtype", ["double", "single"])
+def test_rz_div_schemes_bit_for_bit(dtype, lim):
+    """central, literal upwind and intended upwind Div with their r rows on the 19 x 23 cylinder above, the oracle's bits at every
+    node: pa_div (k_aop) on a scalar field with a number of either sign and a tensor as the speed, and pa_div_general
+    (k_div_general) on a vector field with a number and a tensor -- the references of tests/test_gpu_grid_cap.py.  Dirichlet
+    faces: central Div refuses the others."""
+    n = (19, 23)
+    mo = O.OMesh([0.0, 0.0], [1.0, 1.5], list(n), dtype, "rz")
+    cfg = O.mixed_cfg([0.0, 1.0, 0.25, 0.5], ["dirichlet"] * 4, O.FACES_RZ)
+    obcs = O.make_bcs(mo, cfg)
+    mesh = Mesh(Cylinder([0.0, 0.0], [1.0, 1.5]), None, list(n), "cuda", dtype)
+    g = torch.Generator().manual_seed(5)
+    x = O.bc_fill(torch.randn((1, *n), generator=g, dtype=torch.float64).to(mo.dtype), obcs)
+    ut = (0.8 * torch.randn((1, *n), generator=g, dtype=torch.float64)).to(mo.dtype)
+    vec = torch.randn((2, *n), generator=g, dtype=torch.float64).to(mo.dtype)
+    uvec = (0.8 * torch.randn((2, *n), generator=g, dtype=torch.float64)).to(mo.dtype)
+    var = Field("p", 1, mesh, {"domain": [dict(c, bc_val_opt=None) for c in cfg], "obstacle": None})
+    var.set_var_tensor(x.cuda())
+    fvec = Field("v", 2, mesh, {"domain": None, "obstacle": None}).set_var_tensor(vec.cuda())
+    name = "upwind" if lim == "compat" else lim
+    fdc = FDC({"div": {"limiter": name, "edge": False, "compat": lim != "upwind"}})
+
+    def want(u, target, bcs):
+        if lim == "upwind":
+            return O.div_upwind_intended(u, target, mo) if target.shape[0] == 1 else C.div_general_upwind(u, target, mo)
+        return O.apply_div(O.div_tables(u, target, mo, bcs, name), target, 2)
+
+    bad = []
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for tag, u in (("pos", 0.7), ("neg", -0.7), ("tensor", ut)):
+            r = same_bits(fdc.div(u.cuda() if isinstance(u, torch.Tensor) else u, var), want(u, x, obcs))
+            if not r:
+                bad.append(("pa_div", tag, r.why))
+        for tag, u in (("pos", 0.7), ("neg", -0.7), ("tensor", uvec)):
+            r = same_bits(fdc.div(u.cuda() if isinstance(u, torch.Tensor) else u, fvec), want(u, vec, []))
+            if not r:
+                bad.append(("pa_div_general", tag, r.why))
+    assert not bad, bad
 
 
 def test_rz_periodic_faces_raise_like_the_reference():

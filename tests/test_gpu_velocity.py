@@ -97,13 +97,13 @@ def test_upwind_step_and_stage_on_the_vector_kernel(n, dtype):
     assert run_case(n, dtype, "upwind", VECTOR_OPTIONS) == []
 
 
-@pytest.mark.parametrize("limiter", ["upwind", "quick", "none"])
+@pytest.mark.parametrize("limiter", ["upwind", "quick", "none", "minmod", "mc"])
 @pytest.mark.parametrize("n,dtype", GENERIC, ids=_ids)
 def test_step_and_stage_on_the_generic_kernel(n, dtype, limiter):
     assert run_case(n, dtype, limiter, [{}]) == []
 
 
-@pytest.mark.parametrize("limiter", ["upwind", "quick", "none"])
+@pytest.mark.parametrize("limiter", ["upwind", "quick", "none", "minmod", "mc"])
 def test_step_and_stage_with_a_periodic_axis_0(limiter):
     """the stage is the step, then k_rk_combine, then the fill; the velocity takes the generic kernel"""
     assert run_case([9, 14, 132], "double", limiter, [{}], bcnames=("xper",)) == []
